@@ -12,7 +12,14 @@ double-buffered Jacobi ordering (does not reproduce the reference field; shards 
 measured in the same run and reported under "jacobi"; the reference's own arithmetic (LSF_ARITH_STRICT, bit-identical
 results, 2 x slower) under "strict_arithmetic".
 
-    python bench.py --gpus N --steps K --warmup W [--mode gs|jacobi] [--size 512] [--dtype f64|f32]
+    python bench.py --gpus N --steps K --warmup W [--mode gs|jacobi] [--size 512] [--dtype f64|f32] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ..., with the
+roofline figures computed from the timed run's own kernel events).  --full adds everything else measured or checked at
+N = 1: the measured device-copy peak, the other ordering, the reference's arithmetic, the 256^3 / 1024^3 sizes, min/max
+flow, the committed and in-run FAST-vs-STRICT records and the CPU baseline (each still subject to its --no-* option).
+--dump-outputs DIR (N = 1) writes what the timed call returned after its last step to DIR/*.npy: a fixed, seeded sample of the
+field with its flat indices, the centre z plane, and the RMS trace of the timed sweeps.
 
 --dtype f32 (BASELINE configuration 5; Jacobi ordering only, 12 B per cell-update) is a secondary measurement:
 the headline line is the default fp64 run.
@@ -150,6 +157,33 @@ def cpu_baseline(n: int, slab: int = 48, sweeps: int = 8):
     }
 
 
+DUMP_SAMPLE = 1 << 20  # field points written by --dump-outputs when the field is larger than twice that
+DUMP_SEED = 20240511
+
+
+def dump_outputs(out_dir: str, phi, rep, npts: int) -> None:
+    """--dump-outputs: what the timed call hands its caller -- the field after its last sweep (updated in place) and the report's
+    RMS trace -- as .npy files in the field's own precision.  The field is sampled at fixed seeded flat indices (Fortran order,
+    i fastest; the same points in every run of the same size) and its centre z plane is written whole: < 20 MB at 512^3."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = phi.numel()
+    if n <= 2 * DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+    sample = phi[torch.from_numpy(idx).to(phi.device)].cpu().numpy()
+    np.save(os.path.join(out_dir, "phi_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "phi_sample_index.npy"), idx.astype(np.float64))  # exact: n < 2^53
+    if npts * npts * phi.element_size() <= (16 << 20):
+        k = npts // 2
+        plane = phi[k * npts * npts:(k + 1) * npts * npts].reshape(npts, npts).cpu().numpy()  # [j, i]
+        np.save(os.path.join(out_dir, "phi_plane_zmid.npy"), plane)
+    np.save(os.path.join(out_dir, "rms.npy"), np.asarray(rep.rms, dtype=np.float64))
+
+
 # ------------------------------------------------------------------------------------------------
 def main() -> None:
     ap = argparse.ArgumentParser()
@@ -164,6 +198,10 @@ def main() -> None:
                          "every rank owns a --size^3 block")
     ap.add_argument("--dtype", choices=("f64", "f32"), default="f64",
                     help="f32 = single-precision Jacobi path (BASELINE configuration 5); implies --mode jacobi")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every secondary measurement and check of an N = 1 run (see the module docstring)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: write the timed call's outputs after its last step to DIR/*.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary-ordering measurement")
     ap.add_argument("--no-sizes", action="store_true", help="skip the 256^3 / 1024^3 entries of a 512^3 run")
@@ -200,6 +238,11 @@ def main() -> None:
         with open(args.slab_worker, "w") as fh:
             json.dump(ent, fh)
         return
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs: single-GPU runs only (--gpus 1)")
+    if not args.full:
+        # a plain run measures its headline and nothing else (N > 1: the decomposed measurement below IS the headline)
+        args.no_cpu_baseline, args.no_secondary, args.no_sizes = True, True, True
     f32 = args.dtype == "f32"
     if f32:
         args.mode, args.no_secondary, args.no_cpu_baseline = "jacobi", True, True
@@ -276,12 +319,15 @@ def main() -> None:
             phi0 = phi0.to(torch.float32)
         phiS = phi0.clone()
         phi = phi0.clone()
+        last = {}  # report of the latest timed call
 
         def run(order_, sweeps, profile=False, arith=None):
             lib.lsf_profile(1 if profile else 0)
             rep = lsf.reinit(phi, None, None, nx, ny, nz, sweeps - 1, dx, h, tol=0.0, order=order_, arith=arith or args.arith,
                              phiS=phiS)
             assert rep.count == sweeps, (rep.count, sweeps)
+            if profile:
+                last["rep"] = rep
             return rep
 
         def timed(order_, arith=None, K_=None, W_=None, samples=1):
@@ -312,6 +358,8 @@ def main() -> None:
             return best
 
         seconds, prof = timed(order)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, phi, last["rep"], N)
         cells_total = float(nx - 1) * (ny - 1) * (nz - 1) * K * world
         parallelism = "1 GPU" if world == 1 else f"{world} independent replicas (exact Gauss-Seidel ordering does not shard)"
 
@@ -344,10 +392,11 @@ def main() -> None:
 
     # the roofline "also against a measured device-copy bandwidth" -- a 1 GiB streaming copy (16 bytes per lane
     # and access) timed in THIS run on THIS device, bytes read + bytes written per second of the fastest of 5 passes
+    # (--full only: a plain run reports null)
     peak_measured = None
     try:
         g_ = ctypes.c_double(0.0)
-        if lib.lsf_copy_bandwidth(1 << 30, 5, ctypes.byref(g_)) == 0 and g_.value > 0:
+        if args.full and lib.lsf_copy_bandwidth(1 << 30, 5, ctypes.byref(g_)) == 0 and g_.value > 0:
             peak_measured = g_.value
     except Exception:  # noqa: BLE001
         peak_measured = None
@@ -434,7 +483,7 @@ def main() -> None:
         out["rccl_ranks"] = _rccl_ranks(dist)  # world size as the RCCL backend reports it
     if res is not None:
         out["parity"] = headline_parity
-    if not f32 and args.arith == "fast":
+    if args.full and not f32 and args.arith == "fast":
         # how long the FAST arithmetic of `value` stays within north_star's 1e-10 RMS of the reference's field, per BASELINE
         # configuration (profiles/micro/fast_valid.py on the GPU; STRICT holds it for any number of sweeps)
         import glob

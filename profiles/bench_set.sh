@@ -5,7 +5,7 @@ set -u
 TAG=${1:-r02}
 D=gpurun_out/profiles_$TAG
 mkdir -p "$D"
-run() { local name=$1; shift; python3 bench.py "$@" 2> "$D/${TAG}_bench_$name.err" | grep '^{' | tail -1 > "$D/${TAG}_bench_$name.json"; echo "$name: $(cut -c1-160 "$D/${TAG}_bench_$name.json")"; }
+run() { local name=$1; shift; python3 bench.py --full "$@" 2> "$D/${TAG}_bench_$name.err" | grep '^{' | tail -1 > "$D/${TAG}_bench_$name.json"; echo "$name: $(cut -c1-160 "$D/${TAG}_bench_$name.json")"; }
 run default
 run steps20 --steps 20 --warmup 5
 run 256 --size 256 --steps 16 --warmup 16 --no-cpu-baseline

@@ -8,9 +8,9 @@ TAG=${1:-r01}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --full --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.log"
 # the fp32 Jacobi path (BASELINE configuration 5), same command shape
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_f32" -- python3 bench.py --dtype f32 > "$OUT/bench_f32_under_rocprof.json" 2> "$OUT/trace_f32.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_f32" -- python3 bench.py --full --dtype f32 > "$OUT/bench_f32_under_rocprof.json" 2> "$OUT/trace_f32.log"
 # the driver's own command (--steps 20 --warmup 5) under the kernel trace: its persist-kernel average must agree with the
 # roofline.avg_launch_us of the BENCH line
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_s20" -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > "$OUT/bench_s20_under_rocprof.json" 2> "$OUT/trace_s20.log"
