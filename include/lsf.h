@@ -117,6 +117,39 @@ int lsf_reinit_device(double *d_phi, const double *d_phiS, int nx, int ny, int n
                       double h, double tol, int mode, int first_raster, int *sweeps_done,
                       double *rms_trace, int trace_cap, void *stream);
 
+/* ---- narrow-band (tube) reinitialisation: reinit on the cells of a caller's mask only -------------
+ * No reference counterpart: the reference's reinit visits every interior cell, although the stages behind it (min/max flow,
+ * order-8 gradients, node advection) read phi only where phiNB / phiSB are 1.
+ *   LIST     the interior points (1..n-1 in each axis) with mask == 1 on entry, fixed for the whole call.  Any other mask
+ *            value means "not in the band"; a 1 on a wall point is ignored.  The mask is read once and never written.
+ *   phiS     phi on entry (subs.f90:731), or d_phiS when given (device seam); only its list cells are read.
+ *   a sweep  every list cell becomes phi + h * sgn * (1 - gM) (subs.f90:747-750; weno :489-711; phiSign :152-172) with all 19
+ *            stencil values taken from the field as it was at the start of the sweep (the Jacobi ordering).  Cells 4..n-5 take
+ *            WENO5, the others first-order differences, as in lsf_reinit.  Points outside LIST are NEVER written, wall points
+ *            included: the extrapolation boundary condition (subs.f90:859-897) is NOT applied.
+ *   RMS      sqrt(sum over list cells (new - old)^2 / nL), nL = length of LIST, summed in a fixed order (reproducible from run
+ *            to run).  NOT comparable with lsf_reinit's RMS, which divides by nx*ny*nz.
+ *   sweeps   at most iter+1; stops after the first sweep whose RMS is < tol (tol <= 0: never early).  A NaN RMS returns
+ *            LSF_ERR_NAN and phi holds the state after that sweep.  sweeps_done / rms_trace / trace_cap as in lsf_reinit.
+ *   empty    LIST empty: LSF_OK, sweeps_done = 0, nothing written.
+ *   mode     LSF_ORDER_JACOBI | LSF_ARITH_FAST or | LSF_ARITH_STRICT.  LSF_ORDER_GS is LSF_ERR_INVALID: a raster order has
+ *            no meaning on a list.  With LSF_ARITH_STRICT a sweep is, bit for bit, a full-grid Jacobi sweep whose result is
+ *            kept at the list cells only.
+ *   limits   a NULL mask, iter < 0, bad dims or more than 2^31 - 1 points are LSF_ERR_INVALID (list entries are 32-bit point
+ *            indices, like the min/max band's).
+ * Guidance: make the update mask WIDER than the band whose values are trusted.  List cells within three cells of the list's
+ * edge read frozen neighbours.  On the cube40 fixture after min/max flow, against a full-grid Jacobi run: with phiSB
+ * (|phi| < 8.1 dx) as the mask the cells with |phi| < 4.1 dx differ by 0 after 1 sweep, 1.8e-10 after 10, 1.2e-7 after 50 and
+ * 8.8e-7 after 100; with phiNB (|phi| < 4.1 dx) itself as the mask by 2.9e-4 after 10 sweeps.
+ * Work: beyond one pass over the mask and one copy of the field per call, nothing is proportional to the grid; a sweep visits
+ * the list cells only.  No speed is claimed here (the measurement is profiles/micro/reinit_band_time.py), and there is no
+ * automatic dispatch to the full-grid kernels of lsf_reinit. */
+int lsf_reinit_band(double *phi, const int32_t *mask, int nx, int ny, int nz, int iter, double dx, double h,
+                    double tol, int mode, int *sweeps_done, double *rms_trace, int trace_cap);
+int lsf_reinit_band_device(double *d_phi, const double *d_phiS, const int32_t *d_mask, int nx, int ny, int nz,
+                           int iter, double dx, double h, double tol, int mode, int *sweeps_done,
+                           double *rms_trace, int trace_cap, void *stream);
+
 /* ---- seam 2: min/max flow ---------------------------------------------------------------
  * Replaces the loop DO n = 1,iter ... END DO at set3d.f90:394-462 (secondDeriv subs.f90:370-407,
  * minMax subs.f90:413-483, narrowBand subs.f90:178-207), hoisted into one call.

@@ -58,6 +58,10 @@ SIGNATURES = {
                            POINTER(c_int), c_void_p, c_int]),
     "lsf_reinit_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double,
                                   c_int, c_int, POINTER(c_int), c_void_p, c_int, c_void_p]),
+    "lsf_reinit_band": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_int,
+                                POINTER(c_int), c_void_p, c_int]),
+    "lsf_reinit_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double,
+                                       c_int, POINTER(c_int), c_void_p, c_int, c_void_p]),
     "lsf_minmax": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double,
                            c_double, c_int, POINTER(c_int), c_void_p, c_int]),
     "lsf_minmax_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double,

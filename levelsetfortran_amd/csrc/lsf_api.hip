@@ -22,6 +22,7 @@
 #include "lsf_skew.hpp"
 #include "lsf_f32.hpp"
 #include "lsf_minmax_band.hpp"
+#include "lsf_reinit_band.hpp"
 
 using namespace lsf;
 
@@ -178,7 +179,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -724,6 +725,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 
 #include "lsf_host_minmax.hpp"
 
+#include "lsf_host_reinit_band.hpp"
+
 int box_ok(const lsf_box* b, const int lo[3], const int hi[3])
 {
     if (!b || !lo || !hi) return fail(LSF_ERR_INVALID, "NULL box/range");
@@ -1157,6 +1160,46 @@ int lsf_minmax(double* phi, int32_t* phiNB, int32_t* phiSB, int nx, int ny, int 
         g_err = keep;
     } else
         twin_drop(c.twin_phi), twin_drop(c.twin_nb), twin_drop(c.twin_sb);
+    return rc;
+}
+
+int lsf_reinit_band_device(double* d_phi, const double* d_phiS, const int32_t* d_mask, int nx, int ny, int nz, int iter, double dx,
+                           double h, double tol, int mode, int* sweeps_done, double* rms_trace, int trace_cap, void* stream)
+{
+    Trace trace_("lsf_reinit_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    return reinit_band_core(d_phi, d_phiS, d_mask, nx, ny, nz, iter, dx, h, tol, mode, sweeps_done, rms_trace, trace_cap,
+                            (hipStream_t)stream);
+}
+
+int lsf_reinit_band(double* phi, const int32_t* mask, int nx, int ny, int nz, int iter, double dx, double h, double tol, int mode,
+                    int* sweeps_done, double* rms_trace, int trace_cap)
+{
+    Trace trace_("lsf_reinit_band");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = check_dims(nx, ny, nz))) return rc;
+    if (!phi) return fail(LSF_ERR_INVALID, "phi is NULL");
+    if (!mask) return fail(LSF_ERR_INVALID, "mask is NULL");
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc;
+    // the mask is an input only: it travels through the twin of phiNB when it IS the array that twin stands for (the narrow band
+    // as the update mask), through the twin of phiSB otherwise (the stencil band, or any other array); never copied back
+    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+    const Slot sm = is_nb ? S_HNB : S_HSB;
+    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+    rc = reinit_band_core((double*)c.slot[S_HPHI].p, nullptr, (const int32_t*)c.slot[sm].p, nx, ny, nz, iter, dx, h, tol, mode, sweeps_done,
+                          rms_trace, trace_cap, nullptr);
+    if (rc == LSF_OK || rc == LSF_ERR_NAN) {
+        const std::string keep = g_err;
+        const int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, n * sizeof(double));
+        if (rc2) return rc2;
+        g_err = keep;
+    } else
+        twin_drop(c.twin_phi);
     return rc;
 }
 

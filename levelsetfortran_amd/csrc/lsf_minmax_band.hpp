@@ -33,7 +33,9 @@ constexpr int MB_SCAN = 2048; // points per block of the list build
 constexpr int MB_CH = 256;    // list entries per chunk (= threads per block of the iteration kernels)
 
 // List build, pass 1: block b scans points [2048 b, 2048 b + 2048) and leaves its list cells, in increasing p, in
-// staging[2048 b ...] and their number in counts[b].
+// staging[2048 b ...] and their number in counts[b].  MASK_ONLY: the membership rule is the caller's mask alone and phi is not
+// read (the list of lsf_reinit_band, lsf_reinit_band.hpp); false: the min/max rule, mask == 1 or |phi| < 4.1 dx.
+template <bool MASK_ONLY>
 static __global__ __launch_bounds__(256) void k_mb_collect(const double* __restrict__ phi, const int32_t* __restrict__ mask, int nx, int ny,
                                                     int nz, double dx, int* __restrict__ staging, int* __restrict__ counts)
 {
@@ -41,19 +43,20 @@ static __global__ __launch_bounds__(256) void k_mb_collect(const double* __restr
     const long sxy = (long)(nx + 1) * (ny + 1), n = sxy * (nz + 1);
     const long base = (long)blockIdx.x * MB_SCAN;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double tn = 4.1 * dx;
+    [[maybe_unused]] const double tn = 4.1 * dx;
     const int sx = nx + 1;
     const bool tiny = sxy <= 256;
     const int d256j = 256 / sx, d256i = 256 - d256j * sx;
     int i, j, k;
     point_ijk(base + threadIdx.x, nx + 1, ny + 1, n, i, j, k);
     // all loads of a thread's eight points before the first test (phi and the mask: 12 bytes per point, the whole cost of the pass)
-    double v[MB_SCAN / 256];
+    [[maybe_unused]] double v[MB_SCAN / 256];
     int32_t mk[MB_SCAN / 256];
 #pragma unroll
     for (int t = 0; t < MB_SCAN / 256; ++t) {
         const long p = min(base + t * 256 + threadIdx.x, n - 1);
-        v[t] = phi[p], mk[t] = mask[p];
+        mk[t] = mask[p];
+        if constexpr (!MASK_ONLY) v[t] = phi[p];
     }
     unsigned mine = 0u;
     int before[MB_SCAN / 256];
@@ -67,7 +70,8 @@ static __global__ __launch_bounds__(256) void k_mb_collect(const double* __restr
                 else step_ijk(i, j, k, d256i, d256j, 0, nx + 1, ny + 1);
             }
             const bool interior = i >= 1 && i <= nx - 1 && j >= 1 && j <= ny - 1 && k >= 1 && k <= nz - 1;
-            in = interior && (mk[t] == 1 || __builtin_fabs(v[t]) < tn);
+            if constexpr (MASK_ONLY) in = interior && mk[t] == 1;
+            else in = interior && (mk[t] == 1 || __builtin_fabs(v[t]) < tn);
         }
         const unsigned long long b = __ballot(in);
         before[t] = __popcll(b & ((1ull << lane) - 1ull));

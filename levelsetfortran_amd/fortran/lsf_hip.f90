@@ -12,6 +12,8 @@
 !                                                        replaces the loop set3d.f90:218-268
 !   advectNodes(phi,phiSB,nx,ny,nz,dx,xLo,surfXX,nSurfNode,iter)
 !                                                        replaces set3d.f90:470-479 and :487-501
+!   reinitBand(phi,mask,nx,ny,nz,iter,dx,h)             no reference counterpart: reinit on the cells
+!                                                        with mask == 1 only (include/lsf.h: lsf_reinit_band)
 !   stlRead(surfX,nSurfNode,surfElem,filename,nSurfElem,surfElemTag,surfOrder,nBndComp,nBndElem,bndNormal)
 !                                                        replaces subs.f90:17-121 (same list)
 !
@@ -69,6 +71,7 @@ USE, INTRINSIC :: iso_c_binding
 IMPLICIT NONE
 PRIVATE
 PUBLIC :: reinit, narrowBand, minmaxFlow, phi0Init, advectNodes, lsf_env_real, lsf_env_int, lsf_pad_cells
+PUBLIC :: reinitBand
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
 INTEGER(c_int), PARAMETER :: LSF_OK = 0, LSF_ERR_NAN = 1
@@ -97,6 +100,18 @@ INTERFACE
       REAL(c_double), INTENT(OUT) :: rms_trace(*)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_reinit
+   ! int lsf_reinit_band(double*,const int32_t*,int,int,int,int,double,double,double,int,int*,double*,int)
+   FUNCTION lsf_reinit_band(phi,mask,nx,ny,nz,iter,dx,h,tol,mode,sweeps_done,rms_trace,trace_cap) &
+            BIND(C,NAME='lsf_reinit_band') RESULT(rc)
+      IMPORT :: c_int, c_double
+      REAL(c_double), INTENT(INOUT) :: phi(*)
+      INTEGER(c_int), INTENT(IN) :: mask(*)
+      INTEGER(c_int), VALUE :: nx,ny,nz,iter,mode,trace_cap
+      REAL(c_double), VALUE :: dx,h,tol
+      INTEGER(c_int), INTENT(OUT) :: sweeps_done
+      REAL(c_double), INTENT(OUT) :: rms_trace(*)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_reinit_band
    ! int lsf_reinit_multi(double*,int,int,int,int,double,double,double,int,const int*,int,const int[3],int*,double*,int)
    FUNCTION lsf_reinit_multi(phi,nx,ny,nz,iter,dx,h,tol,mode,devices,ndev,dims,sweeps_done,rms_trace,trace_cap) &
             BIND(C,NAME='lsf_reinit_multi') RESULT(rc)
@@ -389,6 +404,43 @@ PRINT*
 DEALLOCATE(trace)
 
 END SUBROUTINE reinit
+
+!*************************************************************************************!
+! Reinitialize on the cells of a mask only (include/lsf.h: lsf_reinit_band; no reference
+! counterpart).  mask: e.g. phiSB of narrowBand; the interior cells where it is 1 are
+! updated, every other point keeps its value.  Always the Jacobi ordering (a raster order
+! has no meaning on a list of cells); the arithmetic is the run's (arith / LSF_ARITH).
+! The residual printed is the RMS change over the listed cells.
+!*************************************************************************************!
+SUBROUTINE reinitBand(phi,mask,nx,ny,nz,iter,dx,h)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,iter
+REAL,INTENT(IN) :: dx,h
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: mask
+REAL,ALLOCATABLE :: trace(:)
+INTEGER(c_int) :: rc,done,mode
+INTEGER :: n
+
+ALLOCATE(trace(iter+1))
+mode = lsf_mode()
+mode = IOR(IAND(mode,LSF_ARITH_STRICT),LSF_ORDER_JACOBI)
+rc = lsf_reinit_band(phi,mask,nx,ny,nz,iter,dx,h,1.E-5,mode,done,trace,iter+1)
+IF (rc /= LSF_OK .AND. rc /= LSF_ERR_NAN) CALL lsf_fail('lsf_reinit_band',rc)
+
+! the lines of reinit, sweep by sweep (subs.f90:915-926)
+DO n = 0,done-1
+   IF (trace(n+1) < 1.E-5) THEN
+      PRINT*, " Distance function time integration has reached steady state "
+      EXIT
+   END IF
+   PRINT*, " Iteration: ",n," ", " RMS Error: ",trace(n+1)
+   IF (isnan(trace(n+1))) STOP
+END DO
+PRINT*
+DEALLOCATE(trace)
+
+END SUBROUTINE reinitBand
 
 !*************************************************************************************!
 ! Determine Narrow Band  (same dummy arguments as subs.f90:178-184)

@@ -7,6 +7,10 @@ they replace (citations are into /root/reference):
   narrowBand(nx, ny, nz, dx, phi, phiNB, phiSB)                 subs.f90:178-207
   minmaxFlow(phi, phiNB, phiSB, nx, ny, nz, iter, dx, h1)       set3d.f90:394-462 (hoisted)
 
+and, without a reference counterpart, reinit on the cells of a mask only:
+
+  reinitBand(phi, mask, nx, ny, nz, iter, dx, h)                include/lsf.h: lsf_reinit_band
+
 Fields are updated IN PLACE like the INTENT(INOUT) dummies of the reference.  A field is either
   * a numpy float64 array, Fortran-ordered with shape (nx+1, ny+1, nz+1) (or 1-D of that size):
     the host seam -- the library copies it to HBM and back (lsf_reinit / lsf_minmax), or
@@ -28,7 +32,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "narrowBand", "minmaxFlow", "phi0Init", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -148,6 +152,49 @@ def reinit(phi, gradPhi=None, gradPhiMag=None, nx: int = 0, ny: int = 0, nz: int
             p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
             rc = lib.lsf_reinit(p, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode, ctypes.byref(done),
                                 trace.ctypes.data, cap)
+    n = done.value
+    rep = SweepReport(n, [float(v) for v in trace[:n]], bool(n and trace[n - 1] < tol))
+    if echo:
+        for ln in rep.lines(0, "  Distance function time integration has reached steady state "):
+            print(ln)
+        print()
+        sys.stdout.flush()
+    _lib.check(rc)
+    return rep
+
+
+def reinitBand(phi, mask, nx: int, ny: int, nz: int, iter: int, dx: float, h: float, *, tol: float = REINIT_TOL,
+               arith: str = "fast", phiS=None, echo: bool = False) -> SweepReport:
+    """Reinitialisation on the cells of `mask` only (include/lsf.h: lsf_reinit_band); `phi` is updated in place.
+
+    mask: int32, same layout as phi (e.g. phiSB of narrowBand); the interior points where it is 1 are updated with the
+    Jacobi ordering of reinit, every other point -- wall points included -- keeps its value and no boundary condition is
+    applied.  Runs at most iter+1 sweeps and stops after the first whose RMS over the LIST cells is < tol (not comparable
+    with reinit's RMS over the whole grid).  phiS (device seam only): the sign field to use instead of phi on entry, which
+    makes a call continue an earlier one.  Make the mask wider than the band whose values are trusted: cells within three
+    cells of its edge read frozen neighbours.  Raises LsfNaNError on a NaN RMS.
+    """
+    lib = _lib.load()
+    cap = int(iter) + 1
+    trace = np.zeros(max(cap, 1), dtype=np.float64)
+    done = ctypes.c_int(0)
+    mode = mode_word("jacobi", arith)  # a raster order has no meaning on a list
+    if _is_torch(phi):
+        import torch
+
+        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+        ps = _dev_ptr(phiS, torch.float64, nx, ny, nz, "phiS") if phiS is not None else None
+        st = _stream_and_device(phi)
+        rc = lib.lsf_reinit_band_device(p, ps, m, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode,
+                                        ctypes.byref(done), trace.ctypes.data, cap, st)
+    else:
+        if phiS is not None:
+            raise ValueError("phiS is only available on the device seam")
+        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
+        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+        rc = lib.lsf_reinit_band(p, m, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode, ctypes.byref(done),
+                                 trace.ctypes.data, cap)
     n = done.value
     rep = SweepReport(n, [float(v) for v in trace[:n]], bool(n and trace[n - 1] < tol))
     if echo:
