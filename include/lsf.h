@@ -186,6 +186,53 @@ int lsf_phi0_device(double *d_phi, int nx, int ny, int nz, double dx, const doub
                     const double minX[3], const double maxX[3], const double *surfX, int nSurfNode,
                     const int32_t *surfElem, int nSurfElem, void *stream);
 
+/* ---- exact signed distance from the triangle mesh, clamped to a tube -------------------------------
+ * No reference counterpart: lsf_phi0 above restates the reference's inside/outside test (nearest CENTROID, a smeared +-1), which
+ * carries no sub-cell position of the surface.  This is the distance to the triangles themselves.  surfX(nSurfNode,3) and
+ * surfElem(nSurfElem,3) are 1-based Fortran-ordered HOST arrays exactly as lsf_phi0 takes them; the grid point (i,j,k) is
+ * xLo + (i,j,k)*dx (set3d.f90:168-170).  info may be NULL.
+ *   far      width * dx, computed once on the host.
+ *   TUBE     the grid points, wall points included, whose distance to the nearest non-degenerate triangle is <= far.  A tube
+ *            point receives the exact Euclidean point-to-triangle distance d (closest point over the face, edge and vertex
+ *            regions, fp64), negative where the offset from the closest point has a negative dot product with the angle-weighted
+ *            pseudonormal of the closest FEATURE: the face normal, the sum of the two unit face normals of an edge, the sum of
+ *            the unit face normals weighted by their angles at a vertex.  A zero dot product counts as positive.
+ *   ties     between triangles the smaller distance wins; at equal distance bits the positive sign wins.  The field is
+ *            bit-identical from run to run and between the two seams.
+ *   far      every other point receives +-far: the sign of the last tube point met when walking its (i,j) column from k = 0, and
+ *   points   before the first tube point the exterior sign, + if the mesh's signed volume is >= 0, else -.  Correct because two
+ *            neighbouring grid points on opposite sides of the surface are both within dx of it, hence both in the tube: this
+ *            is why width >= 1.5 is required.  THE ONE ASSUMPTION: the k = 0 plane lies outside the body or inside the tube.
+ *            The reference's grid pads 10 cells around the surface (set3d.f90:148-157), so there it always does.
+ *   flags    LSF_MESH_UNSIGNED: no pseudonormals, no requirements on the mesh; tube points get d, all others +far.
+ *   mesh     prepared on the host once per call.  A triangle with a zero-length normal is DEGENERATE: skipped, part of no
+ *            pseudonormal.  An edge pseudonormal is computed once per edge, the lower triangle index first in the sum, and
+ *            copied to both triangles; vertex sums run in triangle order.  An edge is DEFECTIVE unless exactly two
+ *            non-degenerate triangles share it and traverse it in opposite directions.
+ *   info     [0] tube points  [1] degenerate triangles skipped  [2] defective edges  [3] non-degenerate triangles whose padded
+ *            box misses the grid.  Written on LSF_OK only.
+ *   errors   LSF_ERR_INVALID, all detected before anything is written: width not finite or < 1.5, dx <= 0, bad dims, a NULL
+ *            pointer, nSurfElem < 1, an index outside 1..nSurfNode, a non-finite coordinate, an unknown flag, and a SIGNED call
+ *            on a mesh with defective edges (the message names their number; the unsigned call accepts such a mesh).  No device:
+ *            LSF_ERR_NO_DEVICE -- there is no CPU fallback.
+ *   seams    lsf_mesh_distance treats the twin of phi exactly as lsf_phi0 does under lsf_mirror (phi is an output).
+ * lsf_mesh_check is host code only and needs no device (like lsf_stl_read): info[1] and info[2] as above, info[0] = info[3] = 0,
+ * and the signed volume sum(v0 . (v1 x v2)) / 6.
+ * Guidance: the field is a CLAMPED distance, |phi| <= far.  lsf_reinit, lsf_narrowband, lsf_minmax and lsf_reinit_band take it as
+ * it is (narrowBand's 4.1 dx / 8.1 dx bands want width > 8.1 to be read off the field directly; lsf_reinit grows the distance
+ * outwards from any width).  Work: a triangle costs the points of its padded bounding box, (2*width)^3 for a small one, so a wider
+ * tube is paid for per triangle; beyond one fill and one pass over the field nothing is proportional to the grid. */
+#define LSF_MESH_UNSIGNED 1 /* flags */
+#define LSF_MESH_INFO_LEN 4
+int lsf_mesh_check(const double *surfX, int nSurfNode, const int32_t *surfElem, int nSurfElem,
+                   int64_t info[LSF_MESH_INFO_LEN], double *signed_volume);
+int lsf_mesh_distance(double *phi, int nx, int ny, int nz, double dx, const double xLo[3], const double *surfX,
+                      int nSurfNode, const int32_t *surfElem, int nSurfElem, double width, int flags,
+                      int64_t info[LSF_MESH_INFO_LEN]);
+int lsf_mesh_distance_device(double *d_phi, int nx, int ny, int nz, double dx, const double xLo[3], const double *surfX,
+                             int nSurfNode, const int32_t *surfElem, int nSurfElem, double width, int flags,
+                             int64_t info[LSF_MESH_INFO_LEN], void *stream);
+
 /* ---- post-smoothing gradients + surface-node advection (the step after the hot path) ----------
  * Replaces set3d.f90:470-501: firstDeriv order 8 (subs.f90:309-347, with its
  * quirks) on the cells of phiSB, then every surface node is moved by x += phiSurf * gradPhiSurf with

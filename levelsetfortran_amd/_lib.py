@@ -20,6 +20,7 @@ LSF_ARITH_FAST, LSF_ARITH_STRICT = 0x000, 0x100
 
 
 LSF_MIRROR_TRUST, LSF_MIRROR_LAZY = 1, 2  # include/lsf.h: lsf_mirror flags
+LSF_MESH_UNSIGNED, LSF_MESH_INFO_LEN = 1, 4  # include/lsf.h: lsf_mesh_distance
 LSF_TRANSPORT_PEER, LSF_TRANSPORT_RCCL, LSF_TRANSPORT_MOCK = 0, 1, 2  # include/lsf.h: lsf_multi_configure
 
 
@@ -72,6 +73,11 @@ SIGNATURES = {
                          c_void_p, c_int]),
     "lsf_phi0_device": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                 c_void_p, c_int, c_void_p]),
+    "lsf_mesh_check": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, POINTER(c_double)]),
+    "lsf_mesh_distance": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p, c_int, c_double,
+                                  c_int, c_void_p]),
+    "lsf_mesh_distance_device": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                         c_double, c_int, c_void_p, c_void_p]),
     "lsf_advect_nodes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int]),
     "lsf_advect_nodes_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int,
                                         c_int, c_void_p]),

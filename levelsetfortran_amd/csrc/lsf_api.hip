@@ -2,6 +2,7 @@
 // arithmetic lives in lsf_cell.hpp / lsf_kernels.hpp.  There is deliberately no CPU fallback.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -23,6 +24,7 @@
 #include "lsf_f32.hpp"
 #include "lsf_minmax_band.hpp"
 #include "lsf_reinit_band.hpp"
+#include "lsf_mesh_distance.hpp"
 
 using namespace lsf;
 
@@ -179,7 +181,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -726,6 +728,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_minmax.hpp"
 
 #include "lsf_host_reinit_band.hpp"
+
+#include "lsf_host_mesh.hpp"
 
 int box_ok(const lsf_box* b, const int lo[3], const int hi[3])
 {
@@ -1307,6 +1311,47 @@ int lsf_phi0(double* phi, int nx, int ny, int nz, double dx, const double xLo[3]
     rc = lsf_phi0_device((double*)c.slot[S_HPHI].p, nx, ny, nz, dx, xLo, minX, maxX, surfX, nSurfNode, surfElem,
                          nSurfElem, nullptr);
     if (rc) return rc;
+    return twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
+}
+
+int lsf_mesh_check(const double* surfX, int nSurfNode, const int32_t* surfElem, int nSurfElem, int64_t info[LSF_MESH_INFO_LEN],
+                   double* signed_volume)
+{
+    Trace trace_("lsf_mesh_check");
+    MeshPrep M;
+    const int rc = mesh_prepare(surfX, nSurfNode, surfElem, nSurfElem, false, M);
+    if (rc) return rc;
+    if (info) info[0] = 0, info[1] = M.ndegenerate, info[2] = M.ndefective, info[3] = 0;
+    if (signed_volume) *signed_volume = M.volume;
+    return LSF_OK;
+}
+
+int lsf_mesh_distance_device(double* d_phi, int nx, int ny, int nz, double dx, const double xLo[3], const double* surfX, int nSurfNode,
+                             const int32_t* surfElem, int nSurfElem, double width, int flags, int64_t info[LSF_MESH_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_mesh_distance_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (!d_phi) return fail(LSF_ERR_INVALID, "phi is NULL");
+    MeshPrep M;
+    if ((rc = mesh_distance_prepare(nx, ny, nz, dx, xLo, surfX, nSurfNode, surfElem, nSurfElem, width, flags, M))) return rc;
+    return mesh_distance_run(d_phi, nx, ny, nz, dx, xLo, width, flags, M, info, (hipStream_t)stream);
+}
+
+int lsf_mesh_distance(double* phi, int nx, int ny, int nz, double dx, const double xLo[3], const double* surfX, int nSurfNode,
+                      const int32_t* surfElem, int nSurfElem, double width, int flags, int64_t info[LSF_MESH_INFO_LEN])
+{
+    Trace trace_("lsf_mesh_distance");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (!phi) return fail(LSF_ERR_INVALID, "phi is NULL");
+    MeshPrep M;
+    if ((rc = mesh_distance_prepare(nx, ny, nz, dx, xLo, surfX, nSurfNode, surfElem, nSurfElem, width, flags, M))) return rc;
+    Ctx& c = ctx();
+    const size_t bytes = (size_t)(nx + 1) * (ny + 1) * (nz + 1) * sizeof(double);
+    if ((rc = twin_claim(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // (an un-synced result of another array goes home first)
+    twin_drop(c.twin_phi);                                                // phi is an output here, as in lsf_phi0
+    if ((rc = mesh_distance_run((double*)c.slot[S_HPHI].p, nx, ny, nz, dx, xLo, width, flags, M, info, nullptr))) return rc;
     return twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
 }
 

@@ -14,6 +14,9 @@
 !                                                        replaces set3d.f90:470-479 and :487-501
 !   reinitBand(phi,mask,nx,ny,nz,iter,dx,h)             no reference counterpart: reinit on the cells
 !                                                        with mask == 1 only (include/lsf.h: lsf_reinit_band)
+!   meshDistance(phi,nx,ny,nz,dx,xLo,surfX,nSurfNode,surfElem,nSurfElem,width)
+!                                                        no reference counterpart: exact signed distance from the
+!                                                        triangles, clamped at width*dx (include/lsf.h: lsf_mesh_distance)
 !   stlRead(surfX,nSurfNode,surfElem,filename,nSurfElem,surfElemTag,surfOrder,nBndComp,nBndElem,bndNormal)
 !                                                        replaces subs.f90:17-121 (same list)
 !
@@ -72,6 +75,7 @@ IMPLICIT NONE
 PRIVATE
 PUBLIC :: reinit, narrowBand, minmaxFlow, phi0Init, advectNodes, lsf_env_real, lsf_env_int, lsf_pad_cells
 PUBLIC :: reinitBand
+PUBLIC :: meshDistance
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
 INTEGER(c_int), PARAMETER :: LSF_OK = 0, LSF_ERR_NAN = 1
@@ -160,6 +164,18 @@ INTERFACE
       INTEGER(c_int), INTENT(IN) :: surfElem(*)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_phi0
+   ! int lsf_mesh_distance(double*,int,int,int,double,const double[3],const double*,int,const int32_t*,int,double,int,int64_t[4])
+   FUNCTION lsf_mesh_distance(phi,nx,ny,nz,dx,xLo,surfX,nSurfNode,surfElem,nSurfElem,width,flags,info) &
+            BIND(C,NAME='lsf_mesh_distance') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t
+      REAL(c_double), INTENT(INOUT) :: phi(*)
+      INTEGER(c_int), VALUE :: nx,ny,nz,nSurfNode,nSurfElem,flags
+      REAL(c_double), VALUE :: dx,width
+      REAL(c_double), INTENT(IN) :: xLo(3),surfX(*)
+      INTEGER(c_int), INTENT(IN) :: surfElem(*)
+      INTEGER(c_int64_t), INTENT(OUT) :: info(4)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_mesh_distance
    FUNCTION lsf_advect_nodes(phi,phiSB,nx,ny,nz,dx,xLo,surfXX,nSurfNode,iters) &
             BIND(C,NAME='lsf_advect_nodes') RESULT(rc)
       IMPORT :: c_int, c_double
@@ -509,6 +525,29 @@ rc = lsf_phi0(phi,nx,ny,nz,dx,xLo,xMin,xMax,surfX,nSurfNode,surfElem,nSurfElem)
 IF (rc /= LSF_OK) CALL lsf_fail('lsf_phi0',rc)
 
 END SUBROUTINE phi0Init
+
+!*************************************************************************************!
+! Exact signed distance from the triangle mesh (include/lsf.h: lsf_mesh_distance; no
+! reference counterpart).  phi is an output: the distance to the nearest triangle,
+! negative inside, within width cells of the surface and +-width*dx elsewhere.  surfX and
+! surfElem as stlRead returns them.  A mesh with defective edges fails through lsf_fail.
+!*************************************************************************************!
+SUBROUTINE meshDistance(phi,nx,ny,nz,dx,xLo,surfX,nSurfNode,surfElem,nSurfElem,width)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+INTEGER*4,INTENT(IN) :: nSurfNode,nSurfElem
+REAL,INTENT(IN) :: dx,xLo(3),width
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: phi
+REAL,INTENT(IN) :: surfX(nSurfNode,3)
+INTEGER*4,INTENT(IN) :: surfElem(nSurfElem,3)
+INTEGER(c_int64_t) :: info(4)
+INTEGER(c_int) :: rc
+
+CALL lsf_set_mirror()
+rc = lsf_mesh_distance(phi,nx,ny,nz,dx,xLo,surfX,nSurfNode,surfElem,nSurfElem,width,0_c_int,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_mesh_distance',rc)
+
+END SUBROUTINE meshDistance
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

@@ -11,6 +11,11 @@ and, without a reference counterpart, reinit on the cells of a mask only:
 
   reinitBand(phi, mask, nx, ny, nz, iter, dx, h)                include/lsf.h: lsf_reinit_band
 
+and the exact signed distance from the triangle mesh, clamped to a tube (the reference has the centroid test of phi0Init only):
+
+  meshDistance(phi, nx, ny, nz, dx, xLo, surfX, surfElem)       include/lsf.h: lsf_mesh_distance
+  meshCheck(surfX, surfElem)                                    include/lsf.h: lsf_mesh_check (host only)
+
 Fields are updated IN PLACE like the INTENT(INOUT) dummies of the reference.  A field is either
   * a numpy float64 array, Fortran-ordered with shape (nx+1, ny+1, nz+1) (or 1-D of that size):
     the host seam -- the library copies it to HBM and back (lsf_reinit / lsf_minmax), or
@@ -25,14 +30,14 @@ from __future__ import annotations
 import ctypes
 import sys
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -282,6 +287,72 @@ def phi0Init(phi, nx: int, ny: int, nz: int, dx: float, xLo, minX, maxX, surfX, 
     else:
         rc = lib.lsf_phi0(_host_ptr(phi, np.float64, nx, ny, nz, "phi"), *args)
     _lib.check(rc)
+
+
+class MeshInfo(NamedTuple):
+    """The counts of lsf_mesh_distance / lsf_mesh_check (include/lsf.h: info[0..3]); volume: lsf_mesh_check only."""
+    tube_points: int
+    degenerate_triangles: int
+    defective_edges: int
+    triangles_off_grid: int
+    signed_volume: Optional[float] = None
+
+
+def _surface(surfX, surfElem):
+    """(surfX, surfElem) as the Fortran-ordered float64 (nSurfNode,3) / int32 (nSurfElem,3) arrays the library reads."""
+    sX, sE = np.asarray(surfX), np.asarray(surfElem)
+    if sX.ndim != 2 or sX.shape[1] != 3 or sX.shape[0] < 1:
+        raise ValueError("surfX must have shape (nSurfNode, 3) with nSurfNode >= 1")
+    if sE.ndim != 2 or sE.shape[1] != 3 or sE.shape[0] < 1:
+        raise ValueError("surfElem must have shape (nSurfElem, 3) with nSurfElem >= 1")
+    if sX.dtype.kind != "f" or sE.dtype.kind not in "iu":
+        raise TypeError("surfX must be a float array and surfElem an integer array")
+    return np.asfortranarray(sX, dtype=np.float64), np.asfortranarray(sE, dtype=np.int32)
+
+
+def meshCheck(surfX, surfElem) -> MeshInfo:
+    """Degenerate triangles, defective edges and the signed volume of a mesh (include/lsf.h: lsf_mesh_check).  Host code
+    only: no device is needed.  A signed meshDistance wants defective_edges == 0."""
+    sX, sE = _surface(surfX, surfElem)
+    info = np.zeros(_lib.LSF_MESH_INFO_LEN, dtype=np.int64)
+    vol = ctypes.c_double(0.0)
+    _lib.check(_lib.load().lsf_mesh_check(sX.ctypes.data, sX.shape[0], sE.ctypes.data, sE.shape[0], info.ctypes.data, ctypes.byref(vol)))
+    return MeshInfo(*(int(v) for v in info), vol.value)
+
+
+def meshDistance(phi, nx: int, ny: int, nz: int, dx: float, xLo, surfX, surfElem, *, width: float = 4.0, signed: bool = True) -> MeshInfo:
+    """Exact signed distance from the triangle mesh, clamped to a tube of `width` cells (include/lsf.h: lsf_mesh_distance).
+
+    phi (numpy F-ordered or torch CUDA, see module docstring) is an output: points within width*dx of the surface receive
+    the Euclidean distance to the nearest triangle, negative inside (angle-weighted pseudonormals), every other point
+    +-width*dx with the sign carried along its k column.  surfX / surfElem as for phi0Init; the grid point is xLo + i*dx.
+    signed=False: the unsigned distance, no requirement on the mesh (a signed call refuses a mesh with defective edges,
+    see meshCheck).  Returns the counts of the call.  The field is clamped, not a distance everywhere: reinit takes it as
+    its start and needs far fewer sweeps than from phi0Init's smeared sign.
+    """
+    lib = _lib.load()
+    sX, sE = _surface(surfX, surfElem)
+    lo = np.ascontiguousarray(xLo, dtype=np.float64)
+    if lo.shape != (3,):
+        raise ValueError("xLo must hold 3 values")
+    width, dx = float(width), float(dx)
+    if not (np.isfinite(width) and width >= 1.5):
+        raise ValueError("width must be finite and >= 1.5 (cells)")
+    if not (np.isfinite(dx) and dx > 0.0):
+        raise ValueError("dx must be > 0")
+    info = np.zeros(_lib.LSF_MESH_INFO_LEN, dtype=np.int64)
+    args = (nx, ny, nz, dx, lo.ctypes.data, sX.ctypes.data, sX.shape[0], sE.ctypes.data, sE.shape[0], width,
+            0 if signed else _lib.LSF_MESH_UNSIGNED, info.ctypes.data)
+    if _is_torch(phi):
+        import torch
+
+        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        st = _stream_and_device(phi)
+        rc = lib.lsf_mesh_distance_device(p, *args, st)
+    else:
+        rc = lib.lsf_mesh_distance(_host_ptr(phi, np.float64, nx, ny, nz, "phi"), *args)
+    _lib.check(rc)
+    return MeshInfo(*(int(v) for v in info))
 
 
 def advectNodes(phi, phiSB, nx: int, ny: int, nz: int, dx: float, xLo, surfXX, iter: int = 1000) -> None:
