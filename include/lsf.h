@@ -233,6 +233,55 @@ int lsf_mesh_distance_device(double *d_phi, int nx, int ny, int nz, double dx, c
                              int nSurfNode, const int32_t *surfElem, int nSurfElem, double width, int flags,
                              int64_t info[LSF_MESH_INFO_LEN], void *stream);
 
+/* ---- distance fill: first-order fast sweeping outwards from a frozen band --------------------------
+ * No reference counterpart.  Solves |grad phi| = 1 on every point that is not FROZEN, with the frozen points as boundary data, by
+ * rounds of 8 in-place raster sweeps of the first-order Godunov update: what turns the clamped field of lsf_mesh_distance, or a
+ * field that is trusted on a mask only, into a distance on the whole grid without the pseudo-time sweeps of lsf_reinit.  The field
+ * layout is that of every other entry point.  rounds_done, changed_trace and frozen_points may be NULL.
+ *   FROZEN   mask == NULL: the points, wall points included, with |phi| < far on entry; far = band * dx, computed once on the host.
+ *            For a field of lsf_mesh_distance(width = w), band = w selects its tube.  With a mask: the points with mask == 1, and
+ *            band is ignored.  The mask is read once and never written.  Frozen points are never written.
+ *   sign     every other point keeps the sign it has on entry (phi < 0 is negative; anything else, -0.0 included, is positive);
+ *            its magnitude is replaced.
+ *   round    8 in-place raster sweeps over all points 0..n of each axis (walls are solved, not extrapolated), in the direction
+ *            order of the reference's reinit (subs.f90:740-855): (+,+,+) (+,+,-) (+,-,-) (-,-,-) (-,+,-) (-,-,+) (-,+,+) (+,-,+).
+ *            Non-frozen points start at +inf.
+ *   visit    of a non-frozen point, u being the magnitudes as they are at that moment of the sweep:
+ *              x = min(u(i-1), u(i+1)), likewise y and z; a neighbour outside the grid counts as +inf;
+ *              a = min(min(x,y),z); c = max(max(x,y),z); b = max(min(x,y), min(max(x,y),z));
+ *              a = +inf: nothing happens.  Otherwise t = a + dx;
+ *              if t > b:     d = a - b; t = ((a + b) + sqrt(2*(dx*dx) - d*d)) * 0.5;
+ *              if that t > c: t = (((a + b) + c) + sqrt(max(3*(dx*dx) - (((a-b)*(a-b) + (a-c)*(a-c)) + (b-c)*(b-c)), 0))) / 3;
+ *              new = min(old, t).
+ *            Evaluated exactly as written, left to right, without contraction; sqrt and / are the IEEE ones.
+ *   trace    changed_trace[r], r < trace_cap: the number of visits of round r with new < old (an integer: no arrival order in it).
+ *   stop     after the first round whose count is 0 (that round is counted) or after max_rounds; rounds_done = rounds run.
+ *            Reaching max_rounds is LSF_OK: the caller reads the last trace entry.  After round 1 every point is finite.
+ *   result   field, rounds_done and trace are those of the serial loops above, bit for bit, on both seams, on any stream, from
+ *            run to run -- after every round, not only at the fixed point (tests/distance_fill_ref.py is that serial statement).
+ *   errors   LSF_ERR_INVALID, all detected before phi is written, the offending count in lsf_last_error() where there is one:
+ *            a NULL phi; nx, ny or nz < 1 or more than 2^31 - 1 points; dx not finite or <= 0; mask == NULL with band not finite
+ *            or <= 0; max_rounds < 1; no frozen point; a non-finite value on a frozen point; two axis neighbours of opposite
+ *            sign that are not both frozen (the frozen set must separate the signs).  No device: LSF_ERR_NO_DEVICE -- there is no
+ *            CPU fallback.
+ *   seams    lsf_distance_fill treats phi as in/out and the mask as an input under lsf_mirror exactly as lsf_reinit_band does.
+ *            lsf_distance_fill_device returns after the stream is synchronised (the host reads one count per round).
+ * Guidance: the scheme is FIRST ORDER away from the frozen set: against the closed forms of the test inputs the largest error far
+ * from the surface is 0.98 - 1.65 dx (box and sphere, bands of 3.5 and 1.5 cells), growing with the distance travelled; the values
+ * inside the band are the caller's, untouched.  That is enough for lsf_narrowband / lsf_minmax / lsf_write_vti when the band covers
+ * what they read to full accuracy (band >= 8.1 for narrowBand's stencil band).  lsf_reinit afterwards is optional and shorter: on
+ * the cube40 fixture at 62^3 the CPU oracle stops after 367 sweeps from the filled field, 565 from the clamped one (no other count
+ * is promised).  Convergence took 2 - 4 rounds on the test inputs; a shape with many concave turns needs more.
+ * Workspace beyond the caller's field: one bit per point -- a 32-bit word per 32 points of a row, rows padded to a whole word, i.e.
+ * 4 * ceil((nx+1)/32) * (ny+1) * (nz+1) bytes -- plus 32 bytes of counters; no second copy of the field.  (Below one byte per point
+ * for nx >= 3.)  Work: a round is 8 * (tiles_x + tiles_y + tiles_z - 2) dependent launches of 32 x 8 x 8-point tiles.
+ * Not timed on hardware. */
+int lsf_distance_fill(double *phi, const int32_t *mask, int nx, int ny, int nz, double dx, double band, int max_rounds,
+                      int *rounds_done, int64_t *changed_trace, int trace_cap, int64_t *frozen_points);
+int lsf_distance_fill_device(double *d_phi, const int32_t *d_mask, int nx, int ny, int nz, double dx, double band,
+                             int max_rounds, int *rounds_done, int64_t *changed_trace, int trace_cap,
+                             int64_t *frozen_points, void *stream);
+
 /* ---- post-smoothing gradients + surface-node advection (the step after the hot path) ----------
  * Replaces set3d.f90:470-501: firstDeriv order 8 (subs.f90:309-347, with its
  * quirks) on the cells of phiSB, then every surface node is moved by x += phiSurf * gradPhiSurf with

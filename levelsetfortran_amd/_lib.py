@@ -78,6 +78,10 @@ SIGNATURES = {
                                   c_int, c_void_p]),
     "lsf_mesh_distance_device": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                          c_double, c_int, c_void_p, c_void_p]),
+    "lsf_distance_fill": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p, c_int,
+                                  POINTER(ctypes.c_int64)]),
+    "lsf_distance_fill_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p,
+                                         c_int, POINTER(ctypes.c_int64), c_void_p]),
     "lsf_advect_nodes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int]),
     "lsf_advect_nodes_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int,
                                         c_int, c_void_p]),

@@ -25,6 +25,7 @@
 #include "lsf_minmax_band.hpp"
 #include "lsf_reinit_band.hpp"
 #include "lsf_mesh_distance.hpp"
+#include "lsf_distance_fill.hpp"
 
 using namespace lsf;
 
@@ -181,7 +182,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -730,6 +731,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_reinit_band.hpp"
 
 #include "lsf_host_mesh.hpp"
+
+#include "lsf_host_distance_fill.hpp"
 
 int box_ok(const lsf_box* b, const int lo[3], const int hi[3])
 {
@@ -1353,6 +1356,44 @@ int lsf_mesh_distance(double* phi, int nx, int ny, int nz, double dx, const doub
     twin_drop(c.twin_phi);                                                // phi is an output here, as in lsf_phi0
     if ((rc = mesh_distance_run((double*)c.slot[S_HPHI].p, nx, ny, nz, dx, xLo, width, flags, M, info, nullptr))) return rc;
     return twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
+}
+
+int lsf_distance_fill_device(double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, double band, int max_rounds,
+                             int* rounds_done, int64_t* changed_trace, int trace_cap, int64_t* frozen_points, void* stream)
+{
+    Trace trace_("lsf_distance_fill_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = distance_fill_args_ok(d_phi, d_mask, nx, ny, nz, dx, band, max_rounds))) return rc;
+    return distance_fill_core(d_phi, d_mask, nx, ny, nz, dx, band, max_rounds, rounds_done, changed_trace, trace_cap, frozen_points,
+                              (hipStream_t)stream);
+}
+
+int lsf_distance_fill(double* phi, const int32_t* mask, int nx, int ny, int nz, double dx, double band, int max_rounds, int* rounds_done,
+                      int64_t* changed_trace, int trace_cap, int64_t* frozen_points)
+{
+    Trace trace_("lsf_distance_fill");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = distance_fill_args_ok(phi, mask, nx, ny, nz, dx, band, max_rounds))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc;
+    // the mask is an input only and travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin
+    // of phiSB otherwise; never copied back
+    const int32_t* d_mask = nullptr;
+    if (mask) {
+        const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+        Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+        const Slot sm = is_nb ? S_HNB : S_HSB;
+        if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+        d_mask = (const int32_t*)c.slot[sm].p;
+    }
+    rc = distance_fill_core((double*)c.slot[S_HPHI].p, d_mask, nx, ny, nz, dx, band, max_rounds, rounds_done, changed_trace, trace_cap,
+                            frozen_points, nullptr);
+    if (rc == LSF_OK) return twin_out(c, c.twin_phi, S_HPHI, phi, n * sizeof(double));
+    twin_drop(c.twin_phi);
+    return rc;
 }
 
 int lsf_advect_nodes_device(const double* d_phi, const int32_t* d_phiSB, int nx, int ny, int nz, double dx,

@@ -17,6 +17,8 @@
 !   meshDistance(phi,nx,ny,nz,dx,xLo,surfX,nSurfNode,surfElem,nSurfElem,width)
 !                                                        no reference counterpart: exact signed distance from the
 !                                                        triangles, clamped at width*dx (include/lsf.h: lsf_mesh_distance)
+!   distanceFill(phi,nx,ny,nz,dx,band)                   no reference counterpart: first-order distance on every point with
+!                                                        |phi| >= band*dx by fast sweeping (include/lsf.h: lsf_distance_fill)
 !   stlRead(surfX,nSurfNode,surfElem,filename,nSurfElem,surfElemTag,surfOrder,nBndComp,nBndElem,bndNormal)
 !                                                        replaces subs.f90:17-121 (same list)
 !
@@ -76,6 +78,7 @@ PRIVATE
 PUBLIC :: reinit, narrowBand, minmaxFlow, phi0Init, advectNodes, lsf_env_real, lsf_env_int, lsf_pad_cells
 PUBLIC :: reinitBand
 PUBLIC :: meshDistance
+PUBLIC :: distanceFill
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
 INTEGER(c_int), PARAMETER :: LSF_OK = 0, LSF_ERR_NAN = 1
@@ -176,6 +179,18 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: info(4)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_mesh_distance
+   ! int lsf_distance_fill(double*,const int32_t*,int,int,int,double,double,int,int*,int64_t*,int,int64_t*)
+   FUNCTION lsf_distance_fill(phi,mask,nx,ny,nz,dx,band,max_rounds,rounds_done,changed_trace,trace_cap,frozen_points) &
+            BIND(C,NAME='lsf_distance_fill') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(INOUT) :: phi(*)
+      TYPE(c_ptr), VALUE :: mask             ! NULL: the frozen set is |phi| < band*dx
+      INTEGER(c_int), VALUE :: nx,ny,nz,max_rounds,trace_cap
+      REAL(c_double), VALUE :: dx,band
+      INTEGER(c_int), INTENT(OUT) :: rounds_done
+      INTEGER(c_int64_t), INTENT(OUT) :: changed_trace(*),frozen_points
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_distance_fill
    FUNCTION lsf_advect_nodes(phi,phiSB,nx,ny,nz,dx,xLo,surfXX,nSurfNode,iters) &
             BIND(C,NAME='lsf_advect_nodes') RESULT(rc)
       IMPORT :: c_int, c_double
@@ -548,6 +563,30 @@ rc = lsf_mesh_distance(phi,nx,ny,nz,dx,xLo,surfX,nSurfNode,surfElem,nSurfElem,wi
 IF (rc /= LSF_OK) CALL lsf_fail('lsf_mesh_distance',rc)
 
 END SUBROUTINE meshDistance
+
+!*************************************************************************************!
+! First-order distance outside a frozen band by fast sweeping (include/lsf.h:
+! lsf_distance_fill; no reference counterpart).  The points with |phi| < band*dx on entry
+! (the tube of meshDistance(width = band)) are never written; every other point keeps its
+! sign and receives the distance grown outwards from them, at most 64 rounds of 8 raster
+! sweeps.  Prints the rounds run and the visits the last one lowered (0: converged).
+!*************************************************************************************!
+SUBROUTINE distanceFill(phi,nx,ny,nz,dx,band)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+REAL,INTENT(IN) :: dx,band
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: phi
+INTEGER(c_int), PARAMETER :: max_rounds = 64
+INTEGER(c_int64_t) :: trace(max_rounds),frozen
+INTEGER(c_int) :: rc,done
+
+CALL lsf_set_mirror()
+rc = lsf_distance_fill(phi,c_null_ptr,nx,ny,nz,dx,band,max_rounds,done,trace,max_rounds,frozen)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_distance_fill',rc)
+PRINT*, " Distance fill: ",done," rounds, ",frozen," frozen points, last round lowered ",trace(done)
+PRINT*
+
+END SUBROUTINE distanceFill
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call
