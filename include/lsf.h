@@ -282,6 +282,67 @@ int lsf_distance_fill_device(double *d_phi, const int32_t *d_mask, int nx, int n
                              int max_rounds, int *rounds_done, int64_t *changed_trace, int trace_cap,
                              int64_t *frozen_points, void *stream);
 
+/* ---- level-set transport: WENO5 / TVD-RK3 advection by a velocity field and along the normal ----------
+ * No reference counterpart ("Currently has no capability to do moving geometry", the reference's README).  Advances
+ *     phi_t + u . grad(phi) + F |grad(phi)| = 0
+ * by `steps` explicit steps of size dt on the whole grid; lsf_reinit / lsf_reinit_band repair the distance property afterwards.
+ * The field layout is that of every other entry point.  steps_done, cfl and change_trace may be NULL.
+ *   fields   u, v, w (the velocity) and speed (F, the speed along the outward normal grad(phi)/|grad(phi)|: F > 0 grows the
+ *            region phi < 0) have phi's layout: values AT the grid points.  u, v, w are given together or all NULL; speed may be
+ *            NULL; at least one of the two groups is given.  All four are inputs: read, never written, and frozen for the whole
+ *            call -- a caller with a time-dependent velocity calls once per step on the device seam.
+ *   mode     LSF_ORDER_JACOBI | LSF_ARITH_STRICT or | LSF_ARITH_FAST.  LSF_ORDER_GS is LSF_ERR_INVALID (every stage reads the
+ *            field as it was when the stage began), as in lsf_reinit_band.
+ *   D-, D+   every interior cell (1..n-1 on each axis) takes its one-sided derivatives dmA, dpA on each axis A from the
+ *            reference's weno (subs.f90:489-711) WITHOUT the p5 = 0 of its y axis (subs.f90:576 belongs to the reference's
+ *            reinit, not to this operator): WENO5 on all three axes when 4 <= i <= nx-5 and likewise j and k (the reference's
+ *            joint rule), first-order differences (c - m)/dx, (p - c)/dx on all three axes otherwise.
+ *   STRICT   evaluated as written, left to right, without contraction; / and sqrt are the IEEE ones:
+ *              pos(a) = a > 0 ? a : 0;  neg(a) = a < 0 ? a : 0
+ *              T  = ((pos(u)*dmx + neg(u)*dpx) + (pos(v)*dmy + neg(v)*dpy)) + (pos(w)*dmz + neg(w)*dpz)    (absent without u, v, w)
+ *              gA = m*m, m = max(max(dmA*sg, dpA*-sg), 0), sg = speed > 0 ? 1 : -1     (the Godunov term of subs.f90:684-692,
+ *                   switched on the sign of the speed instead of the sign of phi)
+ *              N  = speed * sqrt((gX + gY) + gZ)                                                           (absent without speed)
+ *              R  = T, N or T + N;    t = phi - dt*R
+ *   FAST     the same operator in the restructured arithmetic of LSF_ARITH_FAST (differences scaled by dx, one reciprocal per
+ *            WENO side, FMA): ~1e-16 per stage from STRICT.
+ *   stages   S(a) = t computed from the field a at every interior cell:
+ *              LSF_ADVECT_EULER  phi <- S(phi)
+ *              LSF_ADVECT_RK3    a = S(phi);  b = 0.75*phi + 0.25*S(a);  phi <- (1./3.)*phi + (2./3.)*S(b)     (Shu-Osher)
+ *            After every stage the wall points of the stage's output take the extrapolation boundary condition of
+ *            subs.f90:859-897 (as after a sweep of lsf_reinit).
+ *   trace    change_trace[s], s < trace_cap: the largest |new - old| over the interior cells of step s (0-based), NaN if any of them
+ *            is NaN -- no order of summation in it: bit-identical between the seams, on any stream, from run to run.  A NaN ends the
+ *            call with LSF_ERR_NAN after that step; steps_done counts it and phi holds the state after it.
+ *   cfl      (dt * max over ALL points of (|u| + |v| + |w| + |speed|)) / dx, absent fields left out, computed once per call.  It is
+ *            REPORTED, never judged: the caller keeps it below 1 (RK3 with WENO5 is stable there; tests run at 0.5).  Written on
+ *            LSF_OK and on LSF_ERR_NAN.
+ *   steps=0  LSF_OK, steps_done = 0, phi untouched, cfl still reported.
+ *   result   with LSF_ARITH_STRICT field, trace and cfl are those of the statement above bit for bit (tests/advect_ref.py is that
+ *            statement in numpy), on both seams.  One call of n steps equals n calls of one step: no state between calls.
+ *   errors   LSF_ERR_INVALID, all detected before phi is written, with the count in lsf_last_error() where there is one: a NULL
+ *            phi; u, v, w not given together; neither velocity nor speed; nx, ny or nz < 2, a k-plane above 2 GB or more than
+ *            2^31 - 1 points (the dimensions lsf_reinit_band refuses); dx or dt not finite or <= 0; steps < 0; an unknown scheme;
+ *            LSF_ORDER_GS or an unknown ordering; a non-finite value in u, v, w or speed (counted by the same pass that finds the
+ *            maximum for cfl).  No device: LSF_ERR_NO_DEVICE -- there is no CPU fallback.
+ *   seams    lsf_advect_field treats phi as in/out under lsf_mirror exactly as lsf_reinit_band does, and u, v, w, speed as that
+ *            call treats its mask: inputs only, never copied back; taken from the host, or under LSF_MIRROR_TRUST / LAZY from their
+ *            device twin where they have a current one.
+ *            lsf_advect_field_device returns after the stream is synchronised (the host reads the step counter).
+ * Workspace beyond the caller's fields: two fields for LSF_ADVECT_RK3 (stage 3 writes the caller's field in place: it reads the old
+ * phi at its own point only), one for LSF_ADVECT_EULER; the host seam adds one field per input given.  The result always ends in
+ * the caller's field.  Work: one launch per stage over the interior + the boundary condition, one small launch per step for the
+ * trace.  Out of scope here: a band or mask variant, fp32, multi-GPU, a CFL-chosen dt.
+ * Not timed on hardware yet: no speed is claimed (the measurement is profiles/micro/advect_field_time.py). */
+#define LSF_ADVECT_RK3 0 /* scheme */
+#define LSF_ADVECT_EULER 1
+int lsf_advect_field(double *phi, const double *u, const double *v, const double *w, const double *speed, int nx, int ny,
+                     int nz, double dx, double dt, int steps, int scheme, int mode, int *steps_done, double *cfl,
+                     double *change_trace, int trace_cap);
+int lsf_advect_field_device(double *d_phi, const double *d_u, const double *d_v, const double *d_w, const double *d_speed,
+                            int nx, int ny, int nz, double dx, double dt, int steps, int scheme, int mode, int *steps_done,
+                            double *cfl, double *change_trace, int trace_cap, void *stream);
+
 /* ---- post-smoothing gradients + surface-node advection (the step after the hot path) ----------
  * Replaces set3d.f90:470-501: firstDeriv order 8 (subs.f90:309-347, with its
  * quirks) on the cells of phiSB, then every surface node is moved by x += phiSurf * gradPhiSurf with

@@ -21,6 +21,7 @@ LSF_ARITH_FAST, LSF_ARITH_STRICT = 0x000, 0x100
 
 LSF_MIRROR_TRUST, LSF_MIRROR_LAZY = 1, 2  # include/lsf.h: lsf_mirror flags
 LSF_MESH_UNSIGNED, LSF_MESH_INFO_LEN = 1, 4  # include/lsf.h: lsf_mesh_distance
+LSF_ADVECT_RK3, LSF_ADVECT_EULER = 0, 1  # include/lsf.h: lsf_advect_field
 LSF_TRANSPORT_PEER, LSF_TRANSPORT_RCCL, LSF_TRANSPORT_MOCK = 0, 1, 2  # include/lsf.h: lsf_multi_configure
 
 
@@ -82,6 +83,10 @@ SIGNATURES = {
                                   POINTER(ctypes.c_int64)]),
     "lsf_distance_fill_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p,
                                          c_int, POINTER(ctypes.c_int64), c_void_p]),
+    "lsf_advect_field": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_int, c_int,
+                                 POINTER(c_int), POINTER(c_double), c_void_p, c_int]),
+    "lsf_advect_field_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_int,
+                                        c_int, POINTER(c_int), POINTER(c_double), c_void_p, c_int, c_void_p]),
     "lsf_advect_nodes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int]),
     "lsf_advect_nodes_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int,
                                         c_int, c_void_p]),

@@ -26,6 +26,7 @@
 #include "lsf_reinit_band.hpp"
 #include "lsf_mesh_distance.hpp"
 #include "lsf_distance_fill.hpp"
+#include "lsf_advect_field.hpp"
 
 using namespace lsf;
 
@@ -182,7 +183,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -733,6 +734,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_mesh.hpp"
 
 #include "lsf_host_distance_fill.hpp"
+
+#include "lsf_host_advect_field.hpp"
 
 int box_ok(const lsf_box* b, const int lo[3], const int hi[3])
 {
@@ -1393,6 +1396,61 @@ int lsf_distance_fill(double* phi, const int32_t* mask, int nx, int ny, int nz, 
                             frozen_points, nullptr);
     if (rc == LSF_OK) return twin_out(c, c.twin_phi, S_HPHI, phi, n * sizeof(double));
     twin_drop(c.twin_phi);
+    return rc;
+}
+
+int lsf_advect_field_device(double* d_phi, const double* d_u, const double* d_v, const double* d_w, const double* d_speed, int nx, int ny, int nz,
+                            double dx, double dt, int steps, int scheme, int mode, int* steps_done, double* cfl, double* change_trace,
+                            int trace_cap, void* stream)
+{
+    Trace trace_("lsf_advect_field_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = advect_field_args_ok(d_phi, d_u, d_v, d_w, d_speed, nx, ny, nz, dx, dt, steps, scheme, mode))) return rc;
+    if ((rc = advect_field_scan(d_u, d_v, d_w, d_speed, nx, ny, nz, dx, dt, cfl, (hipStream_t)stream))) return rc;
+    if (steps_done) *steps_done = 0;
+    if (steps == 0) return LSF_OK;
+    return advect_field_steps(d_phi, d_u, d_v, d_w, d_speed, nx, ny, nz, dx, dt, steps, scheme, mode, steps_done, change_trace, trace_cap,
+                              (hipStream_t)stream);
+}
+
+int lsf_advect_field(double* phi, const double* u, const double* v, const double* w, const double* speed, int nx, int ny, int nz, double dx,
+                     double dt, int steps, int scheme, int mode, int* steps_done, double* cfl, double* change_trace, int trace_cap)
+{
+    Trace trace_("lsf_advect_field");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = advect_field_args_ok(phi, u, v, w, speed, nx, ny, nz, dx, dt, steps, scheme, mode))) return rc;
+    Ctx& c = ctx();
+    const size_t bytes = (size_t)(nx + 1) * (ny + 1) * (nz + 1) * sizeof(double);
+    // u, v, w, speed are inputs only and travel like the mask of lsf_reinit_band, never copied back: each into a slot of its own,
+    // from the device twin where the caller lets twins be trusted (lsf_mirror TRUST / LAZY: under LAZY the host copy may be the older
+    // one) and the array has a current one, from the host otherwise -- without lsf_mirror the host copy is the truth: an address may
+    // have been a twin's in an earlier call and hold other values now.  Staged before phi's twin is touched: an input may be the very
+    // array a twin stands for, phi's included.
+    const double* h_in[4] = {u, v, w, speed};
+    const Slot s_in[4] = {S_AF_U, S_AF_V, S_AF_W, S_AF_F};
+    const double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int q = 0; q < 4; ++q) {
+        if (!h_in[q]) continue;
+        if ((rc = ws(c.slot[s_in[q]], bytes))) return rc;
+        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, h_in[q], bytes) : nullptr;
+        HIPCHK(hipMemcpy(c.slot[s_in[q]].p, twin ? twin : (const void*)h_in[q], bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        d_in[q] = (const double*)c.slot[s_in[q]].p;
+    }
+    if ((rc = advect_field_scan(d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, cfl, nullptr))) return rc;
+    if (steps_done) *steps_done = 0;
+    if (steps == 0) return LSF_OK;
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc;
+    rc = advect_field_steps((double*)c.slot[S_HPHI].p, d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, steps, scheme, mode, steps_done,
+                            change_trace, trace_cap, nullptr);
+    if (rc == LSF_OK || rc == LSF_ERR_NAN) {
+        const std::string keep = g_err;
+        const int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
+        if (rc2) return rc2;
+        g_err = keep;
+    } else
+        twin_drop(c.twin_phi);
     return rc;
 }
 

@@ -1,0 +1,141 @@
+// lsf_host_advect_field.hpp -- host side of lsf_advect_field (kernels and design: lsf_advect_field.hpp): validation, the scan of the
+// inputs (CFL number, non-finite values) and the steps, one plain launch per stage.  Included by lsf_api.hip inside its anonymous
+// namespace.
+#pragma once
+
+// what can be decided without the device; nothing is written anywhere before this and the scan have passed
+int advect_field_args_ok(const void* phi, const void* u, const void* v, const void* w, const void* speed, int nx, int ny, int nz, double dx,
+                         double dt, int steps, int scheme, int mode)
+{
+    if (!phi) return fail(LSF_ERR_INVALID, "phi is NULL");
+    const int nvel = (u != nullptr) + (v != nullptr) + (w != nullptr);
+    if (nvel != 0 && nvel != 3) return fail(LSF_ERR_INVALID, "lsf_advect_field: u, v, w are given together or all NULL (" + std::to_string(nvel) + " of 3 given)");
+    if (!nvel && !speed) return fail(LSF_ERR_INVALID, "lsf_advect_field: neither a velocity (u, v, w) nor a speed is given");
+    const int rc = check_dims(nx, ny, nz);
+    if (rc) return rc;
+    if ((double)(nx + 1.0) * (ny + 1.0) * (nz + 1.0) > 2147483647.0) return fail(LSF_ERR_INVALID, "lsf_advect_field: more than 2^31 - 1 points");
+    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "dx must be finite and > 0");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(LSF_ERR_INVALID, "lsf_advect_field: dt must be finite and > 0");
+    if (steps < 0) return fail(LSF_ERR_INVALID, "lsf_advect_field: steps must be >= 0");
+    if (scheme != LSF_ADVECT_RK3 && scheme != LSF_ADVECT_EULER) return fail(LSF_ERR_INVALID, "lsf_advect_field: unknown scheme (LSF_ADVECT_RK3 or LSF_ADVECT_EULER)");
+    const int order = mode & LSF_ORDER_MASK;
+    if (order == LSF_ORDER_GS)
+        return fail(LSF_ERR_INVALID, "lsf_advect_field: LSF_ORDER_GS has no meaning for an explicit step (every stage reads the field as it was); "
+                                     "pass LSF_ORDER_JACOBI");
+    if (order != LSF_ORDER_JACOBI) return fail(LSF_ERR_INVALID, "unknown ordering");
+    return LSF_OK;
+}
+
+// read-only: cfl = (dt * max over all points (|u| + |v| + |w| + |speed|)) / dx; a non-finite input is LSF_ERR_INVALID with its count
+int advect_field_scan(const double* d_u, const double* d_v, const double* d_w, const double* d_f, int nx, int ny, int nz, double dx, double dt,
+                      double* cfl, hipStream_t st)
+{
+    int rc;
+    Ctx& c = ctx();
+    const long n = (long)(nx + 1) * (ny + 1) * (nz + 1);
+    const int nb = (int)std::min<long>(ADV_SCAN_BLOCKS, (n + 255) / 256);
+    if ((rc = ws(c.slot[S_PART2], (size_t)nb * 16))) return rc;
+    double* pmax = (double*)c.slot[S_PART2].p;
+    unsigned long long* pcnt = (unsigned long long*)(pmax + nb);
+    hipLaunchKernelGGL(k_advect_scan, dim3((unsigned)nb), dim3(256), 0, st, d_u, d_v, d_w, d_f, n, pmax, pcnt);
+    HIPCHK(hipGetLastError());
+    std::vector<double> h((size_t)2 * nb);
+    HIPCHK(hipMemcpyAsync(h.data(), pmax, (size_t)nb * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    double m = 0.0;
+    unsigned long long bad = 0;
+    for (int b = 0; b < nb; ++b) {
+        unsigned long long k;
+        std::memcpy(&k, &h[(size_t)nb + b], sizeof k);
+        bad += k;
+        m = h[b] > m ? h[b] : m;
+    }
+    if (bad) return fail(LSF_ERR_INVALID, "lsf_advect_field: " + std::to_string(bad) + " non-finite value(s) in u, v, w, speed");
+    if (cfl) *cfl = (dt * m) / dx;
+    return LSF_OK;
+}
+
+// one stage launch: the instance for the arithmetic and the terms present
+void advect_stage_launch(bool strict, const double* A, double* B, const double* P0, const double* d_u, const double* d_v, const double* d_w,
+                         const double* d_f, int nx, int ny, int nz, double dx, double dt, double c_old, double c_new, unsigned long long* part,
+                         const int* ctl, int nbx, int nby, int nbz, hipStream_t st)
+{
+    const dim3 grid((unsigned)(((long)nbx * nby * nbz + 7) & ~7L)), blk(ADV_BX, ADV_BY);
+#define LSF_ADV_CALL(S, HV, HF) \
+    hipLaunchKernelGGL((k_advect_stage<S, HV, HF>), grid, blk, 0, st, A, B, P0, d_u, d_v, d_w, d_f, nx, ny, nz, dx, dt, c_old, c_new, part, ctl, nbx, nby, nbz)
+    const bool hv = d_u != nullptr, hf = d_f != nullptr;
+    if (strict) {
+        if (hv && hf) LSF_ADV_CALL(true, true, true);
+        else if (hv) LSF_ADV_CALL(true, true, false);
+        else LSF_ADV_CALL(true, false, true);
+    } else {
+        if (hv && hf) LSF_ADV_CALL(false, true, true);
+        else if (hv) LSF_ADV_CALL(false, true, false);
+        else LSF_ADV_CALL(false, false, true);
+    }
+#undef LSF_ADV_CALL
+}
+
+// the steps (arguments validated, inputs scanned, steps >= 1).  Workspace: one field for Euler, two for RK3.
+int advect_field_steps(double* d_phi, const double* d_u, const double* d_v, const double* d_w, const double* d_f, int nx, int ny, int nz, double dx,
+                       double dt, int steps, int scheme, int mode, int* steps_done, double* change_trace, int trace_cap, hipStream_t st)
+{
+    int rc;
+    Ctx& c = ctx();
+    const bool strict = (mode & LSF_ARITH_STRICT) != 0, rk3 = scheme == LSF_ADVECT_RK3;
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    const int nbx = cdiv(nx - 1, ADV_BX), nby = cdiv(ny - 1, ADV_BY), nbz = cdiv(nz - 1, ADV_KC);
+    const long nblk = (long)nbx * nby * nbz;
+    if (nblk > 0x7ffffff0L) return fail(LSF_ERR_INVALID, "lsf_advect_field: too many blocks for one launch");
+    const Box bx{nx + 1, ny + 1, nz + 1, 0, 0, 0, nx, ny, nz};
+    const int blo[3] = {0, 0, 0}, bhi[3] = {nx + 1, ny + 1, nz + 1};
+    unsigned bfaces = 0;
+    const dim3 bgrid = bc_grid(bx, blo, bhi, &bfaces); // the whole grid: all six faces
+    const long n_bc_part = (long)bgrid.x * bgrid.y * bgrid.z;
+    const int tcap = change_trace ? std::max(0, std::min(steps, trace_cap)) : 0;
+    if ((rc = ws(c.slot[S_PONG], n * sizeof(double)))) return rc;
+    if (rk3 && (rc = ws(c.slot[S_PONG2], n * sizeof(double)))) return rc;
+    if ((rc = ws(c.slot[S_PART], (size_t)(nblk + n_bc_part) * sizeof(double)))) return rc;
+    if ((rc = ws(c.slot[S_CTL], 64))) return rc;
+    if ((rc = ws(c.slot[S_TRACE], (size_t)std::max(tcap, 1) * sizeof(double)))) return rc;
+    double* w1 = (double*)c.slot[S_PONG].p;
+    double* w2 = rk3 ? (double*)c.slot[S_PONG2].p : nullptr;
+    unsigned long long* part = (unsigned long long*)c.slot[S_PART].p;
+    double* part_bc = (double*)(part + nblk); // k_bc's sums of squares: written, never read
+    int* ctl = (int*)c.slot[S_CTL].p;
+    double* d_trace = (double*)c.slot[S_TRACE].p;
+    HIPCHK(hipMemsetAsync(ctl, 0, 64, st));
+
+    auto stage = [&](const double* A, double* B, const double* P0, double c_old, double c_new, bool last) {
+        advect_stage_launch(strict, A, B, P0, d_u, d_v, d_w, d_f, nx, ny, nz, dx, dt, c_old, c_new, last ? part : nullptr, ctl, nbx, nby, nbz, st);
+        // the extrapolation boundary condition on the stage's output (subs.f90:859-897)
+        hipLaunchKernelGGL(k_bc<double>, bgrid, dim3(64), 0, st, A, B, bx, 0, 0, 0, nx + 1, ny + 1, nz + 1, dx, part_bc, (const int*)ctl, 0, bfaces);
+    };
+    double* bufs[2] = {d_phi, w1};
+    int host_ctl[3] = {0, 0, 0};
+    for (int s = 0; s < steps; ++s) {
+        if (rk3) {
+            stage(d_phi, w1, nullptr, 0.0, 1.0, false);
+            stage(w1, w2, d_phi, 0.75, 0.25, false);
+            stage(w2, d_phi, d_phi, 1. / 3., 2. / 3., true); // in place: a lane reads the old phi at its own point only
+        } else {
+            stage(bufs[s & 1], bufs[(s + 1) & 1], nullptr, 0.0, 1.0, true);
+        }
+        hipLaunchKernelGGL(k_advect_finish, dim3(1), dim3(RED_T), 0, st, (const unsigned long long*)part, nblk, d_trace, tcap, ctl);
+        if ((s + 1) % CHECK_EVERY == 0 && s + 1 < steps) {
+            HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (host_ctl[0]) break;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int nst = host_ctl[1];
+    if (!rk3 && (nst & 1)) HIPCHK(hipMemcpyAsync(d_phi, w1, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (tcap > 0 && nst > 0) HIPCHK(hipMemcpyAsync(change_trace, d_trace, sizeof(double) * (size_t)std::min(nst, tcap), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (steps_done) *steps_done = nst;
+    if (host_ctl[2]) return fail(LSF_ERR_NAN, "lsf_advect_field: the field became NaN in step " + std::to_string(nst - 1) + " (0-based)");
+    return LSF_OK;
+}

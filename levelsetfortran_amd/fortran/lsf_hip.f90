@@ -19,6 +19,8 @@
 !                                                        triangles, clamped at width*dx (include/lsf.h: lsf_mesh_distance)
 !   distanceFill(phi,nx,ny,nz,dx,band)                   no reference counterpart: first-order distance on every point with
 !                                                        |phi| >= band*dx by fast sweeping (include/lsf.h: lsf_distance_fill)
+!   advectField(phi,u,v,w,nx,ny,nz,dx,dt,steps)          no reference counterpart: transport of phi by the velocity field
+!                                                        (u,v,w), WENO5 / TVD-RK3 (include/lsf.h: lsf_advect_field)
 !   stlRead(surfX,nSurfNode,surfElem,filename,nSurfElem,surfElemTag,surfOrder,nBndComp,nBndElem,bndNormal)
 !                                                        replaces subs.f90:17-121 (same list)
 !
@@ -79,6 +81,7 @@ PUBLIC :: reinit, narrowBand, minmaxFlow, phi0Init, advectNodes, lsf_env_real, l
 PUBLIC :: reinitBand
 PUBLIC :: meshDistance
 PUBLIC :: distanceFill
+PUBLIC :: advectField
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
 INTEGER(c_int), PARAMETER :: LSF_OK = 0, LSF_ERR_NAN = 1
@@ -191,6 +194,21 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: changed_trace(*),frozen_points
       INTEGER(c_int) :: rc
    END FUNCTION lsf_distance_fill
+   ! int lsf_advect_field(double*,const double*,const double*,const double*,const double*,int,int,int,double,double,int,int,int,
+   !                      int*,double*,double*,int)
+   FUNCTION lsf_advect_field(phi,u,v,w,speed,nx,ny,nz,dx,dt,steps,scheme,mode,steps_done,cfl,change_trace,trace_cap) &
+            BIND(C,NAME='lsf_advect_field') RESULT(rc)
+      IMPORT :: c_int, c_double, c_ptr
+      REAL(c_double), INTENT(INOUT) :: phi(*)
+      REAL(c_double), INTENT(IN) :: u(*),v(*),w(*)
+      TYPE(c_ptr), VALUE :: speed            ! NULL: no motion along the normal
+      INTEGER(c_int), VALUE :: nx,ny,nz,steps,scheme,mode,trace_cap
+      REAL(c_double), VALUE :: dx,dt
+      INTEGER(c_int), INTENT(OUT) :: steps_done
+      REAL(c_double), INTENT(OUT) :: cfl
+      REAL(c_double), INTENT(OUT) :: change_trace(*)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_advect_field
    FUNCTION lsf_advect_nodes(phi,phiSB,nx,ny,nz,dx,xLo,surfXX,nSurfNode,iters) &
             BIND(C,NAME='lsf_advect_nodes') RESULT(rc)
       IMPORT :: c_int, c_double
@@ -587,6 +605,40 @@ PRINT*, " Distance fill: ",done," rounds, ",frozen," frozen points, last round l
 PRINT*
 
 END SUBROUTINE distanceFill
+
+!*************************************************************************************!
+! Transport of the level set by a velocity field, phi_t + u.grad(phi) = 0 (include/lsf.h:
+! lsf_advect_field; no reference counterpart): `steps` steps of size dt, WENO5 one-sided
+! derivatives, TVD-RK3, the reference's own arithmetic (LSF_ARITH_STRICT), the
+! extrapolation boundary condition after every stage.  u, v, w have phi's shape and are
+! read only.  The CFL number is printed, not judged: keep dt*max(|u|+|v|+|w|)/dx below 1.
+! A NaN stops the run like the reference's reinit (subs.f90:926).
+!*************************************************************************************!
+SUBROUTINE advectField(phi,u,v,w,nx,ny,nz,dx,dt,steps)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,steps
+REAL,INTENT(IN) :: dx,dt
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: phi
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: u,v,w
+INTEGER(c_int), PARAMETER :: LSF_ADVECT_RK3 = 0
+REAL,ALLOCATABLE :: trace(:)
+REAL :: cfl
+INTEGER(c_int) :: rc,done,mode
+
+ALLOCATE(trace(MAX(steps,1)))
+trace = 0.
+cfl = 0.
+done = 0
+CALL lsf_set_mirror()
+mode = IOR(LSF_ARITH_STRICT,LSF_ORDER_JACOBI)
+rc = lsf_advect_field(phi,u,v,w,c_null_ptr,nx,ny,nz,dx,dt,steps,LSF_ADVECT_RK3,mode,done,cfl,trace,MAX(steps,1))
+IF (rc /= LSF_OK .AND. rc /= LSF_ERR_NAN) CALL lsf_fail('lsf_advect_field',rc)
+PRINT*, " Level-set transport: ",done," steps, CFL ",cfl,", last change ",trace(MAX(done,1))
+PRINT*
+IF (rc == LSF_ERR_NAN) STOP
+DEALLOCATE(trace)
+
+END SUBROUTINE advectField
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

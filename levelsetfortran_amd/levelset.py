@@ -41,7 +41,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "advectField", "AdvectReport", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -403,6 +403,72 @@ def distanceFill(phi, nx: int, ny: int, nz: int, dx: float, *, band: Optional[fl
     n = done.value
     changed = [int(v) for v in trace[:n]]
     return FillReport(n, changed, int(frozen.value), bool(n and changed[-1] == 0))
+
+
+class AdvectReport(NamedTuple):
+    """What lsf_advect_field reports (include/lsf.h): steps run, the CFL number (dt * max(|u|+|v|+|w|+|speed|)) / dx of the inputs,
+    and the largest |new - old| over the interior cells of each step."""
+    steps: int
+    cfl: float
+    change: List[float]
+
+
+def advectField(phi, nx: int, ny: int, nz: int, dx: float, dt: float, steps: int, *, velocity=None, speed=None, scheme: str = "rk3",
+                arith: str = "strict") -> AdvectReport:
+    """Transport of the level set, phi_t + u.grad(phi) + F |grad(phi)| = 0, by `steps` explicit steps of size dt on the whole grid
+    (include/lsf.h: lsf_advect_field); `phi` is updated in place.
+
+    velocity: a 3-tuple (u, v, w) of fields with phi's layout and kind (numpy arrays on the host seam, CUDA tensors on the device
+    seam, which runs on the tensor's current stream); speed: one such field, the speed along the normal (> 0 grows the region
+    phi < 0).  At least one of the two; both are inputs, frozen for the call.  WENO5 one-sided derivatives (first order within
+    three cells of a wall), upwinding by the sign of each velocity component and Godunov's Hamiltonian for the speed;
+    scheme="rk3" (TVD Runge-Kutta of Shu and Osher) or "euler"; the extrapolation boundary condition after every stage.  The CFL
+    number is reported, not judged: keep it below 1.  Raises LsfNaNError when a step produced a NaN (phi holds that step; the
+    exception carries the AdvectReport as `.report`).
+    """
+    if scheme not in ("rk3", "euler"):
+        raise ValueError("scheme must be 'rk3' or 'euler'")
+    if arith not in ("strict", "fast"):
+        raise ValueError("arith must be 'strict' or 'fast'")
+    if velocity is None and speed is None:
+        raise ValueError("give velocity=(u, v, w), speed=F, or both")
+    if velocity is not None:
+        if not isinstance(velocity, (tuple, list)) or len(velocity) != 3 or any(c is None for c in velocity):
+            raise ValueError("velocity must be a 3-tuple (u, v, w) of fields")
+    dev = _is_torch(phi)
+    inputs = [(n, f) for n, f in zip("uvw", velocity or ())] + ([("speed", speed)] if speed is not None else [])
+    if any(_is_torch(f) != dev for _, f in inputs):
+        raise TypeError("phi, velocity and speed must all be numpy arrays or all be CUDA tensors")
+    cap = max(int(steps), 1)
+    trace = np.zeros(cap, dtype=np.float64)
+    done = ctypes.c_int(0)
+    cfl = ctypes.c_double(0.0)
+    if dev:
+        import torch
+
+        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
+        if any(f.device != phi.device for _, f in inputs):
+            raise ValueError("phi, velocity and speed must live on one device")
+    else:
+        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
+    p = ptr(phi, "phi")
+    q = {n: ptr(f, n) for n, f in inputs}
+    lib = _lib.load()
+    tail = (q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps),
+            {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}[scheme], mode_word("jacobi", arith), ctypes.byref(done),
+            ctypes.byref(cfl), trace.ctypes.data, cap)
+    if dev:
+        rc = lib.lsf_advect_field_device(p, *tail, _stream_and_device(phi))
+    else:
+        rc = lib.lsf_advect_field(p, *tail)
+    n = done.value
+    rep = AdvectReport(n, float(cfl.value), [float(x) for x in trace[:n]])
+    try:
+        _lib.check(rc)
+    except LsfNaNError as e:
+        e.report = rep  # the steps run, the NaN one included
+        raise
+    return rep
 
 
 def advectNodes(phi, phiSB, nx: int, ny: int, nz: int, dx: float, xLo, surfXX, iter: int = 1000) -> None:
