@@ -343,6 +343,81 @@ int lsf_advect_field_device(double *d_phi, const double *d_u, const double *d_v,
                             int nx, int ny, int nz, double dx, double dt, int steps, int scheme, int mode, int *steps_done,
                             double *cfl, double *change_trace, int trace_cap, void *stream);
 
+/* ---- iso-surface extraction: the zero (or iso) level of a field as an indexed triangle mesh (marching tetrahedra) ----------
+ * No reference counterpart.  What gives the moved geometry back after lsf_advect_field: the level set phi = iso as nodes
+ * surfX(nSurfNode,3) and triangles surfElem(nSurfElem,3), 1-based INTEGER*4, both Fortran-ordered -- the format lsf_phi0,
+ * lsf_mesh_distance, lsf_mesh_check and lsf_stl_get use -- made on the device with a numbering that is a function of the field alone.
+ * The field layout is that of every other entry point, the grid point (i,j,k) is xLo + (i,j,k)*dx as in lsf_mesh_distance, and the
+ * linear index of a point is p = i + (nx+1)*(j + (ny+1)*k).  info may be NULL.  Extract and keep, then copy out (as lsf_stl_read /
+ * lsf_stl_get): lsf_extract_surface returns the two counts, the caller allocates, lsf_extract_get fills.
+ *   field    f = phi - iso at every grid point.  A point is INSIDE when f < 0; anything else is outside: +0, -0 (phi == iso) and NaN
+ *            included -- the rule of lsf_distance_fill.
+ *   cells    every cell (i,j,k), 0 <= i < nx and likewise j, k, named by its lower corner c0 and ordered by c0's linear index, is cut
+ *            into the six Kuhn tetrahedra: tetrahedron 0..5 for the axis orders ABC = xyz, xzy, yxz, yzx, zxy, zyx has the vertices
+ *            v0 = c0, v1 = v0 + e_A, v2 = v1 + e_B, v3 = v2 + e_C.  All six share the body diagonal v0-v3; the cut of a cell face is
+ *            the same seen from both cells; there are no ambiguous cases and no case table.  PARITY: tetrahedra 0, 3, 4 (even
+ *            permutations of xyz) are positive, 1, 2, 5 negative.
+ *   edges    every tetrahedron edge runs from a grid point a to a + d, d in {0,1}^3 \ {0}, a the LOWER endpoint.  Edge TYPE
+ *            e = d_x + 2*d_y + 4*d_z - 1:  0 x, 1 y, 2 xy, 3 z, 4 xz, 5 yz (face diagonals), 6 xyz (body diagonal).  A wall point
+ *            owns only the types that stay inside the grid and no cell.
+ *   nodes    one per CROSSED edge (exactly one endpoint inside), numbered from 1 in ascending order of 7*p(a) + e.  With
+ *            fa = phi(a) - iso, fb = phi(a + d) - iso:   t = fa / (fa - fb)   (always from the lower endpoint, the IEEE division);
+ *            coordinate A of the node is xLo[A] + ((double)i_A + t) * dx where d_A = 1 and xLo[A] + (double)i_A * dx where d_A = 0,
+ *            evaluated as written, left to right, without contraction.
+ *   triangles  a tetrahedron with 1 or 3 vertices inside yields one triangle, with 2 inside two; "uv" is the node on the edge between
+ *            its vertices u and v, neg = the tetrahedron is negative:
+ *              one vertex m alone on its side, the others a < b < c:  (ma, mb, mc); the last two are swapped when
+ *                  neg xor (m odd) xor (3 inside);
+ *              inside p < q, outside r < s: the quad pr, ps, qs, qr is cut along pr-qs: (pr, ps, qs) then (pr, qs, qr); the last two
+ *                  of each are swapped when neg xor (p + q even).
+ *            Every normal (v1-v0) x (v2-v0) then points towards f >= 0 (outward): the mesh of a closed body has a positive signed
+ *            volume in lsf_mesh_check, and lsf_mesh_distance gives it the sign of phi.  Triangles are ordered by (cell, tetrahedron
+ *            0..5, triangle 0..1).
+ *   result   nodes, connectivity, counts and info are bit-identical from run to run, between the two seams and on any stream, and
+ *            equal the serial statement tests/extract_ref.py with ==.  By construction every mesh edge that does not lie in a wall
+ *            face of the grid is shared by exactly two triangles that traverse it in opposite directions; a level set that reaches
+ *            the grid's walls gives an OPEN mesh whose only one-triangle edges lie in wall faces.  Where phi == iso exactly on a grid
+ *            point (an outside point), the nodes of its crossed edges coincide there (t == 1, or t == 0 seen from it) and zero-area
+ *            triangles appear: the connectivity is still closed, nothing is welded, and lsf_mesh_check counts those triangles as
+ *            degenerate.
+ *   info     [0] nodes  [1] triangles  [2] cells crossed (neither all corners inside nor all outside)  [3] nodes with t == 1.
+ *            Written on LSF_OK only.
+ *   empty    no crossed edge: LSF_OK, both counts 0; lsf_extract_get is then LSF_OK, writes nothing and accepts NULL pointers.
+ *   keep     the result stays on the device, owned by the calling thread, until lsf_extract_get / lsf_extract_get_device copies it
+ *            out and releases it.  EVERY call of lsf_extract_surface[_device], a failing one included, first releases an un-fetched
+ *            result: a new extraction replaces it, a failed one keeps nothing.  A get without a result (a second get too) is
+ *            LSF_ERR_INVALID; so is a get with a NULL pointer, which releases nothing.  lsf_release_workspace drops the calling
+ *            thread's result.  The get runs on the device of the extraction (lsf_set_device).
+ *   errors   LSF_ERR_INVALID, all detected before anything is kept, with the count in lsf_last_error() where there is one: NULL phi,
+ *            xLo or count pointers; nx, ny or nz < 1, or more than 2^31 - 1 points; dx not finite or <= 0; iso not finite; crossed
+ *            edges with a non-finite phi - iso on an endpoint (their number, found by the counting pass; a non-finite value on no
+ *            crossed edge is accepted: NaN and +inf are outside, -inf inside); more than 2^31 - 1 nodes or triangles.  No device:
+ *            LSF_ERR_NO_DEVICE -- there is no CPU fallback.
+ *   seams    phi is an input only: lsf_extract_surface treats it under lsf_mirror exactly as lsf_narrowband treats its phi.
+ *            lsf_extract_surface_device returns after the stream is synchronised (the host reads the two totals);
+ *            lsf_extract_get_device copies on `stream` and returns after it is synchronised (the kept arrays are freed).
+ * Workspace beyond the caller's field: 10 bytes per grid point (crossed-edge mask and corner byte, node offset and triangle offset)
+ * + 24 bytes per 1024 points, and the kept mesh (24 bytes per node, 12 per triangle).  Work: one pass over the field that loads four
+ * values per point, three passes over the bytes (tile sums, ONE block scanning them 1024 at a time, offsets), one pass that writes
+ * the mesh; plain launches only, no block waits for another.  Out of scope: marching cubes, fp32, a band-restricted extraction,
+ * multi-GPU, welding of the coincident nodes at exact zeros.
+ * Not timed on hardware yet: no speed is claimed (the measurement is profiles/micro/extract_surface_time.py).
+ * lsf_stl_write is host code only and needs no device (like lsf_stl_read): binary STL, an 80-byte header (blank-padded text that
+ * does not begin with "solid"), the INTEGER*4 count, and per triangle the unit normal, the three vertices -- all REAL*4 -- and an
+ * INTEGER*2 zero.  The vertices are the coordinates rounded to REAL*4; the normal (v1-v0) x (v2-v0) / its length is computed in
+ * double from the ROUNDED vertices and is (0,0,0) for a zero-area triangle.  LSF_ERR_INVALID, all detected before the file is
+ * opened (an error leaves no file): a NULL pointer, nSurfElem < 1, nSurfNode < 1, an index outside 1..nSurfNode, a coordinate that
+ * is not finite as REAL*4; and a path that cannot be opened or written.  lsf_stl_read returns the float-rounded nodes in the order
+ * of their first use and merges nodes that round to the same REAL*4 triple. */
+#define LSF_SURF_INFO_LEN 4
+int lsf_extract_surface(const double *phi, int nx, int ny, int nz, double dx, const double xLo[3], double iso,
+                        int *nSurfNode, int *nSurfElem, int64_t info[LSF_SURF_INFO_LEN]);
+int lsf_extract_surface_device(const double *d_phi, int nx, int ny, int nz, double dx, const double xLo[3], double iso,
+                               int *nSurfNode, int *nSurfElem, int64_t info[LSF_SURF_INFO_LEN], void *stream);
+int lsf_extract_get(double *surfX, int32_t *surfElem);                          /* host arrays   */
+int lsf_extract_get_device(double *d_surfX, int32_t *d_surfElem, void *stream); /* device arrays */
+int lsf_stl_write(const char *path, const double *surfX, int nSurfNode, const int32_t *surfElem, int nSurfElem); /* host only */
+
 /* ---- post-smoothing gradients + surface-node advection (the step after the hot path) ----------
  * Replaces set3d.f90:470-501: firstDeriv order 8 (subs.f90:309-347, with its
  * quirks) on the cells of phiSB, then every surface node is moved by x += phiSurf * gradPhiSurf with

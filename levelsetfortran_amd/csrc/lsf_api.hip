@@ -27,6 +27,7 @@
 #include "lsf_mesh_distance.hpp"
 #include "lsf_distance_fill.hpp"
 #include "lsf_advect_field.hpp"
+#include "lsf_extract_surface.hpp"
 
 using namespace lsf;
 
@@ -183,7 +184,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -737,6 +738,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 
 #include "lsf_host_advect_field.hpp"
 
+#include "lsf_host_extract_surface.hpp"
+
 int box_ok(const lsf_box* b, const int lo[3], const int hi[3])
 {
     if (!b || !lo || !hi) return fail(LSF_ERR_INVALID, "NULL box/range");
@@ -1069,6 +1072,7 @@ int lsf_release_workspace(void)
     if (rc) return rc;
     Ctx& c = ctx();
     HIPCHK(hipDeviceSynchronize());
+    extract_drop(); // an un-fetched lsf_extract_surface result of this thread
     {   // lazy twins: the host copies they stand for are brought up to date before the device copies go
         struct { Twin* t; Slot s; } all[] = {{&c.twin_phi, S_HPHI}, {&c.twin_nb, S_HNB}, {&c.twin_sb, S_HSB}, {&c.twin_snap, S_SNAP}};
         for (auto& e : all) {
@@ -1453,6 +1457,35 @@ int lsf_advect_field(double* phi, const double* u, const double* v, const double
         twin_drop(c.twin_phi);
     return rc;
 }
+
+int lsf_extract_surface_device(const double* d_phi, int nx, int ny, int nz, double dx, const double xLo[3], double iso, int* nSurfNode,
+                               int* nSurfElem, int64_t info[LSF_SURF_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_extract_surface_device");
+    extract_drop(); // every call begins by releasing an un-fetched result
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = extract_args_ok(d_phi, nx, ny, nz, dx, xLo, iso, nSurfNode, nSurfElem))) return rc;
+    return extract_core(d_phi, nx, ny, nz, dx, xLo, iso, nSurfNode, nSurfElem, info, (hipStream_t)stream);
+}
+
+int lsf_extract_surface(const double* phi, int nx, int ny, int nz, double dx, const double xLo[3], double iso, int* nSurfNode, int* nSurfElem,
+                        int64_t info[LSF_SURF_INFO_LEN])
+{
+    Trace trace_("lsf_extract_surface");
+    extract_drop();
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = extract_args_ok(phi, nx, ny, nz, dx, xLo, iso, nSurfNode, nSurfElem))) return rc;
+    Ctx& c = ctx();
+    const size_t bytes = (size_t)(nx + 1) * (ny + 1) * (nz + 1) * sizeof(double);
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_narrowband
+    return extract_core((const double*)c.slot[S_HPHI].p, nx, ny, nz, dx, xLo, iso, nSurfNode, nSurfElem, info, nullptr);
+}
+
+int lsf_extract_get(double* surfX, int32_t* surfElem) { return extract_get(surfX, surfElem, false, nullptr); }
+
+int lsf_extract_get_device(double* d_surfX, int32_t* d_surfElem, void* stream) { return extract_get(d_surfX, d_surfElem, true, (hipStream_t)stream); }
 
 int lsf_advect_nodes_device(const double* d_phi, const int32_t* d_phiSB, int nx, int ny, int nz, double dx,
                             const double xLo[3], double* surfXX, int nSurfNode, int iters, void* stream)

@@ -1,5 +1,5 @@
 // lsf_host_stl.hpp -- lsf_stl_read / lsf_stl_get: the reference's binary STL ingest (subs.f90:17-121) with a hash instead of its quadratic
-// vertex search.  Host code only.  Included by lsf_api.hip inside extern "C".
+// vertex search; lsf_stl_write: the way out, the same records.  Host code only.  Included by lsf_api.hip inside extern "C".
 #pragma once
 
 // ---- binary STL with the reference's vertex merge (subs.f90:17-121) --------------------------------------------
@@ -99,5 +99,45 @@ int lsf_stl_get(double* surfX, int32_t* surfElem)
     for (size_t t = 0; t < nt; ++t)
         for (int p = 0; p < 3; ++p) surfElem[t + nt * p] = R.elem[t * 3 + p];
     R = StlResult{};
+    return LSF_OK;
+}
+
+// binary STL as lsf_stl_read takes it: 80 bytes of header, the count, per triangle the unit normal, three vertices (REAL*4) and an
+// INTEGER*2 zero.  Everything is checked before the file is opened: an error leaves no file behind.
+int lsf_stl_write(const char* path, const double* surfX, int nSurfNode, const int32_t* surfElem, int nSurfElem)
+{
+    Trace trace_("lsf_stl_write");
+    if (!path || !surfX || !surfElem) return fail(LSF_ERR_INVALID, "NULL pointer");
+    if (nSurfElem < 1 || nSurfNode < 1) return fail(LSF_ERR_INVALID, "lsf_stl_write: empty surface");
+    const size_t nn = (size_t)nSurfNode, nt = (size_t)nSurfElem;
+    for (size_t q = 0; q < 3 * nn; ++q)
+        if (!std::isfinite((float)surfX[q])) return fail(LSF_ERR_INVALID, "lsf_stl_write: a coordinate is not finite as REAL*4");
+    for (size_t q = 0; q < 3 * nt; ++q)
+        if (surfElem[q] < 1 || surfElem[q] > nSurfNode) return fail(LSF_ERR_INVALID, "surfElem index out of range");
+    std::vector<unsigned char> rec(84 + nt * 50, 0);
+    std::memset(rec.data(), ' ', 80);
+    static const char head[] = "levelsetfortran_amd lsf_stl_write";
+    std::memcpy(rec.data(), head, sizeof head - 1);
+    const int32_t count = nSurfElem;
+    std::memcpy(rec.data() + 80, &count, 4);
+    for (size_t t = 0; t < nt; ++t) {
+        float v[3][3];
+        for (int p = 0; p < 3; ++p)
+            for (int c = 0; c < 3; ++c) v[p][c] = (float)surfX[(size_t)(surfElem[t + nt * p] - 1) + nn * c];
+        // the normal in double from the rounded vertices; a zero-area triangle gets (0,0,0)
+        const double a[3] = {(double)v[1][0] - (double)v[0][0], (double)v[1][1] - (double)v[0][1], (double)v[1][2] - (double)v[0][2]};
+        const double b[3] = {(double)v[2][0] - (double)v[0][0], (double)v[2][1] - (double)v[0][1], (double)v[2][2] - (double)v[0][2]};
+        const double n[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+        const double len = std::sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+        float out[12];
+        for (int c = 0; c < 3; ++c) out[c] = len > 0.0 ? (float)(n[c] / len) : 0.0f;
+        std::memcpy(out + 3, v, sizeof v);
+        std::memcpy(rec.data() + 84 + t * 50, out, 48);
+    }
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(LSF_ERR_INVALID, std::string("cannot open ") + path + " for writing");
+    const size_t put = fwrite(rec.data(), 1, rec.size(), f);
+    const int closed = fclose(f);
+    if (put != rec.size() || closed != 0) return fail(LSF_ERR_INVALID, std::string("cannot write ") + path);
     return LSF_OK;
 }

@@ -21,6 +21,10 @@
 !                                                        |phi| >= band*dx by fast sweeping (include/lsf.h: lsf_distance_fill)
 !   advectField(phi,u,v,w,nx,ny,nz,dx,dt,steps)          no reference counterpart: transport of phi by the velocity field
 !                                                        (u,v,w), WENO5 / TVD-RK3 (include/lsf.h: lsf_advect_field)
+!   extractSurface(phi,nx,ny,nz,dx,xLo,iso,surfX,nSurfNode,surfElem,nSurfElem)
+!                                                        no reference counterpart: the level set phi = iso as a triangle mesh,
+!                                                        marching tetrahedra (include/lsf.h: lsf_extract_surface)
+!   stlWrite(surfX,nSurfNode,surfElem,filename,nSurfElem) no reference counterpart: binary STL of a mesh (lsf_stl_write)
 !   stlRead(surfX,nSurfNode,surfElem,filename,nSurfElem,surfElemTag,surfOrder,nBndComp,nBndElem,bndNormal)
 !                                                        replaces subs.f90:17-121 (same list)
 !
@@ -82,6 +86,7 @@ PUBLIC :: reinitBand
 PUBLIC :: meshDistance
 PUBLIC :: distanceFill
 PUBLIC :: advectField
+PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
 INTEGER(c_int), PARAMETER :: LSF_OK = 0, LSF_ERR_NAN = 1
@@ -256,6 +261,30 @@ INTERFACE
       REAL(c_double), VALUE :: dx
       INTEGER(c_int) :: rc
    END FUNCTION lsf_write_vti
+   ! int lsf_extract_surface(const double*,int,int,int,double,const double[3],double,int*,int*,int64_t[4])
+   FUNCTION lsf_extract_surface(phi,nx,ny,nz,dx,xLo,iso,nSurfNode,nSurfElem,info) BIND(C,NAME='lsf_extract_surface') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t
+      REAL(c_double), INTENT(IN) :: phi(*),xLo(3)
+      INTEGER(c_int), VALUE :: nx,ny,nz
+      REAL(c_double), VALUE :: dx,iso
+      INTEGER(c_int), INTENT(OUT) :: nSurfNode,nSurfElem
+      INTEGER(c_int64_t), INTENT(OUT) :: info(4)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_extract_surface
+   FUNCTION lsf_extract_get(surfX,surfElem) BIND(C,NAME='lsf_extract_get') RESULT(rc)
+      IMPORT :: c_int, c_double
+      REAL(c_double), INTENT(OUT) :: surfX(*)
+      INTEGER(c_int), INTENT(OUT) :: surfElem(*)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_extract_get
+   FUNCTION lsf_stl_write(path,surfX,nSurfNode,surfElem,nSurfElem) BIND(C,NAME='lsf_stl_write') RESULT(rc)
+      IMPORT :: c_int, c_double, c_char
+      CHARACTER(KIND=c_char), INTENT(IN) :: path(*)
+      REAL(c_double), INTENT(IN) :: surfX(*)
+      INTEGER(c_int), INTENT(IN) :: surfElem(*)
+      INTEGER(c_int), VALUE :: nSurfNode,nSurfElem
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_stl_write
    FUNCTION lsf_stl_read(path,nSurfElem,nSurfNode) BIND(C,NAME='lsf_stl_read') RESULT(rc)
       IMPORT :: c_int, c_char
       CHARACTER(KIND=c_char), INTENT(IN) :: path(*)
@@ -817,6 +846,59 @@ INTEGER(c_int) :: rc
 rc = lsf_mirror_sync(c_loc(a))
 IF (rc /= LSF_OK) CALL lsf_fail('lsf_mirror_sync',rc)
 END SUBROUTINE syncHostInt
+
+!*************************************************************************************!
+! The level set phi = iso as a triangle mesh (include/lsf.h: lsf_extract_surface; no
+! reference counterpart): marching tetrahedra on the six Kuhn tetrahedra of every cell,
+! made on the device.  surfX(nSurfNode,3) and surfElem(nSurfElem,3) are allocated here, as
+! stlRead allocates them, in the format meshDistance and phi0Init take; normals point
+! towards phi >= iso.  An empty level set gives nSurfNode = nSurfElem = 0 and arrays of
+! zero rows.  phi is read only.
+!*************************************************************************************!
+SUBROUTINE extractSurface(phi,nx,ny,nz,dx,xLo,iso,surfX,nSurfNode,surfElem,nSurfElem)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+REAL,INTENT(IN) :: dx,xLo(3),iso
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+REAL,ALLOCATABLE,DIMENSION(:,:),INTENT(OUT) :: surfX
+INTEGER*4,ALLOCATABLE,DIMENSION(:,:),INTENT(OUT) :: surfElem
+INTEGER*4,INTENT(OUT) :: nSurfNode,nSurfElem
+INTEGER(c_int64_t) :: info(4)
+INTEGER(c_int) :: rc
+
+CALL lsf_set_mirror()
+rc = lsf_extract_surface(phi,nx,ny,nz,dx,xLo,iso,nSurfNode,nSurfElem,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_extract_surface',rc)
+ALLOCATE(surfX(nSurfNode,3))
+ALLOCATE(surfElem(nSurfElem,3))
+rc = lsf_extract_get(surfX,surfElem)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_extract_get',rc)
+PRINT*, " Surface extraction: ",nSurfNode," nodes, ",nSurfElem," triangles, ",info(3)," cells crossed"
+PRINT*
+
+END SUBROUTINE extractSurface
+
+!*************************************************************************************!
+! Binary STL of a mesh (include/lsf.h: lsf_stl_write): what stlRead reads back.
+!*************************************************************************************!
+SUBROUTINE stlWrite(surfX,nSurfNode,surfElem,filename,nSurfElem)
+
+INTEGER*4,INTENT(IN) :: nSurfNode,nSurfElem
+REAL,INTENT(IN) :: surfX(nSurfNode,3)
+INTEGER*4,INTENT(IN) :: surfElem(nSurfElem,3)
+CHARACTER(LEN=*), INTENT(IN) :: filename
+INTEGER(c_int) :: rc
+CHARACTER(KIND=c_char) :: cname(LEN_TRIM(filename)+1)
+INTEGER :: i
+
+DO i = 1,LEN_TRIM(filename)
+   cname(i) = filename(i:i)
+END DO
+cname(LEN_TRIM(filename)+1) = c_null_char
+rc = lsf_stl_write(cname,surfX,nSurfNode,surfElem,nSurfElem)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_stl_write',rc)
+
+END SUBROUTINE stlWrite
 
 !*************************************************************************************!
 ! Read STL and Allocate  (same dummy arguments as subs.f90:17; host edit E11)

@@ -32,6 +32,7 @@ numerical code and no fallback.
 from __future__ import annotations
 
 import ctypes
+import os
 import sys
 from dataclasses import dataclass, field
 from typing import List, NamedTuple, Optional
@@ -41,7 +42,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "advectField", "AdvectReport", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "advectField", "AdvectReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -469,6 +470,70 @@ def advectField(phi, nx: int, ny: int, nz: int, dx: float, dt: float, steps: int
         e.report = rep  # the steps run, the NaN one included
         raise
     return rep
+
+
+class SurfaceInfo(NamedTuple):
+    """The counts of lsf_extract_surface (include/lsf.h: info[0..3])."""
+    nodes: int
+    triangles: int
+    cells_crossed: int
+    nodes_on_grid_points: int
+
+
+def extractSurface(phi, nx: int, ny: int, nz: int, dx: float, xLo, *, iso: float = 0.0):
+    """The level set phi = iso as an indexed triangle mesh (include/lsf.h: lsf_extract_surface): marching tetrahedra on the six Kuhn
+    tetrahedra of every cell, one node per crossed edge, made on the device.  Returns (surfX, surfElem, SurfaceInfo).
+
+    phi is an input (numpy F-ordered or torch CUDA, see module docstring); the grid point is xLo + i*dx as for meshDistance.
+    surfX is (nSurfNode, 3) float64 and surfElem (nSurfElem, 3) int32, 1-based, both Fortran-ordered -- what meshCheck, meshDistance,
+    phi0Init and stlWrite take.  Numpy in gives numpy out; a CUDA tensor in gives CUDA tensors out through the device seam, on the
+    tensor's current stream.  Triangle normals point towards phi >= iso; the numbering is a function of the field alone.  A level set
+    that reaches the walls of the grid gives an open mesh; an empty one gives arrays with 0 rows.
+    """
+    lo = np.ascontiguousarray(xLo, dtype=np.float64)
+    if lo.shape != (3,):
+        raise ValueError("xLo must hold 3 values")
+    dx, iso = float(dx), float(iso)
+    if not (np.isfinite(dx) and dx > 0.0):
+        raise ValueError("dx must be finite and > 0")
+    if not np.isfinite(iso):
+        raise ValueError("iso must be finite")
+    if min(int(nx), int(ny), int(nz)) < 1:
+        raise ValueError("nx, ny, nz must be >= 1")
+    dev = _is_torch(phi)
+    nn, nt = ctypes.c_int(0), ctypes.c_int(0)
+    info = np.zeros(_lib.LSF_SURF_INFO_LEN, dtype=np.int64)
+    if dev:
+        import torch
+
+        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        lib = _lib.load()
+        st = _stream_and_device(phi)
+        _lib.check(lib.lsf_extract_surface_device(p, nx, ny, nz, dx, lo.ctypes.data, iso, ctypes.byref(nn), ctypes.byref(nt), info.ctypes.data, st))
+        # (n,3) in Fortran order: the transpose of a contiguous (3,n)
+        sX = torch.empty((3, nn.value), dtype=torch.float64, device=phi.device)
+        sE = torch.empty((3, nt.value), dtype=torch.int32, device=phi.device)
+        _lib.check(lib.lsf_extract_get_device(sX.data_ptr() if nn.value else None, sE.data_ptr() if nt.value else None, st))
+        sX, sE = sX.t(), sE.t()
+    else:
+        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
+        lib = _lib.load()
+        _lib.check(lib.lsf_extract_surface(p, nx, ny, nz, dx, lo.ctypes.data, iso, ctypes.byref(nn), ctypes.byref(nt), info.ctypes.data))
+        sX = np.zeros((nn.value, 3), dtype=np.float64, order="F")
+        sE = np.zeros((nt.value, 3), dtype=np.int32, order="F")
+        _lib.check(lib.lsf_extract_get(sX.ctypes.data if nn.value else None, sE.ctypes.data if nt.value else None))
+    return sX, sE, SurfaceInfo(*(int(v) for v in info))
+
+
+def stlWrite(path, surfX, surfElem) -> None:
+    """Binary STL from nodes + 1-based connectivity (include/lsf.h: lsf_stl_write): vertices rounded to float32, unit normals
+    computed from the rounded vertices.  Host code only: no device is needed.  CUDA tensors are copied to the host first."""
+    if _is_torch(surfX):
+        surfX = surfX.cpu().numpy()
+    if _is_torch(surfElem):
+        surfElem = surfElem.cpu().numpy()
+    sX, sE = _surface(surfX, surfElem)
+    _lib.check(_lib.load().lsf_stl_write(os.fsencode(path), sX.ctypes.data, sX.shape[0], sE.ctypes.data, sE.shape[0]))
 
 
 def advectNodes(phi, phiSB, nx: int, ny: int, nz: int, dx: float, xLo, surfXX, iter: int = 1000) -> None:
