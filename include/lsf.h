@@ -423,7 +423,19 @@ int lsf_stl_write(const char *path, const double *surfX, int nSurfNode, const in
  * quirks) on the cells of phiSB, then every surface node is moved by x += phiSurf * gradPhiSurf with
  * setPhiSurf's trilinear interpolation (subs.f90:1056-1170) until phiSurf <= 1e-13 or `iters` (host: 1000)
  * passes.  surfXX is the host's REAL surfXX(nSurfNode,3) (Fortran-ordered HOST array), in = the nodes,
- * out = the advected nodes.  Bit-identical to the reference. */
+ * out = the advected nodes.  Bit-identical to the reference.
+ *   phiSB    a cell is band where phiSB == 1 exactly; any other value (0, 7, -1) is not.  The gradient is 0 outside the band.
+ *            firstDeriv's neighbours are addressed linearly, so a band cell fewer than 4 points from a wall reads the neighbouring
+ *            row / plane; a read before the first or after the last element of phi yields 0.
+ *   nodes    accepted where, on every axis, xLo <= x < xLo + dx*(n-1) with n = nx, ny, nz: the cells 0 .. n-2, whose eight corners
+ *            exist and stay in the field when the quotient (x-xLo)/dx rounds up by one cell.  The upper bound itself, anything
+ *            below xLo, NaN and +-inf are refused.  Only the positions on entry are checked: a node that phi carries out of that
+ *            range is not reported, and its reads are clamped into the field.
+ *   iters    >= 0; 0 returns the nodes as they came.  One call with iters = k equals k calls with iters = 1 whose nodes are in the
+ *            accepted range on every entry.
+ *   phiSurf  a node moves while phiSurf > 1e-13: a NaN phiSurf (a NaN corner) or a negative one leaves the node bit for bit as it is.
+ * phi and phiSB are inputs only.  LSF_ERR_INVALID with a message, surfXX untouched: a NULL pointer, nSurfNode < 1, iters < 0, a node
+ * outside the accepted range. */
 int lsf_advect_nodes(const double *phi, const int32_t *phiSB, int nx, int ny, int nz, double dx,
                      const double xLo[3], double *surfXX, int nSurfNode, int iters);
 int lsf_advect_nodes_device(const double *d_phi, const int32_t *d_phiSB, int nx, int ny, int nz, double dx,

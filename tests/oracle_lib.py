@@ -109,18 +109,28 @@ def phi0(nx, ny, nz, dx, xLo, minX, maxX, surfX, surfElem):
     return phi
 
 
-def advect(phi, phiSB, nx, ny, nz, dx, xLo, surfX, iters=1000):
-    """set3d.f90:464-501: order-8 gradients on the stencil band, then the node advection.  Returns surfXX."""
+def firstderiv8(phi, phiSB, nx, ny, nz, dx):
+    """set3d.f90:470-479: firstDeriv order 8 on the cells with phiSB == 1.  Returns gradPhi (0:nx,0:ny,0:nz,3), zero elsewhere."""
     L = lib()
     vp = ctypes.c_void_p
     L.lsf_oracle_firstderiv8.restype = None
     L.lsf_oracle_firstderiv8.argtypes = [vp, vp, c_int, c_int, c_int, c_double, vp]
-    L.lsf_oracle_advect.restype = None
-    L.lsf_oracle_advect.argtypes = [vp, vp, c_int, c_int, c_int, c_double, vp, vp, c_int, c_int]
+    assert phi.shape == (nx + 1, ny + 1, nz + 1)
     grad = np.zeros(phi.shape + (3,), order="F")
     sb = np.asfortranarray(phiSB, dtype=np.int32)
+    assert sb.shape == phi.shape
+    L.lsf_oracle_firstderiv8(_d(phi), sb.ctypes.data, nx, ny, nz, dx, grad.ctypes.data)
+    return grad
+
+
+def advect(phi, phiSB, nx, ny, nz, dx, xLo, surfX, iters=1000):
+    """set3d.f90:464-501: order-8 gradients on the stencil band, then the node advection.  Returns surfXX."""
+    L = lib()
+    vp = ctypes.c_void_p
+    L.lsf_oracle_advect.restype = None
+    L.lsf_oracle_advect.argtypes = [vp, vp, c_int, c_int, c_int, c_double, vp, vp, c_int, c_int]
+    grad = firstderiv8(phi, phiSB, nx, ny, nz, dx)
     lo = np.ascontiguousarray(xLo, dtype=np.float64)
     XX = np.array(surfX, dtype=np.float64, order="F", copy=True)
-    L.lsf_oracle_firstderiv8(phi.ctypes.data, sb.ctypes.data, nx, ny, nz, dx, grad.ctypes.data)
     L.lsf_oracle_advect(phi.ctypes.data, grad.ctypes.data, nx, ny, nz, dx, lo.ctypes.data, XX.ctypes.data, XX.shape[0], iters)
     return XX
