@@ -437,6 +437,16 @@ dim3 bc_grid(const Box& bx, const int lo[3], const int hi[3], unsigned* faces)
     *faces = list;
     return dim3(cdiv(m, 64), m, cnt);
 }
+// ... of a single-domain call: the whole grid as one box, all six faces
+struct BcWhole { Box bx; dim3 grid; unsigned faces; long nparts; }; // (nparts: partial sums the launch writes)
+BcWhole bc_whole(int nx, int ny, int nz)
+{
+    BcWhole w{Box{nx + 1, ny + 1, nz + 1, 0, 0, 0, nx, ny, nz}, dim3(), 0, 0};
+    const int lo[3] = {0, 0, 0}, hi[3] = {nx + 1, ny + 1, nz + 1};
+    w.grid = bc_grid(w.bx, lo, hi, &w.faces);
+    w.nparts = (long)w.grid.x * w.grid.y * w.grid.z;
+    return w;
+}
 
 int check_dims(int nx, int ny, int nz)
 {
@@ -470,6 +480,17 @@ static int jacobi_kc(long columns, int cz)
     while (kc > 4 && columns * cdiv(cz, kc) < 2048) kc >>= 1;
     return kc;
 }
+// wavefronts a block of the shared-interface kernels (fp64 FAST, fp32) spans along x: the 64 wx - 1 cells of a block tile a row of cx
+// cells with the fewest wavefronts
+static int jacobi_wx(int cx)
+{
+    int best = 1 << 30, best_wx = 1;
+    for (int wx : {4, 2, 1, 8}) { // on a tie the first wins: four wavefronts across measured 5-7 % faster than 2 x 2 or eight (256^3, the 506-cell cores of a decomposed 512^3 block)
+        const int waves = wx * cdiv(cx, 64 * wx - 1);
+        if (waves < best) best = waves, best_wx = wx;
+    }
+    return best_wx;
+}
 JacPlan jacobi_plan(const int lo[3], const int hi[3], bool strict, const int ext[3])
 {
     JacPlan p;
@@ -502,11 +523,7 @@ JacPlan jacobi_plan(const int lo[3], const int hi[3], bool strict, const int ext
         return p;
     }
     p.kind = 2;
-    int best = 1 << 30;
-    for (int wx : {4, 2, 1, 8}) { // on a tie the first wins: four wavefronts across measured 5-7 % faster than 2 x 2 or eight (256^3, the 506-cell cores of a decomposed 512^3 block)
-        const int waves = wx * cdiv(cx, 64 * wx - 1);
-        if (waves < best) best = waves, p.wx = wx;
-    }
+    p.wx = jacobi_wx(cx);
     p.by = p.wx == 1 ? 4 : (p.wx == 2 ? 2 : 1);
     static const int shapes[][2] = {{1, 4}, {2, 2}, {4, 1}, {4, 2}, {8, 1}};
     for (auto& sh : shapes)
@@ -565,11 +582,7 @@ JacPlan jacobi_plan_f32(const int lo[3], const int hi[3])
         return p;
     }
     p.kind = 2;
-    int best = 1 << 30;
-    for (int wx : {4, 2, 1, 8}) { // on a tie the first wins: four wavefronts across measured 5-7 % faster than 2 x 2 or eight (256^3, the 506-cell cores of a decomposed 512^3 block)
-        const int waves = wx * cdiv(cx, 64 * wx - 1);
-        if (waves < best) best = waves, p.wx = wx;
-    }
+    p.wx = jacobi_wx(cx);
     int fwx = 0, fby = 0;
     if (env && sscanf(env, "%dx%d", &fwx, &fby) >= 1 && (fwx == 1 || fwx == 2 || fwx == 4 || fwx == 8)) p.wx = fwx;
     p.by = 1;
@@ -599,6 +612,8 @@ void jacobi_launch_f32(const JacPlan& p, const float* A, float* B, const float* 
 #undef LSF_F32_SH
 }
 
+#include "lsf_host_stop.hpp"
+
 int gs_schedule();
 int reinit_slot_core(double* d_phi, const double* d_phiS_in, int nx, int ny, int nz, int iter, double dx, double h,
                      double tol, int mode, int first_raster, int* sweeps_done, double* rms_trace, int trace_cap,
@@ -624,27 +639,15 @@ int jacobi_loop(T* d_phi, const T* d_phiS_in, int nx, int ny, int nz, int iter, 
         HIPCHK(hipMemcpyAsync(c.slot[S_PHIS].p, d_phi, n * sizeof(T), hipMemcpyDeviceToDevice, st)); // subs.f90:731
         d_phiS = (const T*)c.slot[S_PHIS].p;
     }
-    if ((rc = ws(c.slot[S_CTL], 64))) return rc;
-    if ((rc = ws(c.slot[S_TRACE], (size_t)max_sweeps * sizeof(double)))) return rc;
-    int* ctl = (int*)c.slot[S_CTL].p;
-    double* d_trace = (double*)c.slot[S_TRACE].p;
-    HIPCHK(hipMemsetAsync(ctl, 0, 64, st));
+    StopLoop stop;
+    if ((rc = stop.begin(c, max_sweeps, st))) return rc;
+    int* ctl = stop.ctl;
 
-    const int jlo[3] = {1, 1, 1}, jhi[3] = {nx, ny, nz};
-    JacPlan jp;
-    long n_sweep_part;
-    if constexpr (F32) jp = jacobi_plan_f32(jlo, jhi);
-    else {
-        const int jext[3] = {nx + 1, ny + 1, nz + 1};
-        jp = jacobi_plan(jlo, jhi, strict, jext);
-    }
-    n_sweep_part = jp.nparts;
-    const Box bx{nx + 1, ny + 1, nz + 1, 0, 0, 0, nx, ny, nz};
-    const int blo[3] = {0, 0, 0}, bhi[3] = {nx + 1, ny + 1, nz + 1};
-    unsigned bfaces = 0;
-    const dim3 bgrid = bc_grid(bx, blo, bhi, &bfaces); // the whole grid: all six faces
-    const long n_bc_part = (long)bgrid.x * bgrid.y * bgrid.z;
-    const long n_part = n_sweep_part + n_bc_part;
+    const int jlo[3] = {1, 1, 1}, jhi[3] = {nx, ny, nz}, jext[3] = {nx + 1, ny + 1, nz + 1};
+    const JacPlan jp = F32 ? jacobi_plan_f32(jlo, jhi) : jacobi_plan(jlo, jhi, strict, jext);
+    const BcWhole bc = bc_whole(nx, ny, nz);
+    const Box& bx = bc.bx;
+    const long n_part = jp.nparts + bc.nparts;
     if ((rc = ws(c.slot[S_PART], (size_t)n_part * sizeof(double)))) return rc;
     double* part = (double*)c.slot[S_PART].p;
     // fp64: the reference's INTEGER*4 product nx*ny*nz (subs.f90:914), wrapping like the reference; it is negative for the
@@ -654,7 +657,6 @@ int jacobi_loop(T* d_phi, const T* d_phiS_in, int nx, int ny, int nz, int iter, 
     const int xwall = F32 ? F32_XWALL : 0;
 
     T* bufs[2] = {d_phi, (T*)c.slot[S_PONG].p};
-    int host_ctl[3] = {0, 0, 0};
     prof_begin();
     for (int s = 0; s < max_sweeps; ++s) {
         const T* A = bufs[s & 1];
@@ -663,21 +665,15 @@ int jacobi_loop(T* d_phi, const T* d_phiS_in, int nx, int ny, int nz, int iter, 
         if constexpr (F32) jacobi_launch_f32(jp, A, B, d_phiS, bx, jlo, jhi, dx, h, part, ctl, xwall, st);
         else jacobi_launch(jp, strict, A, B, d_phiS, bx, jlo, jhi, dx, h, part, ctl, st);
         prof_mark(st);
-        hipLaunchKernelGGL(k_bc<T>, bgrid, dim3(64), 0, st, A, B, bx, 0, 0, 0, nx + 1, ny + 1, nz + 1, (T)dx, part + n_sweep_part, ctl,
-                           xwall, bfaces);
+        hipLaunchKernelGGL(k_bc<T>, bc.grid, dim3(64), 0, st, A, B, bx, 0, 0, 0, nx + 1, ny + 1, nz + 1, (T)dx, part + jp.nparts, ctl,
+                           xwall, bc.faces);
         prof_mark(st);
-        hipLaunchKernelGGL(k_finish, dim3(1), dim3(RED_T), 0, st, part, n_part, den, tol, d_trace, max_sweeps, ctl);
+        hipLaunchKernelGGL(k_finish, dim3(1), dim3(RED_T), 0, st, part, n_part, den, tol, stop.d_trace, max_sweeps, ctl);
         prof_mark(st);
-        if ((s + 1) % CHECK_EVERY == 0 && s + 1 < max_sweeps) {
-            HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (host_ctl[0]) break;
-        }
+        if (stop.poll(s, max_sweeps)) break;
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int nsw = host_ctl[1];
+    if ((rc = stop.finish())) return rc;
+    const int nsw = stop.count();
     prof_end(nsw);
     g_prof.sweep_launches = g_prof.sweeps;
     if (jp.kind == 2 && F32) snprintf(g_prof.kernel_buf, sizeof g_prof.kernel_buf, "k_reinit_jacobi_f32_sh<%d>", jp.wx);
@@ -687,12 +683,7 @@ int jacobi_loop(T* d_phi, const T* d_phiS_in, int nx, int ny, int nz, int iter, 
     g_prof.kernel = g_prof.kernel_buf;
     if (bufs[nsw & 1] != d_phi)
         HIPCHK(hipMemcpyAsync(d_phi, bufs[nsw & 1], n * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if (rms_trace && trace_cap > 0 && nsw > 0)
-        HIPCHK(hipMemcpyAsync(rms_trace, d_trace, sizeof(double) * (size_t)std::min(nsw, trace_cap), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (sweeps_done) *sweeps_done = nsw;
-    if (host_ctl[2]) return fail(LSF_ERR_NAN, "RMS became NaN (the reference STOPs here, subs.f90:926)");
-    return LSF_OK;
+    return stop.verdict(rms_trace, trace_cap, sweeps_done, "RMS became NaN (the reference STOPs here, subs.f90:926)");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -87,32 +87,25 @@ int advect_field_steps(double* d_phi, const double* d_u, const double* d_v, cons
     const int nbx = cdiv(nx - 1, ADV_BX), nby = cdiv(ny - 1, ADV_BY), nbz = cdiv(nz - 1, ADV_KC);
     const long nblk = (long)nbx * nby * nbz;
     if (nblk > 0x7ffffff0L) return fail(LSF_ERR_INVALID, "lsf_advect_field: too many blocks for one launch");
-    const Box bx{nx + 1, ny + 1, nz + 1, 0, 0, 0, nx, ny, nz};
-    const int blo[3] = {0, 0, 0}, bhi[3] = {nx + 1, ny + 1, nz + 1};
-    unsigned bfaces = 0;
-    const dim3 bgrid = bc_grid(bx, blo, bhi, &bfaces); // the whole grid: all six faces
-    const long n_bc_part = (long)bgrid.x * bgrid.y * bgrid.z;
+    const BcWhole bc = bc_whole(nx, ny, nz);
     const int tcap = change_trace ? std::max(0, std::min(steps, trace_cap)) : 0;
     if ((rc = ws(c.slot[S_PONG], n * sizeof(double)))) return rc;
     if (rk3 && (rc = ws(c.slot[S_PONG2], n * sizeof(double)))) return rc;
-    if ((rc = ws(c.slot[S_PART], (size_t)(nblk + n_bc_part) * sizeof(double)))) return rc;
-    if ((rc = ws(c.slot[S_CTL], 64))) return rc;
-    if ((rc = ws(c.slot[S_TRACE], (size_t)std::max(tcap, 1) * sizeof(double)))) return rc;
+    if ((rc = ws(c.slot[S_PART], (size_t)(nblk + bc.nparts) * sizeof(double)))) return rc;
+    StopLoop stop;
+    if ((rc = stop.begin(c, tcap, st))) return rc;
     double* w1 = (double*)c.slot[S_PONG].p;
     double* w2 = rk3 ? (double*)c.slot[S_PONG2].p : nullptr;
     unsigned long long* part = (unsigned long long*)c.slot[S_PART].p;
     double* part_bc = (double*)(part + nblk); // k_bc's sums of squares: written, never read
-    int* ctl = (int*)c.slot[S_CTL].p;
-    double* d_trace = (double*)c.slot[S_TRACE].p;
-    HIPCHK(hipMemsetAsync(ctl, 0, 64, st));
+    int* ctl = stop.ctl;
 
     auto stage = [&](const double* A, double* B, const double* P0, double c_old, double c_new, bool last) {
         advect_stage_launch(strict, A, B, P0, d_u, d_v, d_w, d_f, nx, ny, nz, dx, dt, c_old, c_new, last ? part : nullptr, ctl, nbx, nby, nbz, st);
         // the extrapolation boundary condition on the stage's output (subs.f90:859-897)
-        hipLaunchKernelGGL(k_bc<double>, bgrid, dim3(64), 0, st, A, B, bx, 0, 0, 0, nx + 1, ny + 1, nz + 1, dx, part_bc, (const int*)ctl, 0, bfaces);
+        hipLaunchKernelGGL(k_bc<double>, bc.grid, dim3(64), 0, st, A, B, bc.bx, 0, 0, 0, nx + 1, ny + 1, nz + 1, dx, part_bc, (const int*)ctl, 0, bc.faces);
     };
     double* bufs[2] = {d_phi, w1};
-    int host_ctl[3] = {0, 0, 0};
     for (int s = 0; s < steps; ++s) {
         if (rk3) {
             stage(d_phi, w1, nullptr, 0.0, 1.0, false);
@@ -121,21 +114,11 @@ int advect_field_steps(double* d_phi, const double* d_u, const double* d_v, cons
         } else {
             stage(bufs[s & 1], bufs[(s + 1) & 1], nullptr, 0.0, 1.0, true);
         }
-        hipLaunchKernelGGL(k_advect_finish, dim3(1), dim3(RED_T), 0, st, (const unsigned long long*)part, nblk, d_trace, tcap, ctl);
-        if ((s + 1) % CHECK_EVERY == 0 && s + 1 < steps) {
-            HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (host_ctl[0]) break;
-        }
+        hipLaunchKernelGGL(k_advect_finish, dim3(1), dim3(RED_T), 0, st, (const unsigned long long*)part, nblk, stop.d_trace, tcap, ctl);
+        if (stop.poll(s, steps)) break;
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int nst = host_ctl[1];
+    if ((rc = stop.finish())) return rc;
+    const int nst = stop.count();
     if (!rk3 && (nst & 1)) HIPCHK(hipMemcpyAsync(d_phi, w1, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (tcap > 0 && nst > 0) HIPCHK(hipMemcpyAsync(change_trace, d_trace, sizeof(double) * (size_t)std::min(nst, tcap), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (steps_done) *steps_done = nst;
-    if (host_ctl[2]) return fail(LSF_ERR_NAN, "lsf_advect_field: the field became NaN in step " + std::to_string(nst - 1) + " (0-based)");
-    return LSF_OK;
+    return stop.verdict(change_trace, tcap, steps_done, "lsf_advect_field: the field became NaN in step " + std::to_string(nst - 1) + " (0-based)");
 }

@@ -28,11 +28,9 @@ int minmax_core_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
     if ((rc = ws(c.slot[S_PONG], n * sizeof(double)))) return rc;
-    if ((rc = ws(c.slot[S_CTL], 64))) return rc;
-    if ((rc = ws(c.slot[S_TRACE], (size_t)std::max(iter, 1) * sizeof(double)))) return rc;
-    int* ctl = (int*)c.slot[S_CTL].p;
-    double* d_trace = (double*)c.slot[S_TRACE].p;
-    HIPCHK(hipMemsetAsync(ctl, 0, 64, st));
+    StopLoop stop;
+    if ((rc = stop.begin(c, std::max(iter, 1), st))) return rc;
+    int* ctl = stop.ctl;
 
     TileList* tl = nullptr;
     int nTi = 0, nTj = 0, nTk = 0, jblocks = 0;
@@ -67,12 +65,11 @@ int minmax_core_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
     const double den = rms_denominator(nx, ny, nz);
 
     double* bufs[2] = {d_phi, (double*)c.slot[S_PONG].p};
-    int host_ctl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const char* tfp = getenv("LSF_TRACE_MINMAX");
     const bool trace_fp = tfp && atoi(tfp) != 0;
     // Fix passes enqueued per iteration.  A pass that finds the fixed point certified returns at once, but an empty
-    // launch still costs ~6 us, so the count follows what the field needs (ctl[4] = most passes that changed cells,
-    // read with the stop flag every CHECK_EVERY iterations): three times that plus four.  Too few -> ctl[3], the
+    // launch still costs ~6 us, so the count follows what the field needs (CTL_FIXMAX = most passes that changed cells,
+    // read with the stop flag every CHECK_EVERY iterations): three times that plus four.  Too few -> CTL_UNCERT, the
     // caller repeats the call with MM_MAX_FIX passes.  Large grids skip the adaptation (minmax_core): their chains of
     // sign flips grow fast (1024^3 two spheres: 4, 7, 9, 16 passes in iterations 4..8 of a call) and 32 launches are
     // 4 % of an iteration there.
@@ -97,9 +94,6 @@ int minmax_core_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
             // pass 2 also records how many fix passes changed cells (first = cap) and flags an uncertified iteration
             hipLaunchKernelGGL((k_minmax_fp<2>), gwide, b, 0, st, A, B, mask, nx, ny, nz, dx, h1, bflag, stamp, fp_chunks, 0,
                                cap, (const int*)(chg + cap - 1), (int*)nullptr, part, ctl);
-            hipLaunchKernelGGL(k_reduce_slices, dim3(256), dim3(256), 0, st, (const double*)part, fp_chunks, part2);
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(RED_T), 0, st, (const double*)part2, 256L, den, tol, d_trace,
-                               std::max(iter, 1), ctl);
         } else if (order == LSF_ORDER_GS) {
             const int nplanes = (int)tl->off.size() - 1;
             for (int P = 0; P < nplanes; ++P) {
@@ -112,9 +106,7 @@ int minmax_core_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
             hipLaunchKernelGGL(k_minmax_jacobi, dim3(jblocks), dim3(256), 0, st, A, B, mask, nx, ny, nz, dx, h1, part,
                                ctl);
         }
-        if (!fixed_point)
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(RED_T), 0, st, part, n_part, den, tol, d_trace, std::max(iter, 1),
-                               ctl);
+        reduce_finish(k_finish, part, n_part, part2, den, tol, stop, 0); // (the fixed point alone has part2: always through the slices)
         if (fixed_point && trace_fp) {
             int hc[MM_MAX_FIX + 1] = {0};
             HIPCHK(hipMemcpyAsync(hc, chg, sizeof hc, hipMemcpyDeviceToHost, st));
@@ -125,28 +117,25 @@ int minmax_core_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
         }
         // the adaptive pass count looks at the device early (after iterations 1, 2 and 4), then with the stop flag
         const bool early = fixed_point && exact_mode == MM_FP_ADAPTIVE && (it == 0 || it == 1 || it == 3);
-        if (((it + 1) % CHECK_EVERY == 0 || early) && it + 1 < iter) {
-            HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (host_ctl[0] || host_ctl[3]) break;
-            if (exact_mode == MM_FP_ADAPTIVE) cap = std::min(MM_MAX_FIX, std::max(8, 3 * host_ctl[4] + 4));
+        if (stop.due(it, iter, early)) {
+            if (stop.look()) break;
+            if (exact_mode == MM_FP_ADAPTIVE) cap = std::min(MM_MAX_FIX, std::max(8, 3 * stop.host[CTL_FIXMAX] + 4));
         }
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = stop.finish())) return rc;
+    const bool uncertified = stop.host[CTL_UNCERT] != 0;
     if (fixed_point && getenv("LSF_TRACE")) {
         int hc[MM_MAX_FIX + 1] = {0};
         HIPCHK(hipMemcpy(hc, chg, sizeof hc, hipMemcpyDeviceToHost));
         int used = 0;
         for (int f = 0; f < MM_MAX_FIX; ++f) used += hc[f] != 0;
         fprintf(stderr, "[lsf] min/max fixed point: last iteration needed %d fix passes that changed cells (%d enqueued)%s\n",
-                used, cap, host_ctl[3] ? "; NOT certified -> rerun" : "");
+                used, cap, uncertified ? "; NOT certified -> rerun" : "");
     }
-    if (inexact) *inexact = host_ctl[3] != 0;
-    if (host_ctl[3]) return LSF_OK; // caller restores the input and reruns with the tile wavefront
-    const int nit = host_ctl[1];
-    const bool stopped_early = host_ctl[0] != 0; // converged or NaN: EXIT/STOP before narrowBand
+    if (inexact) *inexact = uncertified;
+    if (uncertified) return LSF_OK; // caller restores the input and reruns with the tile wavefront
+    const int nit = stop.count();
+    const bool stopped_early = stop.stopped(); // converged or NaN: EXIT/STOP before narrowBand
     // masks the host would hold now (set3d.f90:448-460)
     if (nit >= 1) {
         const double* src = nullptr;
@@ -156,12 +145,71 @@ int minmax_core_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
     }
     if (bufs[nit & 1] != d_phi)
         HIPCHK(hipMemcpyAsync(d_phi, bufs[nit & 1], n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (rms_trace && trace_cap > 0 && nit > 0)
-        HIPCHK(hipMemcpyAsync(rms_trace, d_trace, sizeof(double) * (size_t)std::min(nit, trace_cap),
-                              hipMemcpyDeviceToHost, st));
+    return stop.verdict(rms_trace, trace_cap, iters_done, "RMS became NaN (the reference STOPs here, set3d.f90:458)");
+}
+
+// The list of cells a band executor works on (the min/max flow below, lsf_host_reinit_band.hpp), built once per call in two phases with
+// the caller's decision between them.  Staging: the first n ints of S_PONG -- asked for at n doubles, the size at which the dense min/max
+// executors and the reinit on the band want their second field, so that no call frees and allocates the buffer a second time.
+struct BandList {
+    int nL = 0, nchunks = 0;       // cells (after band_list_count), chunks of MB_CH cells
+    int* L = nullptr;              // S_MB_L: point indices, sorted by brick key or in memory order (after band_list_sort)
+    const unsigned* key = nullptr; // S_MB_KEY: the sorted brick keys; NULL for a list in memory order
+    size_t n = 0;                  // points of the grid
+    long nblk = 0;                 // blocks of the scan
+    int nx = 0, ny = 0, nz = 0, nbx = 0, nby = 0; // ... bricks along x, y
+    int *staging = nullptr, *counts = nullptr, *offsets = nullptr;
+    // brick keys are 32-bit: beyond that a list can only stay in memory order
+    bool keys_fit() const { return (double)nbx * nby * cdiv(nz + 1, 4) * 256.0 <= 4.0e9; }
+};
+// phase 1: the cells per scan block and their number.  MASK_ONLY: the cells of the caller's mask; otherwise the cells that can ever be
+// in the band of phi (k_mb_collect).  Waits for the device.
+template <bool MASK_ONLY>
+int band_list_count(BandList& bl, const double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, hipStream_t st)
+{
+    int rc;
+    Ctx& c = ctx();
+    bl.n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    bl.nx = nx, bl.ny = ny, bl.nz = nz, bl.nbx = cdiv(nx + 1, 8), bl.nby = cdiv(ny + 1, 8);
+    bl.nblk = (long)((bl.n + MB_SCAN - 1) / MB_SCAN);
+    if ((rc = ws(c.slot[S_PONG], bl.n * sizeof(double)))) return rc;
+    if ((rc = ws(c.slot[S_MB_CNT], (size_t)(2 * bl.nblk + 8) * sizeof(int)))) return rc;
+    bl.staging = (int*)c.slot[S_PONG].p, bl.counts = (int*)c.slot[S_MB_CNT].p;
+    bl.offsets = bl.counts + ((bl.nblk + 3) & ~3L); // 16-byte aligned like counts (k_mb_offsets moves vectors)
+    hipLaunchKernelGGL(k_mb_collect<MASK_ONLY>, dim3((unsigned)bl.nblk), dim3(256), 0, st, MASK_ONLY ? nullptr : d_phi, d_mask, nx, ny, nz, dx,
+                       bl.staging, bl.counts);
+    hipLaunchKernelGGL(k_mb_offsets, dim3(1), dim3(1024), 0, st, (const int*)bl.counts, bl.nblk, bl.offsets);
+    HIPCHK(hipMemcpyAsync(&bl.nL, bl.offsets + bl.nblk, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (iters_done) *iters_done = nit;
-    if (host_ctl[2]) return fail(LSF_ERR_NAN, "RMS became NaN (the reference STOPs here, set3d.f90:458)");
+    bl.nchunks = (bl.nL + MB_CH - 1) / MB_CH;
+    return LSF_OK;
+}
+// phase 2 (nL > 0): the list in memory order and its brick keys, then -- `sort`, which needs keys_fit() -- sorted by key.  Both pairs of
+// arrays live in S_MB_KEY and S_MB_L; the sort's temporary storage is the staging buffer, free again once its segments have been
+// gathered (in stream order).
+int band_list_sort(BandList& bl, bool sort, hipStream_t st)
+{
+    int rc;
+    Ctx& c = ctx();
+    const size_t nL = (size_t)bl.nL;
+    if ((rc = ws(c.slot[S_MB_L], nL * sizeof(int)))) return rc;
+    if ((rc = ws(c.slot[S_MB_KEY], nL * 3 * sizeof(int)))) return rc;
+    bl.L = (int*)c.slot[S_MB_L].p;
+    unsigned* key_in = (unsigned*)c.slot[S_MB_KEY].p;
+    unsigned* key = key_in + nL;
+    int* L_in = (int*)(key + nL);
+    hipLaunchKernelGGL(k_mb_gather, dim3((unsigned)((bl.nblk + 3) / 4)), dim3(256), 0, st, (const int*)bl.staging, (const int*)bl.counts,
+                       (const int*)bl.offsets, bl.nblk, bl.nx + 1, bl.ny + 1, bl.nbx, bl.nby, sort ? L_in : bl.L, key_in);
+    if (!sort) return LSF_OK;
+    size_t tmp_bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key_in, key, L_in, bl.L, nL, 0, 32, st));
+    void* tmp = bl.staging;
+    if (tmp_bytes > bl.n * sizeof(int)) { // tiny grids
+        if ((rc = ws(c.slot[S_MB_TMP], tmp_bytes))) return rc;
+        tmp = c.slot[S_MB_TMP].p;
+    }
+    HIPCHK(rocprim::radix_sort_pairs(tmp, tmp_bytes, key_in, key, L_in, bl.L, nL, 0, 32, st));
+    bl.key = key;
     return LSF_OK;
 }
 
@@ -180,24 +228,11 @@ int minmax_band_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
     Ctx& c = ctx();
     if (gs && c.mm_band_off) return LSF_OK; // the looping launch timed out on this device before (said once, below)
     int rc;
-    const long nblk = (long)((n + MB_SCAN - 1) / MB_SCAN);
-    // staging of the list build (the band executor has no second field).  Asked for at the size the dense executors want their second
-    // field at (n doubles; the staging uses n ints of it): a call that turns out to need them -- a band above a quarter of the grid,
-    // cube40 as shipped -- does not free and allocate the buffer a second time
-    if ((rc = ws(c.slot[S_PONG], n * sizeof(double)))) return rc;
-    if ((rc = ws(c.slot[S_MB_CNT], (size_t)(2 * nblk + 8) * sizeof(int)))) return rc;
-    if ((rc = ws(c.slot[S_CTL], 64))) return rc;
-    int* staging = (int*)c.slot[S_PONG].p;
-    int* counts = (int*)c.slot[S_MB_CNT].p;
-    int* offsets = counts + ((nblk + 3) & ~3L); // 16-byte aligned like counts (k_mb_offsets moves vectors)
     const bool trace = getenv("LSF_TRACE") != nullptr;
     const double t_build0 = trace ? now_s() : 0.0;
-    hipLaunchKernelGGL(k_mb_collect<false>, dim3((unsigned)nblk), dim3(256), 0, st, (const double*)d_phi, (const int32_t*)d_nb, nx, ny, nz, dx,
-                       staging, counts);
-    hipLaunchKernelGGL(k_mb_offsets, dim3(1), dim3(1024), 0, st, (const int*)counts, nblk, offsets);
-    int nL = 0;
-    HIPCHK(hipMemcpyAsync(&nL, offsets + nblk, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    BandList bl;
+    if ((rc = band_list_count<false>(bl, d_phi, d_nb, nx, ny, nz, dx, st))) return rc;
+    const int nL = bl.nL, nchunks = bl.nchunks;
     // Which executor is faster is a question of list cells against grid points (round 6, profiles/r06_minmax_small.txt: two-sphere
     // fields of 48^3 ... 384^3 with 2 ... 57 % of the grid in the band, ms per exact iteration): this executor costs ~0.02 ms + 0.035 ms
     // per million LIST cells, the dense one ~0.15 ms (its launches) + 0.0105 ms per million GRID points -- so the band executor takes
@@ -206,9 +241,7 @@ int minmax_band_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
     // replaces the rule: test hook.
     bool take = nL > 0 && (double)nL <= 3.5e6 + 0.30 * (double)n;
     if (const char* e = getenv("LSF_MINMAX_BAND_MAX")) take = nL > 0 && (double)nL * 100.0 <= std::min(100.0, std::max(0.0, atof(e))) * (double)n;
-    if (!take) return LSF_OK;
-    const int nchunks = (nL + MB_CH - 1) / MB_CH;
-    if ((rc = ws(c.slot[S_MB_L], (size_t)nL * sizeof(int)))) return rc;
+    if (!take || !bl.keys_fit()) return LSF_OK; // (keys beyond 32 bits: dense executor)
     if ((rc = ws(c.slot[S_MB_NB6], (size_t)nL * 6 * sizeof(int)))) return rc;
     if ((rc = ws(c.slot[S_MB_AOLD], (size_t)nL * 2 * sizeof(double)))) return rc;
     if ((rc = ws(c.slot[S_MB_A0], (size_t)nL * 4 * sizeof(double)))) return rc; // curvature | three downstream values
@@ -218,44 +251,22 @@ int minmax_band_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
     if ((rc = ws(c.slot[S_PART], (size_t)nchunks * sizeof(double)))) return rc;
     if ((rc = ws(c.slot[S_PART2], 256 * sizeof(double)))) return rc;
     if ((rc = ws(c.slot[S_CHG], 1024))) return rc;
-    if ((rc = ws(c.slot[S_TRACE], (size_t)std::max(iter, 1) * sizeof(double)))) return rc;
-    int* L = (int*)c.slot[S_MB_L].p;
+    if ((rc = band_list_sort(bl, true, st))) return rc;
     double* V[2] = {(double*)c.slot[S_MB_AOLD].p, (double*)c.slot[S_MB_AOLD].p + nL};
     double* part = (double*)c.slot[S_PART].p;
     double* part2 = (double*)c.slot[S_PART2].p;
     int* chg = (int*)c.slot[S_CHG].p;
-    int* ctl = (int*)c.slot[S_CTL].p;
-    double* d_trace = (double*)c.slot[S_TRACE].p;
+    const dim3 b256(256), gl((unsigned)nchunks), ge((unsigned)cdiv(nL, 256));
+    hipLaunchKernelGGL(k_mb_links, ge, b256, 0, st, (const int*)bl.L, bl.key, nL, nx + 1, ny + 1, bl.nbx, bl.nby, (const double*)d_phi,
+                       (int*)c.slot[S_MB_NB6].p, V[0]);
+    StopLoop stop;
+    if ((rc = stop.begin(c, std::max(iter, 1), st))) return rc;
     MbArgs a;
-    a.F = d_phi, a.L = L, a.nb = (const int*)c.slot[S_MB_NB6].p, a.isband = (unsigned char*)c.slot[S_MB_BAND].p;
+    a.F = d_phi, a.L = bl.L, a.nb = (const int*)c.slot[S_MB_NB6].p, a.isband = (unsigned char*)c.slot[S_MB_BAND].p;
     a.curv = (double*)c.slot[S_MB_A0].p, a.down = a.curv + nL;
     a.nL = nL, a.sx = nx + 1, a.sxy = (long)(nx + 1) * (ny + 1), a.dx = dx, a.h1 = h1;
-    a.chunkflag = (int*)c.slot[S_BFLAG].p, a.stamp = (int*)c.slot[S_STAMP].p, a.nchunks = nchunks, a.partials = part, a.ctl = ctl;
+    a.chunkflag = (int*)c.slot[S_BFLAG].p, a.stamp = (int*)c.slot[S_STAMP].p, a.nchunks = nchunks, a.partials = part, a.ctl = stop.ctl;
     a.chg = chg;
-    const dim3 b256(256), gl((unsigned)nchunks), ge((unsigned)cdiv(nL, 256));
-    {
-        // the list in memory order and its brick keys -> sorted by key (both pairs of arrays live in the staging buffer's tail and in
-        // the slots of the list: the scan's segments are no longer needed once they have been gathered)
-        const int nbx = cdiv(nx + 1, 8), nby = cdiv(ny + 1, 8);
-        if ((double)nbx * nby * cdiv(nz + 1, 4) * 256.0 > 4.0e9) return LSF_OK; // keys beyond 32 bits: dense executor
-        if ((rc = ws(c.slot[S_MB_KEY], (size_t)nL * 3 * sizeof(int)))) return rc;
-        unsigned* key_in = (unsigned*)c.slot[S_MB_KEY].p;
-        unsigned* key = key_in + nL;
-        int* L_in = (int*)(key + nL);
-        hipLaunchKernelGGL(k_mb_gather, dim3((unsigned)((nblk + 3) / 4)), b256, 0, st, (const int*)staging, (const int*)counts,
-                           (const int*)offsets, nblk, nx + 1, ny + 1, nbx, nby, L_in, key_in);
-        size_t tmp_bytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key_in, key, L_in, L, (size_t)nL, 0, 32, st));
-        void* tmp = staging; // (free again: its segments have been gathered -- in stream order)
-        if (tmp_bytes > n * sizeof(int)) { // tiny grids
-            if ((rc = ws(c.slot[S_MB_TMP], tmp_bytes))) return rc;
-            tmp = c.slot[S_MB_TMP].p;
-        }
-        HIPCHK(rocprim::radix_sort_pairs(tmp, tmp_bytes, key_in, key, L_in, L, (size_t)nL, 0, 32, st));
-        hipLaunchKernelGGL(k_mb_links, ge, b256, 0, st, (const int*)L, (const unsigned*)key, nL, nx + 1, ny + 1, nbx, nby, (const double*)d_phi,
-                           (int*)c.slot[S_MB_NB6].p, V[0]);
-    }
-    HIPCHK(hipMemsetAsync(ctl, 0, 64, st));
     HIPCHK(hipMemsetAsync(a.stamp, 0, (size_t)nchunks * sizeof(int), st));
     if (trace) {
         HIPCHK(hipStreamSynchronize(st));
@@ -289,7 +300,6 @@ int minmax_band_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
     if (const char* e = getenv("LSF_MINMAX_TAIL_BLOCKS")) tail_blocks = std::min(512, std::max(8, atoi(e))); // measurement aid (all resident: <= 2 per CU)
     unsigned long long tail_timeout = 200000000ull; // 2 s of the 100 MHz clock
     if (const char* e = getenv("LSF_MINMAX_TAIL_TIMEOUT_TICKS")) tail_timeout = strtoull(e, nullptr, 10); // test hook
-    int host_ctl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int it = 0; it < iter; ++it) { // DO n = 1,iter (set3d.f90:394)
         const MbArgs q = args_of(it);
         hipLaunchKernelGGL((k_minmax_band<0>), gl, b256, 0, st, q);
@@ -300,13 +310,7 @@ int minmax_band_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
                                tail_timeout);
         }
         hipLaunchKernelGGL((k_minmax_band<2>), gl, b256, 0, st, q);
-        if (nchunks > 16384) {
-            hipLaunchKernelGGL(k_reduce_slices, dim3(256), dim3(256), 0, st, (const double*)part, (long)nchunks, part2);
-            hipLaunchKernelGGL(k_mb_finish, dim3(1), dim3(RED_T), 0, st, (const double*)part2, 256L, den, tol, d_trace, std::max(iter, 1), ctl);
-        } else {
-            hipLaunchKernelGGL(k_mb_finish, dim3(1), dim3(RED_T), 0, st, (const double*)part, (long)nchunks, den, tol, d_trace, std::max(iter, 1),
-                               ctl);
-        }
+        reduce_finish(k_mb_finish, part, nchunks, part2, den, tol, stop);
         if (gs && trace_fp) {
             int hc[MB_EPOCHS] = {0};
             HIPCHK(hipMemcpyAsync(hc, chg, sizeof hc, hipMemcpyDeviceToHost, st));
@@ -315,17 +319,11 @@ int minmax_band_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
             for (int f = 0; f < MB_EPOCHS && (f == 0 || hc[f - 1]); ++f) fprintf(stderr, " %d", hc[f]);
             fprintf(stderr, "\n");
         }
-        if ((it + 1) % CHECK_EVERY == 0 && it + 1 < iter) {
-            HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (host_ctl[0] || host_ctl[3]) break;
-        }
+        if (stop.poll(it, iter)) break;
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (host_ctl[3]) { // an iteration the tail launch did not certify (never observed): phi and the masks have not been written
-        if (host_ctl[5]) {
+    if ((rc = stop.finish())) return rc;
+    if (stop.host[CTL_UNCERT]) { // an iteration the tail launch did not certify (never observed): phi and the masks have not been written
+        if (stop.host[CTL_TIMEOUT]) {
             // a block waited for the others longer than the bound: the grid was not resident as a whole (a device shared with other
             // work).  Said once, whatever LSF_TRACE holds, and remembered: later calls go to the dense executors at once instead of
             // paying the bound and the list build again.
@@ -333,26 +331,21 @@ int minmax_band_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
             fprintf(stderr, "[lsf] min/max on the band: the looping launch (%d blocks) timed out waiting for its own blocks -- is the device shared? "
                             "This and every later exact min/max call on this device use the dense executors.\n", tail_blocks);
         } else if (trace)
-            fprintf(stderr, "[lsf] min/max on the band: iteration %d NOT certified -> dense executor\n", host_ctl[1] + 1);
+            fprintf(stderr, "[lsf] min/max on the band: iteration %d NOT certified -> dense executor\n", stop.count() + 1);
         return LSF_OK;
     }
-    if (gs && trace) fprintf(stderr, "[lsf] min/max on the band: at most %d fix passes per iteration\n", host_ctl[4] + 1);
+    if (gs && trace) fprintf(stderr, "[lsf] min/max on the band: at most %d fix passes per iteration\n", stop.host[CTL_FIXMAX] + 1);
     *dense = false;
-    const int nit = host_ctl[1];
-    const bool stopped_early = host_ctl[0] != 0; // converged or NaN: EXIT/STOP before narrowBand
-    if (nit >= 1) hipLaunchKernelGGL(k_mb_scatter, ge, b256, 0, st, (const int*)L, (const double*)V[nit & 1], nL, d_phi);
+    const int nit = stop.count();
+    const bool stopped_early = stop.stopped(); // converged or NaN: EXIT/STOP before narrowBand
+    if (nit >= 1) hipLaunchKernelGGL(k_mb_scatter, ge, b256, 0, st, (const int*)bl.L, (const double*)V[nit & 1], nL, d_phi);
     // masks the host would hold now (set3d.f90:448-460): narrowBand of the final field, or -- when the loop was left by EXIT / STOP
     // -- of the field before the last iteration: the final field with the list cells as that iteration froze them
     if (nit >= 1 && (!stopped_early || nit >= 2)) {
         if ((rc = narrowband_core(d_phi, d_nb, d_sb, n, dx, st))) return rc;
-        if (stopped_early) hipLaunchKernelGGL(k_mb_patch_masks, ge, b256, 0, st, (const int*)L, (const double*)V[(nit - 1) & 1], nL, dx, d_nb, d_sb);
+        if (stopped_early) hipLaunchKernelGGL(k_mb_patch_masks, ge, b256, 0, st, (const int*)bl.L, (const double*)V[(nit - 1) & 1], nL, dx, d_nb, d_sb);
     }
-    if (rms_trace && trace_cap > 0 && nit > 0)
-        HIPCHK(hipMemcpyAsync(rms_trace, d_trace, sizeof(double) * (size_t)std::min(nit, trace_cap), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (iters_done) *iters_done = nit;
-    if (host_ctl[2]) return fail(LSF_ERR_NAN, "RMS became NaN (the reference STOPs here, set3d.f90:458)");
-    return LSF_OK;
+    return stop.verdict(rms_trace, trace_cap, iters_done, "RMS became NaN (the reference STOPs here, set3d.f90:458)");
 }
 
 // Exact ordering: fixed-point passes (fast), as many per iteration as the field has needed so far; if a fixed point is
@@ -366,8 +359,8 @@ int minmax_core(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny, int
     const bool force_tiles = e && atoi(e) != 0;
     const int order = mode & LSF_ORDER_MASK;
     const bool args_ok = d_phi && d_nb && d_sb && iter > 0 && (order == LSF_ORDER_GS || order == LSF_ORDER_JACOBI) && !check_dims(nx, ny, nz);
-    // Default: the executor whose cost follows the band (lsf_minmax_band.hpp).  LSF_MINMAX_DENSE=1, a band above a quarter of the
-    // grid or a field beyond 32-bit point indices: the dense executors below.
+    // Default: the executor whose cost follows the band (lsf_minmax_band.hpp).  LSF_MINMAX_DENSE=1, a list beyond 3.5 M cells + 30 % of
+    // the grid or a field beyond 32-bit point indices: the dense executors below.
     const char* ed = getenv("LSF_MINMAX_DENSE");
     if (args_ok && !force_tiles && !(ed && atoi(ed) != 0)) {
         bool dense = false;

@@ -24,6 +24,9 @@ GRIDS = [(40, 33, 27), (10, 10, 10), (9, 12, 10), (5, 5, 5), (70, 21, 45), (13, 
 RAGGED = [(70, 21, 45), (13, 11, 75)]  # the two spheres lie outside these: one off-centre sphere, as tests/test_gpu_reinit_band.py
 TERMS = ["velocity", "speed", "both"]
 SCHEMES = [("rk3", 3), ("euler", 4)]
+# ... and, on the smallest grid with a WENO cell, runs that reach the host's look at the stop flag (every 8 steps): Euler with an odd count
+# ends in the second buffer after a look at step 8; RK3 with 8 steps ends on the step whose look is left out because it is the last
+STRICT_CASES = [(g, t, sc, st) for g in GRIDS for t in TERMS for sc, st in SCHEMES] + [((10, 10, 10), "both", "euler", 9), ((10, 10, 10), "both", "rk3", 8)]
 SEAMS = ["host", "device"]
 
 
@@ -100,9 +103,7 @@ def _run(lsf, seam, phi0, vel, F, n, dx, dt, steps, **kw):
 
 # ---------------------------------------------------------------------------------- 1: STRICT == the statement
 @pytest.mark.parametrize("seam", SEAMS)
-@pytest.mark.parametrize("scheme,steps", SCHEMES)
-@pytest.mark.parametrize("terms", TERMS)
-@pytest.mark.parametrize("npts", GRIDS, ids=_gid)
+@pytest.mark.parametrize("npts,terms,scheme,steps", STRICT_CASES, ids=lambda v: _gid(v) if isinstance(v, tuple) else None)
 def test_strict_is_bit_identical_to_the_statement(lsf, oracle, npts, terms, scheme, steps, seam):
     phi0, vel, F, n, dx, dt = _inputs(npts, terms)
     want, change, cfl = _want(npts, terms, scheme, steps)

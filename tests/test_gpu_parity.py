@@ -189,6 +189,32 @@ def test_reinit_jacobi_matches_oracle_jacobi(lsf, oracle, synth):
     assert _rms(phi, ref) < FAST_RMS_TOL
 
 
+def test_reinit_jacobi_stops_where_the_oracle_stops(lsf, oracle, synth):
+    """tol between the oracle's RMS values s and s + 1: the stop lands one sweep before the host's look at the stop flag (every 8
+    sweeps), on it and one past it.  Field and count as the oracle's with the same tol."""
+    nx, ny, nz = _n(synth)
+    dx, h = float(synth["dx"]), float(synth["h"])
+    _, _, tr = oracle.reinit(F(synth["phi0"]), nx, ny, nz, 19, dx, h, tol=0.0, order=oracle.JACOBI)
+    for s in (5, 6, 7):
+        lo, hi = sorted((tr[s], tr[s + 1]))
+        assert (hi - lo) / hi > 1e-3  # far above the summation allowance (1e-11)
+        tol = float(np.sqrt(lo * hi))
+        ref = F(synth["phi0"])
+        _, n_ref, tr_ref = oracle.reinit(ref, nx, ny, nz, 19, dx, h, tol=tol, order=oracle.JACOBI)
+        assert n_ref == s + 2
+        for seam in ("host", "device"):
+            phi = F(synth["phi0"])
+            if seam == "device":
+                t = _dev(phi)
+                rep = lsf.reinit(t, None, None, nx, ny, nz, 19, dx, h, tol=tol, order="jacobi", arith="strict")
+                phi = _host(t, phi.shape)
+            else:
+                rep = lsf.reinit(phi, None, None, nx, ny, nz, 19, dx, h, tol=tol, order="jacobi", arith="strict")
+            assert rep.count == n_ref and rep.converged, (s, seam, rep.count)
+            assert np.array_equal(phi, ref), (s, seam)
+            assert np.allclose(rep.rms, tr_ref, rtol=1e-11, atol=0)
+
+
 @pytest.mark.parametrize("shape", ["1x4", "2x2", "4x1", "4x2", "8x1", None])
 def test_jacobi_shared_interface_kernel_equals_per_cell_kernel(lsf, oracle, monkeypatch, shape):
     """FAST Jacobi sweeps run k_reinit_jacobi_sh (WENO interfaces shared along x and z, lsf_cell.hpp) in one of five
@@ -359,16 +385,20 @@ def test_minmax_cube40_to_convergence(lsf, cube40, mm_executor):
         assert np.allclose(rep.rms[:-1], cube40["rms_minmax"], rtol=1e-9, atol=0)
 
 
-def test_minmax_vs_oracle_other_shapes(lsf, oracle):
+def _shell_field(npts):
+    """a rough signed-distance-like field so that the band is a thin shell away from the walls; (phi0, dx)"""
     from levelsetfortran_amd import fields
 
+    _, dx = fields.sphere_phi0(npts, radius=0.45, centers=((0.0, 0.0, -0.1),), lo=-1.0, hi=1.0)
+    x, y, z, _ = fields.grid_axes(npts, -1.0, 1.0)
+    d = np.sqrt(x[:, None, None] ** 2 + y[None, :, None] ** 2 + (z[None, None, :] + 0.1) ** 2) - 0.45
+    return np.asfortranarray(d + 0.02 * np.sin(9 * x)[:, None, None] * np.cos(7 * y)[None, :, None]), dx
+
+
+def test_minmax_vs_oracle_other_shapes(lsf, oracle):
     for npts, order, oo in (((40, 33, 27), "gs", None), ((24, 50, 31), "gs", None), ((40, 33, 27), "jacobi", None)):
-        phi0, dx = fields.sphere_phi0(npts, radius=0.45, centers=((0.0, 0.0, -0.1),), lo=-1.0, hi=1.0)
         nx, ny, nz = (v - 1 for v in npts)
-        # a rough signed-distance-like field so that the band is a thin shell away from the walls
-        x, y, z, _ = fields.grid_axes(npts, -1.0, 1.0)
-        d = np.sqrt(x[:, None, None] ** 2 + y[None, :, None] ** 2 + (z[None, None, :] + 0.1) ** 2) - 0.45
-        phi0 = np.asfortranarray(d + 0.02 * np.sin(9 * x)[:, None, None] * np.cos(7 * y)[None, :, None])
+        phi0, dx = _shell_field(npts)
         nb, sb = oracle.narrowband(nx, ny, nz, dx, phi0)
         assert 0 < nb.sum() < nb.size // 2
         a, na, sa = phi0.copy(order="F"), nb.copy(order="F"), sb.copy(order="F")
@@ -377,6 +407,28 @@ def test_minmax_vs_oracle_other_shapes(lsf, oracle):
         rep = lsf.minmaxFlow(b, nb2, sb2, nx, ny, nz, 12, dx, 1e-4, tol=0.0, order=order)
         assert rep.count == 12
         assert np.array_equal(a, b) and np.array_equal(na, nb2) and np.array_equal(sa, sb2)
+
+
+def test_minmax_stops_where_the_oracle_stops(lsf, oracle, mm_executor):
+    """tol between the oracle's RMS values s and s + 1: the stop lands one iteration before the host's look at the stop flag (every 8
+    iterations), on it and one past it.  Field, count and the masks (those of the iteration before the exit) as the oracle's."""
+    npts = (40, 33, 27)
+    nx, ny, nz = (v - 1 for v in npts)
+    phi0, dx = _shell_field(npts)
+    nb, sb = oracle.narrowband(nx, ny, nz, dx, phi0)
+    for order, oo in (("gs", oracle.GS_LEX), ("jacobi", oracle.JACOBI)):
+        _, _, tr = oracle.minmax(phi0.copy(order="F"), nb.copy(order="F"), sb.copy(order="F"), nx, ny, nz, 20, dx, 1e-4, tol=0.0, order=oo)
+        for s in (5, 6, 7):
+            lo, hi = sorted((tr[s], tr[s + 1]))
+            assert (hi - lo) / hi > 1e-3  # far above the summation allowance
+            tol = float(np.sqrt(lo * hi))
+            a, na, sa = phi0.copy(order="F"), nb.copy(order="F"), sb.copy(order="F")
+            _, n_ref, _ = oracle.minmax(a, na, sa, nx, ny, nz, 20, dx, 1e-4, tol=tol, order=oo)
+            assert n_ref == s + 2
+            b, nb2, sb2 = phi0.copy(order="F"), nb.copy(order="F"), sb.copy(order="F")
+            rep = lsf.minmaxFlow(b, nb2, sb2, nx, ny, nz, 20, dx, 1e-4, tol=tol, order=order)
+            assert rep.count == n_ref and rep.converged, (order, s, rep.count)
+            assert np.array_equal(a, b) and np.array_equal(na, nb2) and np.array_equal(sa, sb2), (order, s)
 
 
 def test_zero_iterations_and_errors(lsf):
