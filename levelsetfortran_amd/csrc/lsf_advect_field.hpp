@@ -126,7 +126,7 @@ __global__ __launch_bounds__(ADV_BX* ADV_BY) void k_advect_stage(const double* _
                                                                   int nbx, int nby, int nbz)
 {
     __shared__ unsigned long long red[ADV_BX * ADV_BY / 64];
-    if (done && *done) return;
+    if (done && done[CTL_STOP]) return;
     const unsigned per = gridDim.x >> 3;
     const unsigned L = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
     if (L >= (unsigned)nbx * (unsigned)nby * (unsigned)nbz) return; // padding
@@ -217,12 +217,12 @@ __global__ __launch_bounds__(ADV_BX* ADV_BY) void k_advect_stage(const double* _
 }
 
 // End of a step: the maximum of the blocks' partials -> trace[step] (NaN if any change was NaN), the step counter, the NaN verdict.
-// ctl[0] = stop flag (later launches of the call leave at once), ctl[1] = steps completed, ctl[2] = 1: a change was NaN
+// CTL_STOP: later launches of the call leave at once; CTL_COUNT = steps completed; CTL_NAN: a change was NaN
 static __global__ __launch_bounds__(RED_T) void k_advect_finish(const unsigned long long* __restrict__ partials, long nPart, double* __restrict__ trace,
                                                                 int trace_cap, int* __restrict__ ctl)
 {
     __shared__ unsigned long long red[RED_T];
-    if (ctl[0]) return;
+    if (ctl[CTL_STOP]) return;
     unsigned long long t[4] = {0ull, 0ull, 0ull, 0ull}; // four loads in flight per round
     long p = threadIdx.x;
     for (; p + 3L * RED_T < nPart; p += 4L * RED_T) {
@@ -246,10 +246,10 @@ static __global__ __launch_bounds__(RED_T) void k_advect_finish(const unsigned l
     if (threadIdx.x == 0) {
         const unsigned long long bits = red[0];
         const bool nan = bits > ADV_INF_BITS;
-        const int n = ctl[1];
+        const int n = ctl[CTL_COUNT];
         if (n < trace_cap) trace[n] = nan ? __builtin_nan("") : __longlong_as_double((long long)bits);
-        ctl[1] = n + 1;
-        if (nan) ctl[0] = 1, ctl[2] = 1;
+        ctl[CTL_COUNT] = n + 1;
+        if (nan) ctl[CTL_STOP] = 1, ctl[CTL_NAN] = 1;
     }
 }
 

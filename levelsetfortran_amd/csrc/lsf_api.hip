@@ -415,9 +415,12 @@ long skew_spacing(const int* da, const int* db, int nx, int ny, int nz, int ta, 
     return q + 2;
 }
 
-double rms_denominator(int nx, int ny, int nz)
+// What the sum of squares of an RMS is divided by.  fp64: the reference's INTEGER*4 product nx*ny*nz (subs.f90:914 / set3d.f90:447),
+// wrapping like the reference -- it is negative for the 1536^3 grid of configuration 5 (RMS = NaN, STOP).  There is no fp32 reference
+// behaviour to mirror: fp32 fields divide by the true product (include/lsf.h).
+double rms_denominator(int nx, int ny, int nz, bool f32 = false)
 {
-    // INTEGER*4 product nx*ny*nz, subs.f90:914 / set3d.f90:447 (wraps like the reference)
+    if (f32) return (double)nx * (double)ny * (double)nz;
     return (double)(int32_t)((uint32_t)nx * (uint32_t)ny * (uint32_t)nz);
 }
 
@@ -650,10 +653,7 @@ int jacobi_loop(T* d_phi, const T* d_phiS_in, int nx, int ny, int nz, int iter, 
     const long n_part = jp.nparts + bc.nparts;
     if ((rc = ws(c.slot[S_PART], (size_t)n_part * sizeof(double)))) return rc;
     double* part = (double*)c.slot[S_PART].p;
-    // fp64: the reference's INTEGER*4 product nx*ny*nz (subs.f90:914), wrapping like the reference; it is negative for the
-    // 1536^3 grid of configuration 5 (RMS = NaN, STOP) and there is no fp32 reference behaviour to mirror: fp32 fields
-    // divide by the true product
-    const double den = F32 ? (double)nx * (double)ny * (double)nz : rms_denominator(nx, ny, nz);
+    const double den = rms_denominator(nx, ny, nz, F32);
     const int xwall = F32 ? F32_XWALL : 0;
 
     T* bufs[2] = {d_phi, (T*)c.slot[S_PONG].p};
@@ -882,6 +882,33 @@ int f32_mode_ok(int mode)
                     "fp32 fields: only LSF_ORDER_JACOBI | LSF_ARITH_FAST exists (the reference is fp64; there is no "
                     "fp32 field to be identical to)");
     return LSF_OK;
+}
+
+// one Jacobi sweep over the region [lo, hi) of a box.  The plans of the two precisions stay apart (jacobi_plan, jacobi_plan_f32).
+template <typename T>
+int sweep_box_impl(const T* d_in, T* d_out, const T* d_phiS, const lsf_box* box, const int lo[3], const int hi[3], double dx, double h,
+                   int mode, double* d_sumsq, void* stream)
+{
+    constexpr bool F32 = sizeof(T) == 4;
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (F32 && (rc = f32_mode_ok(mode))) return rc;
+    if ((rc = box_ok(box, lo, hi))) return rc;
+    if (!d_in || !d_out || !d_phiS || !d_sumsq) return fail(LSF_ERR_INVALID, "NULL pointer");
+    if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return LSF_OK; // empty region
+    if ((rc = sweep_region_ok(box, lo, hi))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // regions a few cells wide in x (the x rim of a decomposed sweep) run with the lanes along y (jacobi_plan)
+    const bool strict = (mode & LSF_ARITH_STRICT) != 0;
+    const int ext[3] = {box->lx, box->ly, box->lz};
+    const JacPlan jp = F32 ? jacobi_plan_f32(lo, hi) : jacobi_plan(lo, hi, strict, ext);
+    const long np = jp.nparts;
+    double* part = nullptr;
+    if ((rc = stream_partials(st, (size_t)np, &part))) return rc;
+    const Box bx{box->lx, box->ly, box->lz, box->gx0, box->gy0, box->gz0, box->nx, box->ny, box->nz};
+    if constexpr (F32) jacobi_launch_f32(jp, d_in, d_out, d_phiS, bx, lo, hi, dx, h, part, nullptr, 0, st); // (xwall = 0)
+    else jacobi_launch(jp, strict, d_in, d_out, d_phiS, bx, lo, hi, dx, h, part, nullptr, st);
+    return finish_partials(st, part, np, d_sumsq);
 }
 
 } // namespace
@@ -1535,23 +1562,7 @@ int lsf_jacobi_sweep_box(const double* d_in, double* d_out, const double* d_phiS
                          const int lo[3], const int hi[3], double dx, double h, int mode, double* d_sumsq,
                          void* stream)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if ((rc = box_ok(box, lo, hi))) return rc;
-    if (!d_in || !d_out || !d_phiS || !d_sumsq) return fail(LSF_ERR_INVALID, "NULL pointer");
-    if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return LSF_OK; // empty region
-    if ((rc = sweep_region_ok(box, lo, hi))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    // regions a few cells wide in x (the x rim of a decomposed sweep) run with the lanes along y (jacobi_plan)
-    const bool strict = (mode & LSF_ARITH_STRICT) != 0;
-    const int ext[3] = {box->lx, box->ly, box->lz};
-    const JacPlan jp = jacobi_plan(lo, hi, strict, ext);
-    const long np = jp.nparts;
-    double* part = nullptr;
-    if ((rc = stream_partials(st, (size_t)np, &part))) return rc;
-    const Box bx{box->lx, box->ly, box->lz, box->gx0, box->gy0, box->gz0, box->nx, box->ny, box->nz};
-    jacobi_launch(jp, strict, d_in, d_out, d_phiS, bx, lo, hi, dx, h, part, nullptr, st);
-    return finish_partials(st, part, np, d_sumsq);
+    return sweep_box_impl<double>(d_in, d_out, d_phiS, box, lo, hi, dx, h, mode, d_sumsq, stream);
 }
 
 int lsf_sumsq_begin(void* stream)
@@ -1634,21 +1645,7 @@ int lsf_jacobi_sweep_box_f32(const float* d_in, float* d_out, const float* d_phi
                              const int lo[3], const int hi[3], double dx, double h, int mode, double* d_sumsq,
                              void* stream)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if ((rc = f32_mode_ok(mode))) return rc;
-    if ((rc = box_ok(box, lo, hi))) return rc;
-    if (!d_in || !d_out || !d_phiS || !d_sumsq) return fail(LSF_ERR_INVALID, "NULL pointer");
-    if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return LSF_OK;
-    if ((rc = sweep_region_ok(box, lo, hi))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const JacPlan jp = jacobi_plan_f32(lo, hi);
-    const long np = jp.nparts;
-    double* part = nullptr;
-    if ((rc = stream_partials(st, (size_t)np, &part))) return rc;
-    const Box bx{box->lx, box->ly, box->lz, box->gx0, box->gy0, box->gz0, box->nx, box->ny, box->nz};
-    jacobi_launch_f32(jp, d_in, d_out, d_phiS, bx, lo, hi, dx, h, part, nullptr, 0, st);
-    return finish_partials(st, part, np, d_sumsq);
+    return sweep_box_impl<float>(d_in, d_out, d_phiS, box, lo, hi, dx, h, mode, d_sumsq, stream);
 }
 
 int lsf_reinit_f32_device(float* d_phi, const float* d_phiS, int nx, int ny, int nz, int iter, double dx, double h,
@@ -1788,12 +1785,10 @@ int lsf_multi_info(const lsf_multi* M, int* check_every, int* transport, int* rc
     if (transport) *transport = M->transport;
     if (rccl_ranks) *rccl_ranks = (int)M->rccl.comms.size();
     if (rccl_version) *rccl_version = M->rccl.version;
-    double he = 0.0;
-    for (auto& R : M->r64) he = std::max(he, R.host_enqueue_s);
-    for (auto& R : M->r32) he = std::max(he, R.host_enqueue_s);
-    double hc = 0.0;
-    for (auto& R : M->r64) hc = std::max(hc, R.host_calls_s);
-    for (auto& R : M->r32) hc = std::max(hc, R.host_calls_s);
+    double he = 0.0, hc = 0.0;
+    with_ranks(M, [&](auto& ranks) {
+        for (auto& R : ranks) he = std::max(he, R.host_enqueue_s), hc = std::max(hc, R.host_calls_s);
+    });
     if (host_calls_s) *host_calls_s = hc;
     if (host_enqueue_s) *host_enqueue_s = he;
     if (wall_s) *wall_s = M->last_wall_s;
@@ -1852,13 +1847,12 @@ int lsf_multi_create(int nx, int ny, int nz, const int* devices, int ndev, const
         }
         return LSF_OK;
     };
-    rc = f32 ? build(M->r32) : build(M->r64);
+    rc = with_ranks(M, build);
     if (!rc) {
         int ce = g_multi_check_every, tp = g_multi_transport;
         if (const char* e = getenv("LSF_MULTI_CHECK_EVERY")) ce = std::min(std::max(atoi(e), 1), (int)lsfm::MAX_CHECK);
         if (const char* e = getenv("LSF_MULTI_TRANSPORT"))
             tp = !std::strcmp(e, "rccl") ? LSF_TRANSPORT_RCCL : (!std::strcmp(e, "mock") ? LSF_TRANSPORT_MOCK : LSF_TRANSPORT_PEER);
-        if (const char* e = getenv("LSF_MULTI_GRAPHS")) M->graphs = atoi(e) != 0; // default off: measured slower, see lsf_multi.hpp
         rc = lsf_multi_configure(M, ce, tp);
     }
     if (rc) {
@@ -1875,8 +1869,9 @@ int lsf_multi_destroy(lsf_multi* M)
 {
     DeviceRestore restore_;
     if (!M) return LSF_OK;
-    for (auto& R : M->r64) lsfm::free_rank(R);
-    for (auto& R : M->r32) lsfm::free_rank(R);
+    with_ranks(M, [](auto& ranks) {
+        for (auto& R : ranks) lsfm::free_rank(R);
+    });
     delete M;
     return LSF_OK;
 }
@@ -1884,7 +1879,7 @@ int lsf_multi_destroy(lsf_multi* M)
 int lsf_multi_block(const lsf_multi* M, int r, int g0[3], int ext[3], int own_lo[3], int own_hi[3], int* device)
 {
     if (!M || r < 0 || r >= M->ndev) return fail(LSF_ERR_INVALID, "bad block index");
-    const lsfm::Geom& g = M->f32 ? M->r32[r].g : M->r64[r].g;
+    const lsfm::Geom& g = with_ranks(M, [&](auto& ranks) -> const lsfm::Geom& { return ranks[r].g; });
     for (int a = 0; a < 3; ++a) {
         if (g0) g0[a] = g.g0[a];
         if (ext) ext[a] = g.ext[a];
@@ -1900,8 +1895,7 @@ int lsf_multi_scatter(lsf_multi* M, const void* host_phi)
     DeviceRestore restore_;
     if (!M || !host_phi) return fail(LSF_ERR_INVALID, "NULL pointer");
     std::string err;
-    const int rc = M->f32 ? lsfm::scatter(M->r32, (const float*)host_phi, M->nx, M->ny, &err)
-                          : lsfm::scatter(M->r64, (const double*)host_phi, M->nx, M->ny, &err);
+    const int rc = with_ranks(M, [&](auto& ranks) { return lsfm::scatter(ranks, host_phi, M->nx, M->ny, &err); });
     M->result_parity = 0;
     return rc ? fail(rc, err) : LSF_OK;
 }
@@ -1934,14 +1928,12 @@ int lsf_multi_run(lsf_multi* M, int iter, double dx, double h, double tol, int m
     if (M->result_parity) {
         for (int r = 0; r < M->ndev; ++r) {
             HIPCHK(hipSetDevice(M->devs[r]));
-            if (M->f32) std::swap(M->r32[r].buf[0], M->r32[r].buf[1]);
-            else std::swap(M->r64[r].buf[0], M->r64[r].buf[1]);
+            with_ranks(M, [&](auto& ranks) { std::swap(ranks[r].buf[0], ranks[r].buf[1]); });
         }
         M->result_parity = 0;
     }
     std::string err;
-    const int rc = M->f32 ? lsfm::run(M, M->r32, iter, dx, h, tol, mode, sweeps_done, rms_trace, trace_cap, &err)
-                          : lsfm::run(M, M->r64, iter, dx, h, tol, mode, sweeps_done, rms_trace, trace_cap, &err);
+    const int rc = with_ranks(M, [&](auto& ranks) { return lsfm::run(M, ranks, iter, dx, h, tol, mode, sweeps_done, rms_trace, trace_cap, &err); });
     return rc ? fail(rc, err) : LSF_OK;
 }
 
@@ -1950,8 +1942,7 @@ int lsf_multi_gather(lsf_multi* M, void* host_phi)
     DeviceRestore restore_;
     if (!M || !host_phi) return fail(LSF_ERR_INVALID, "NULL pointer");
     std::string err;
-    const int rc = M->f32 ? lsfm::gather(M->r32, M->result_parity, (float*)host_phi, M->nx, M->ny, &err)
-                          : lsfm::gather(M->r64, M->result_parity, (double*)host_phi, M->nx, M->ny, &err);
+    const int rc = with_ranks(M, [&](auto& ranks) { return lsfm::gather(ranks, M->result_parity, host_phi, M->nx, M->ny, &err); });
     return rc ? fail(rc, err) : LSF_OK;
 }
 

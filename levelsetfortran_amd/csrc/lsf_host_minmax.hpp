@@ -106,7 +106,7 @@ int minmax_core_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
             hipLaunchKernelGGL(k_minmax_jacobi, dim3(jblocks), dim3(256), 0, st, A, B, mask, nx, ny, nz, dx, h1, part,
                                ctl);
         }
-        reduce_finish(k_finish, part, n_part, part2, den, tol, stop, 0); // (the fixed point alone has part2: always through the slices)
+        reduce_finish(part, n_part, part2, den, tol, stop, 0); // (the fixed point alone has part2: always through the slices)
         if (fixed_point && trace_fp) {
             int hc[MM_MAX_FIX + 1] = {0};
             HIPCHK(hipMemcpyAsync(hc, chg, sizeof hc, hipMemcpyDeviceToHost, st));
@@ -310,7 +310,7 @@ int minmax_band_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
                                tail_timeout);
         }
         hipLaunchKernelGGL((k_minmax_band<2>), gl, b256, 0, st, q);
-        reduce_finish(k_mb_finish, part, nchunks, part2, den, tol, stop);
+        reduce_finish(part, nchunks, part2, den, tol, stop);
         if (gs && trace_fp) {
             int hc[MB_EPOCHS] = {0};
             HIPCHK(hipMemcpyAsync(hc, chg, sizeof hc, hipMemcpyDeviceToHost, st));

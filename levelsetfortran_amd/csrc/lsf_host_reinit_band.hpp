@@ -57,7 +57,7 @@ int reinit_band_core(double* d_phi, const double* d_phiS, const int32_t* d_mask,
             hipLaunchKernelGGL((k_reinit_band<true>), gl, b256, 0, st, A, B, (const double*)ps, L, nL, nx, ny, nz, dx, h, part, (const int*)stop.ctl);
         else
             hipLaunchKernelGGL((k_reinit_band<false>), gl, b256, 0, st, A, B, (const double*)ps, L, nL, nx, ny, nz, dx, h, part, (const int*)stop.ctl);
-        reduce_finish(k_finish, part, nchunks, part2, (double)nL, tol, stop);
+        reduce_finish(part, nchunks, part2, (double)nL, tol, stop);
         if (stop.poll(s, max_sweeps)) break;
     }
     if ((rc = stop.finish())) return rc;

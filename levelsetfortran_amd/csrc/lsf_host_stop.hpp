@@ -1,25 +1,12 @@
 // lsf_host_stop.hpp -- the device-side stop flag of the iterative calls and the host's side of it: one driver for the Jacobi reinit, the
 // reinit on the band, the field advection and both min/max executors.  (The exact-GS drivers, lsf_host_gs.hpp and lsf_gs_slabs.hpp, keep
 // their own: there the verdict is tied to the batch planning.)  Included by lsf_api.hip inside its anonymous namespace.
-// A loop enqueues its sweeps ahead of the device; the last kernel of a sweep (k_finish, k_mb_finish, k_advect_finish) gives the verdict
+// A loop enqueues its sweeps ahead of the device; the last kernel of a sweep (k_finish, k_advect_finish) gives the verdict
 // and every kernel enqueued past a stop returns at once.  The host looks every CHECK_EVERY sweeps, so at most CHECK_EVERY - 1 empty
 // sweeps are enqueued past the verdict, and COUNT -- never the host's loop counter -- says which buffer holds the result.
 #pragma once
 
-// the control words (S_CTL: 16 ints, cleared by begin(); the host reads the first CTL_WORDS)
-enum CtlWord {
-    CTL_STOP = 0,    // finish kernel: converged (value < tol) or NaN -- everything enqueued behind it leaves at once
-    CTL_COUNT = 1,   // finish kernel: sweeps / iterations / steps completed, the one that set STOP included
-    CTL_NAN = 2,     // finish kernel: the RMS (advection: a change) was NaN; set together with STOP
-    // the exact min/max flow alone (zero in every other loop):
-    CTL_UNCERT = 3,  // k_minmax_fp<2> / k_minmax_band_tail: the fix passes of an iteration ran out (or timed out) before one changed
-                     // nothing -- the iteration is not certified; stops the device like STOP, COUNT stays at the iterations before it
-    CTL_FIXMAX = 4,  // the same kernels (atomicMax): most fix passes an iteration has needed so far
-    CTL_TIMEOUT = 5, // k_minmax_band_tail: UNCERT because a block waited for the others beyond the bound, not because passes ran out
-    CTL_WORDS = 8,
-    CTL_BYTES = 64   // of S_CTL
-};
-
+// The control words are CtlWord (lsf_kernels.hpp): the kernels and this driver address them by the same names.
 struct StopLoop {
     int* ctl = nullptr;        // device: the control words
     double* d_trace = nullptr; // device: one value per completed sweep, written by the finish kernel
@@ -71,13 +58,12 @@ struct StopLoop {
 };
 
 // The RMS: the partials summed in a fixed order by one block -- through 256 slice sums where the caller has room for them (part2) and
-// there are more than `slices_above` -- then the verdict (`finish`: k_finish or k_mb_finish)
-template <typename Finish>
-void reduce_finish(Finish finish, const double* part, long n, double* part2, double den, double tol, const StopLoop& stop, long slices_above = 16384)
+// there are more than `slices_above` -- then the verdict (k_finish)
+void reduce_finish(const double* part, long n, double* part2, double den, double tol, const StopLoop& stop, long slices_above = 16384)
 {
     if (part2 && n > slices_above) {
         hipLaunchKernelGGL(k_reduce_slices, dim3(256), dim3(256), 0, stop.st, part, n, part2);
         part = part2, n = 256L;
     }
-    hipLaunchKernelGGL(finish, dim3(1), dim3(RED_T), 0, stop.st, part, n, den, tol, stop.d_trace, stop.trace_entries, stop.ctl);
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(RED_T), 0, stop.st, part, n, den, tol, stop.d_trace, stop.trace_entries, stop.ctl);
 }

@@ -689,8 +689,22 @@ __global__ __launch_bounds__(64) void k_bc(const T* __restrict__ A, T* __restric
 // =============================================================================================
 // Sweep epilogue: fixed-order sum of the partials, RMS, stop test -- all on the device so that the
 // host never has to synchronise per sweep (subs.f90:902-926 / set3d.f90:435-458).
-// ctl[0]=done flag, ctl[1]=sweeps completed, ctl[2]=status (0 ok, 1 NaN)
 // =============================================================================================
+// the control words of the iterative calls (S_CTL: 16 ints, cleared by StopLoop::begin, lsf_host_stop.hpp; the host reads the first
+// CTL_WORDS)
+enum CtlWord {
+    CTL_STOP = 0,    // finish kernel: converged (value < tol) or NaN -- everything enqueued behind it leaves at once
+    CTL_COUNT = 1,   // finish kernel: sweeps / iterations / steps completed, the one that set STOP included
+    CTL_NAN = 2,     // finish kernel: the RMS (advection: a change) was NaN; set together with STOP
+    // the exact min/max flow alone (zero in every other loop):
+    CTL_UNCERT = 3,  // k_minmax_fp<2> / k_minmax_band_tail: the fix passes of an iteration ran out (or timed out) before one changed
+                     // nothing -- the iteration is not certified; stops the device like STOP, COUNT stays at the iterations before it
+    CTL_FIXMAX = 4,  // the same kernels (atomicMax): most fix passes an iteration has needed so far
+    CTL_TIMEOUT = 5, // k_minmax_band_tail: UNCERT because a block waited for the others beyond the bound, not because passes ran out
+    CTL_WORDS = 8,
+    CTL_BYTES = 64   // of S_CTL
+};
+
 // fixed-order sum of partials[0..nPart) by one block of RED_T threads: thread t adds elements t, t+RED_T, ... in
 // eight independent chains (the loads of a round are all in flight together: a serial chain of ~1 us loads is
 // what made the first version of this kernel cost 50 us), then a tree over the block.  Result valid in thread 0.
@@ -715,20 +729,22 @@ __device__ __forceinline__ double block_sum(const double* __restrict__ partials,
     return red[0];
 }
 
+// The verdict of a sweep / iteration.  An iteration of the exact min/max flow that is not certified is not counted (the host resumes
+// or reruns it); CTL_UNCERT is zero in every other loop.
 static __global__ __launch_bounds__(RED_T) void k_finish(const double* __restrict__ partials, long nPart, double den,
                                                   double tol, double* __restrict__ trace, int trace_cap,
                                                   int* __restrict__ ctl)
 {
     __shared__ double red[RED_T];
-    if (ctl[0]) return;
+    if (ctl[CTL_STOP] | ctl[CTL_UNCERT]) return;
     const double tot = block_sum(partials, nPart, red);
     if (threadIdx.x == 0) {
         const double rms = __builtin_sqrt(tot / den);
-        const int n = ctl[1];
+        const int n = ctl[CTL_COUNT];
         if (n < trace_cap) trace[n] = rms;
-        ctl[1] = n + 1;
-        if (rms < tol) ctl[0] = 1;
-        else if (rms != rms) { ctl[0] = 1; ctl[2] = 1; }
+        ctl[CTL_COUNT] = n + 1;
+        if (rms < tol) ctl[CTL_STOP] = 1;
+        else if (rms != rms) { ctl[CTL_STOP] = 1; ctl[CTL_NAN] = 1; }
     }
 }
 
@@ -879,7 +895,7 @@ __global__ __launch_bounds__(256) void k_minmax_fp(const double* __restrict__ A,
     __shared__ int flag, flag4[MM_CH / MM_SUB];
     __shared__ unsigned long long todo;
     constexpr int CH = PASS == 0 ? MM_CH : MM_SUB; // points one trip of the loop below covers
-    if (ctl[0]) return;
+    if (ctl[CTL_STOP]) return;
     if (PASS == 1 && changed_prev && *changed_prev == 0) return;
     const long sx = nx + 1, sxy = (long)(nx + 1) * (ny + 1), n = sxy * (nz + 1);
     const double dxx = 1. / (dx * dx);
@@ -992,9 +1008,9 @@ __global__ __launch_bounds__(256) void k_minmax_fp(const double* __restrict__ A,
         const int* c0 = changed_prev - (first - 1);
         int used = 0;
         for (int f = 0; f < first; ++f) used += c0[f] != 0;
-        atomicMax(ctl + 4, used);
+        atomicMax(ctl + CTL_FIXMAX, used);
         // the last allowed fix pass still changed something: the fixed point is not certified
-        if (*changed_prev != 0) ctl[3] = 1;
+        if (*changed_prev != 0) ctl[CTL_UNCERT] = 1;
     }
 }
 

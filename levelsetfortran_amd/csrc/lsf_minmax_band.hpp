@@ -222,7 +222,7 @@ struct MbArgs {
     int* stamp;            // [nchunks]
     int nchunks;
     double* partials;      // [nchunks]
-    int* ctl;              // [0] stop, [1] iterations done, [2] NaN, [3] an iteration was not certified, [4] most fix passes that changed cells
+    int* ctl;              // the control words (CtlWord, lsf_kernels.hpp): CTL_COUNT = iterations done
     int* chg;              // [64] chunks changed per fix pass of the iteration | [64] barrier word of the looping launch
 };
 constexpr int MB_EPOCHS = 64; // fix passes an iteration can take (epochs of iteration it: it * MB_EPOCHS + 1 + pass)
@@ -233,10 +233,10 @@ template <int PASS>
 __global__ __launch_bounds__(256) void k_minmax_band(MbArgs a)
 {
     __shared__ double red[4];
-    if (a.ctl[0] | a.ctl[3]) return;
+    if (a.ctl[CTL_STOP] | a.ctl[CTL_UNCERT]) return;
     // (pass 0 also zeroes the iteration's change counts and barrier word: no memset command between the launches.  The block that
     // finishes pass 2 last could add the partials and apply the stop test as well -- built and measured: 5 800 blocks counting
-    // themselves on ONE word cost 60 us per iteration on this chip, three times what the separate launch of k_mb_finish costs)
+    // themselves on ONE word cost 60 us per iteration on this chip, three times what the separate launch of k_finish costs)
     if (PASS == 0 && blockIdx.x == 0 && threadIdx.x <= MB_EPOCHS) a.chg[threadIdx.x] = 0;
     const int chunk = blockIdx.x, e = chunk * MB_CH + threadIdx.x;
     const int nL = a.nL;
@@ -338,7 +338,7 @@ __device__ __forceinline__ bool mb_visit_chunk(const MbArgs& a, int chunk, int e
 // First fix pass of an iteration: every band chunk, one chunk per block.
 static __global__ __launch_bounds__(256) void k_minmax_band_fix(MbArgs a, int epoch, int* __restrict__ changed_cur)
 {
-    if (a.ctl[0] | a.ctl[3]) return;
+    if (a.ctl[CTL_STOP] | a.ctl[CTL_UNCERT]) return;
     if (!a.chunkflag[blockIdx.x]) return;
     const bool any = mb_visit_chunk(a, (int)blockIdx.x, epoch);
     if (threadIdx.x == 0 && any) atomicAdd(changed_cur, 1); // number of chunks this pass changed
@@ -350,7 +350,7 @@ static __global__ __launch_bounds__(256) void k_minmax_band_fix(MbArgs a, int ep
 // dependent sign flips a min/max iteration resolves grows with the flow (two-sphere field at 512^3: 2 passes in the first ten
 // iterations, 17 by the fiftieth).  Stamps, change counts and evolving values travel past the non-coherent caches (sc1 stores
 // drained before the barrier, sc1 loads behind it: cdna_hip_programming.md G16); every spin is bounded: a grid that is not
-// resident as a whole (a device shared with other work) ends with ctl[3] and ctl[5] (= timed out, as opposed to "passes exhausted")
+// resident as a whole (a device shared with other work) ends with CTL_UNCERT and CTL_TIMEOUT (= timed out, as opposed to "passes exhausted")
 // and the host takes the dense executor -- for this call and, having said so once, for every later one on that device.  The host
 // sizes the grid from the occupancy query: at most one block per CU, never more than the device admits at once.
 // (blocks: one per CU measured best at 512^3 -- 64: 0.177, 128: 0.152, 256: 0.147, 512: 0.172 ms per iteration of a 50-iteration call)
@@ -360,7 +360,7 @@ static __global__ __launch_bounds__(256) void k_minmax_band_tail(MbArgs a, int e
 {
     __shared__ unsigned long long todo;
     __shared__ int sh_go;
-    if (a.ctl[0] | a.ctl[3]) return;
+    if (a.ctl[CTL_STOP] | a.ctl[CTL_UNCERT]) return;
     if (*changed_first == 0) return; // (written by the launch before this one)
     const int nchunks = a.nchunks, G = gridDim.x;
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
@@ -394,7 +394,7 @@ static __global__ __launch_bounds__(256) void k_minmax_band_tail(MbArgs a, int e
             while (ld_flag(bar) < target) {
                 if (__builtin_amdgcn_s_memrealtime() - t0 > timeout_ticks) {
                     go = -1;
-                    st_flag(a.ctl + 5, 1);
+                    st_flag(a.ctl + CTL_TIMEOUT, 1);
                     break;
                 }
                 __builtin_amdgcn_s_sleep(1);
@@ -408,25 +408,8 @@ static __global__ __launch_bounds__(256) void k_minmax_band_tail(MbArgs a, int e
         if (go != 1) break;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicMax(a.ctl + 4, pass + 1);
-        if (go != 0) a.ctl[3] = 1; // passes exhausted or a block timed out: not certified
-    }
-}
-
-// k_finish for the band executor: an iteration that is not certified is not counted (the host resumes it)
-static __global__ __launch_bounds__(RED_T) void k_mb_finish(const double* __restrict__ partials, long nPart, double den, double tol,
-                                                     double* __restrict__ trace, int trace_cap, int* __restrict__ ctl)
-{
-    __shared__ double red[RED_T];
-    if (ctl[0] | ctl[3]) return;
-    const double tot = block_sum(partials, nPart, red);
-    if (threadIdx.x == 0) {
-        const double rms = __builtin_sqrt(tot / den);
-        const int n = ctl[1];
-        if (n < trace_cap) trace[n] = rms;
-        ctl[1] = n + 1;
-        if (rms < tol) ctl[0] = 1;
-        else if (rms != rms) { ctl[0] = 1; ctl[2] = 1; }
+        atomicMax(a.ctl + CTL_FIXMAX, pass + 1);
+        if (go != 0) a.ctl[CTL_UNCERT] = 1; // passes exhausted or a block timed out: not certified
     }
 }
 

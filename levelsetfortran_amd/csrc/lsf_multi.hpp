@@ -26,6 +26,9 @@
 // so its schedule is tested through a stand-in transport (LSF_TRANSPORT_MOCK) and the library itself with one block.
 // levelsetfortran_amd/distributed.py remains the one-process-per-GPU variant of the same sweep over torch.distributed
 // (RCCL), built on the same four box calls.
+//
+// Included by lsf_api.hip alone, behind its anonymous namespace: the blocks call the typed box layer there directly (sweep_box_impl,
+// bc_box_impl, pack_multi_impl, rms_denominator), not the C entry points that wrap it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -238,16 +241,6 @@ struct RankState {
     double host_enqueue_s = 0.0;    // time this block's thread spent enqueuing during the last run, the waits for its neighbours'
                                     // threads and (blocks sharing a device) for the device's enqueue lock included
     double host_calls_s = 0.0;      // ... of which inside the runtime / library calls themselves
-    // The compute stream of a sweep as two HIP graphs per buffer parity (core | rims + BC + block sum; the wait for the ghosts
-    // sits between them): captured from the third sweep of a run on, replayed while the run's parameters stay the same
-    struct SweepGraph {
-        hipGraphExec_t core = nullptr, rest = nullptr;
-        const void *in = nullptr, *out = nullptr;
-        double dx = 0, h = 0;
-        int mode = -1;
-        bool failed = false;
-    } graph[2];
-    double* d_sum1 = nullptr;       // target of the captured reductions (copied into d_sums[slot] behind the graph)
     std::string err;
     int rc = LSF_OK;
 };
@@ -286,16 +279,19 @@ struct lsf_multi {
     int result_parity = 0;           // buf[result_parity] holds the field after lsf_multi_run
     std::vector<int> devs;
     int check_every = 8;             // sweeps per judging window (lsf_multi_configure)
-    // compute stream of a sweep replayed from two HIP graphs (LSF_MULTI_GRAPHS=1).  Off by default: with eight blocks of 128^3
-    // on one MI355X the host threads spend 9 % less time enqueuing (633 against 693 us per sweep) but the device takes 23 % longer
-    // (884 against 717 us per sweep): a graph launch costs the device more than the five plain launches it replaces
-    int graphs = 0;
     int transport = LSF_TRANSPORT_PEER;
     lsfm::Rccl rccl;
     double last_wall_s = 0.0;
     int last_sweeps_enqueued = 0;
     lsf_multi(int nd) : devlock(64), posted(64), taken_seq(64 * 6) { ndev = nd; }
 };
+
+// the blocks of an lsf_multi are fp32 or fp64: f(the vector in use) -- the one place that picks
+template <typename Multi, typename F>
+decltype(auto) with_ranks(Multi* M, F&& f)
+{
+    return M->f32 ? f(M->r32) : f(M->r64);
+}
 
 namespace lsfm {
 
@@ -327,28 +323,6 @@ namespace lsfm {
         }                                                                                                \
     } while (0)
 
-template <typename T> struct BoxCalls;
-template <> struct BoxCalls<double> {
-    static int sweep(const double* a, double* b, const double* s, const lsf_box* bx, const int* lo, const int* hi, double dx, double h,
-                     int mode, double* sum, void* st) { return lsf_jacobi_sweep_box(a, b, s, bx, lo, hi, dx, h, mode, sum, st); }
-    static int bc(const double* a, double* b, const lsf_box* bx, const int* lo, const int* hi, double dx, double* sum, void* st)
-    { return lsf_bc_box(a, b, bx, lo, hi, dx, sum, st); }
-    static int pack(const double* f, const lsf_box* bx, const int* lo, const int* hi, double* buf, void* st) { return lsf_pack_box(f, bx, lo, hi, buf, st); }
-    static int unpack(double* f, const lsf_box* bx, const int* lo, const int* hi, const double* buf, void* st) { return lsf_unpack_box(f, bx, lo, hi, buf, st); }
-    static int pack_all(const double* f, const lsf_box* bx, int n, const int (*lo)[3], const int (*hi)[3], double* const* bufs, void* st) { return lsf_pack_boxes(f, bx, n, lo, hi, bufs, st); }
-    static int unpack_all(double* f, const lsf_box* bx, int n, const int (*lo)[3], const int (*hi)[3], double* const* bufs, void* st) { return lsf_unpack_boxes(f, bx, n, lo, hi, bufs, st); }
-};
-template <> struct BoxCalls<float> {
-    static int sweep(const float* a, float* b, const float* s, const lsf_box* bx, const int* lo, const int* hi, double dx, double h,
-                     int mode, double* sum, void* st) { return lsf_jacobi_sweep_box_f32(a, b, s, bx, lo, hi, dx, h, mode, sum, st); }
-    static int bc(const float* a, float* b, const lsf_box* bx, const int* lo, const int* hi, double dx, double* sum, void* st)
-    { return lsf_bc_box_f32(a, b, bx, lo, hi, dx, sum, st); }
-    static int pack(const float* f, const lsf_box* bx, const int* lo, const int* hi, float* buf, void* st) { return lsf_pack_box_f32(f, bx, lo, hi, buf, st); }
-    static int unpack(float* f, const lsf_box* bx, const int* lo, const int* hi, const float* buf, void* st) { return lsf_unpack_box_f32(f, bx, lo, hi, buf, st); }
-    static int pack_all(const float* f, const lsf_box* bx, int n, const int (*lo)[3], const int (*hi)[3], float* const* bufs, void* st) { return lsf_pack_boxes_f32(f, bx, n, lo, hi, bufs, st); }
-    static int unpack_all(float* f, const lsf_box* bx, int n, const int (*lo)[3], const int (*hi)[3], float* const* bufs, void* st) { return lsf_unpack_boxes_f32(f, bx, n, lo, hi, bufs, st); }
-};
-
 template <typename T>
 void alloc_rank(RankState<T>& R)
 {
@@ -360,7 +334,6 @@ void alloc_rank(RankState<T>& R)
     for (int q = 0; q < 2; ++q) LSFM_HIP(hipMalloc((void**)&R.buf[q], np * sizeof(T)));
     LSFM_HIP(hipMalloc((void**)&R.phiS, np * sizeof(T)));
     LSFM_HIP(hipMalloc((void**)&R.d_sums, MAX_CHECK * sizeof(double)));
-    LSFM_HIP(hipMalloc((void**)&R.d_sum1, sizeof(double)));
     LSFM_HIP(hipHostMalloc((void**)&R.h_sums, 2 * MAX_CHECK * sizeof(double), hipHostMallocDefault));
     for (int f = 0; f < 6; ++f) {
         if (R.g.nb[f] < 0) continue;
@@ -402,11 +375,6 @@ void free_rank(RankState<T>& R)
         if (R.sendb[f]) (void)hipFree(R.sendb[f]);
     if (R.phiS) (void)hipFree(R.phiS);
     if (R.d_sums) (void)hipFree(R.d_sums);
-    if (R.d_sum1) (void)hipFree(R.d_sum1);
-    for (auto& g : R.graph) {
-        if (g.core) (void)hipGraphExecDestroy(g.core);
-        if (g.rest) (void)hipGraphExecDestroy(g.rest);
-    }
     if (R.h_sums) (void)hipHostFree(R.h_sums);
     if (R.halo) (void)hipEventDestroy(R.halo);
     if (R.compute) (void)hipStreamDestroy(R.compute);
@@ -454,7 +422,6 @@ struct RunShared {
 template <typename T>
 void worker(lsf_multi* M, std::vector<RankState<T>>* ranks, int r, SpinBarrier* bar, RunShared* S)
 {
-    using C = BoxCalls<T>;
     using clk = std::chrono::steady_clock;
     RankState<T>& R = (*ranks)[r];
     const int nr = (int)ranks->size();
@@ -469,7 +436,6 @@ void worker(lsf_multi* M, std::vector<RankState<T>>* ranks, int r, SpinBarrier* 
     std::mutex& dl = M->devlock[(size_t)R.dev % M->devlock.size()];
     const int K = std::min(std::max(M->check_every, 1), MAX_CHECK);
     const int transport = M->transport;
-    const bool use_graphs = M->graphs != 0;
     R.host_enqueue_s = R.host_calls_s = 0.0;
     long seq = S->seq0; // exchanges enqueued so far
 
@@ -495,7 +461,7 @@ void worker(lsf_multi* M, std::vector<RankState<T>>* ranks, int r, SpinBarrier* 
     auto unpack_faces = [&](T* a_in, int eq) -> int {
         T* r_buf[6];
         for (int k = 0; k < nf; ++k) r_buf[k] = R.recvb[eq][face_of[k]];
-        return C::unpack_all(a_in, &bx, nf, r_lo, r_hi, r_buf, R.comm);
+        return pack_multi_impl<T>(nullptr, a_in, &bx, nf, r_lo, r_hi, r_buf, 1, R.comm);
     };
 
     // ---- comm stream, first half: pack (and, PEER, push) the slabs of sweep s, exchange number e
@@ -506,7 +472,7 @@ void worker(lsf_multi* M, std::vector<RankState<T>>* ranks, int r, SpinBarrier* 
         const T* a_in = R.buf[q];
         // the input of this sweep is the output of the previous one (compute stream)
         if (e > S->seq0) LSFM_HIP(hipStreamWaitEvent(R.comm, R.done[(s - 1) & 1], 0));
-        LSFM_LSF(C::pack_all(a_in, &bx, nf, s_lo, s_hi, s_buf, R.comm));
+        LSFM_LSF(pack_multi_impl<T>(a_in, nullptr, &bx, nf, s_lo, s_hi, s_buf, 0, R.comm));
         for (int f = 0; f < 6; ++f) {
             const int p = R.g.nb[f];
             if (p < 0) continue;
@@ -574,67 +540,20 @@ void worker(lsf_multi* M, std::vector<RankState<T>>* ranks, int r, SpinBarrier* 
         }
         LSFM_HIP(hipEventRecord(R.halo, R.comm));
         // ---- compute stream
-        double* d_slot = R.d_sums + (s % K);
-        auto core_part = [&](double* d_sum) -> int {
-            if (hipMemsetAsync(d_sum, 0, sizeof(double), R.compute) != hipSuccess) return LSF_ERR_HIP;
-            int rc = lsf_sumsq_begin(R.compute);
-            if (rc == LSF_OK && R.g.core.vol() > 0)
-                rc = C::sweep(a_in, a_out, R.phiS, &bx, R.g.core.lo, R.g.core.hi, S->dx, S->h, S->mode, d_sum, R.compute); // overlaps the exchange
-            return rc;
-        };
-        auto rest_part = [&](double* d_sum) -> int {
-            int rc = LSF_OK;
-            for (size_t k = 0; k < R.g.rims.size() && rc == LSF_OK; ++k)
-                if (R.g.rims[k].vol() > 0)
-                    rc = C::sweep(a_in, a_out, R.phiS, &bx, R.g.rims[k].lo, R.g.rims[k].hi, S->dx, S->h, S->mode, d_sum, R.compute);
-            if (rc == LSF_OK) rc = C::bc(a_in, a_out, &bx, own_lo, own_hi, S->dx, d_sum, R.compute);
-            const int rc2 = lsf_sumsq_end(R.compute); // always close the bracket
-            return rc ? rc : rc2;
-        };
-        auto& G = R.graph[q];
-        const bool same = G.core && G.rest && G.in == a_in && G.out == a_out && G.dx == S->dx && G.h == S->h && G.mode == S->mode;
-        if (use_graphs && !same && !G.failed && e - S->seq0 >= 2) {
-            // capture this sweep (the two sweeps before it have sized every workspace: nothing allocates any more)
-            if (G.core) (void)hipGraphExecDestroy(G.core);
-            if (G.rest) (void)hipGraphExecDestroy(G.rest);
-            G.core = G.rest = nullptr;
-            hipGraph_t g1 = nullptr, g2 = nullptr;
-            bool ok = hipStreamBeginCapture(R.compute, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            if (ok) {
-                const int rc = core_part(R.d_sum1);
-                ok = hipStreamEndCapture(R.compute, &g1) == hipSuccess && rc == LSF_OK && g1;
-            }
-            if (ok) ok = hipStreamBeginCapture(R.compute, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            if (ok) {
-                const int rc = rest_part(R.d_sum1);
-                ok = hipStreamEndCapture(R.compute, &g2) == hipSuccess && rc == LSF_OK && g2;
-            } else {
-                (void)lsf_sumsq_end(R.compute);
-            }
-            if (ok) ok = hipGraphInstantiate(&G.core, g1, nullptr, nullptr, 0) == hipSuccess && hipGraphInstantiate(&G.rest, g2, nullptr, nullptr, 0) == hipSuccess;
-            if (g1) (void)hipGraphDestroy(g1);
-            if (g2) (void)hipGraphDestroy(g2);
-            (void)hipGetLastError();
-            if (ok) G.in = a_in, G.out = a_out, G.dx = S->dx, G.h = S->h, G.mode = S->mode;
-            else {
-                if (G.core) (void)hipGraphExecDestroy(G.core);
-                if (G.rest) (void)hipGraphExecDestroy(G.rest);
-                G.core = G.rest = nullptr, G.failed = true; // this object keeps to plain launches
-            }
-        }
-        if (use_graphs && G.core && G.rest && G.in == a_in && G.out == a_out && G.dx == S->dx && G.h == S->h && G.mode == S->mode) {
-            LSFM_HIP(hipGraphLaunch(G.core, R.compute));
-            LSFM_HIP(hipStreamWaitEvent(R.compute, R.halo, 0));
-            LSFM_HIP(hipGraphLaunch(G.rest, R.compute));
-            LSFM_HIP(hipMemcpyAsync(d_slot, R.d_sum1, sizeof(double), hipMemcpyDeviceToDevice, R.compute));
-        } else {
-            int rc = core_part(d_slot);
-            const hipError_t he = hipStreamWaitEvent(R.compute, R.halo, 0);
-            const int rc2 = rest_part(d_slot);
-            if (he != hipSuccess) { R.rc = LSF_ERR_HIP, R.err = hipGetErrorString(he); return; }
-            LSFM_LSF(rc);
-            LSFM_LSF(rc2);
-        }
+        double* d_sum = R.d_sums + (s % K);
+        LSFM_HIP(hipMemsetAsync(d_sum, 0, sizeof(double), R.compute));
+        int rc = lsf_sumsq_begin(R.compute);
+        if (rc == LSF_OK && R.g.core.vol() > 0)
+            rc = sweep_box_impl<T>(a_in, a_out, R.phiS, &bx, R.g.core.lo, R.g.core.hi, S->dx, S->h, S->mode, d_sum, R.compute); // overlaps the exchange
+        const hipError_t he = hipStreamWaitEvent(R.compute, R.halo, 0);
+        for (size_t k = 0; k < R.g.rims.size() && rc == LSF_OK && he == hipSuccess; ++k)
+            if (R.g.rims[k].vol() > 0)
+                rc = sweep_box_impl<T>(a_in, a_out, R.phiS, &bx, R.g.rims[k].lo, R.g.rims[k].hi, S->dx, S->h, S->mode, d_sum, R.compute);
+        if (rc == LSF_OK && he == hipSuccess) rc = bc_box_impl<T>(a_in, a_out, &bx, own_lo, own_hi, S->dx, d_sum, R.compute);
+        const int rc2 = lsf_sumsq_end(R.compute); // always close the bracket
+        if (he != hipSuccess) { R.rc = LSF_ERR_HIP, R.err = hipGetErrorString(he); return; }
+        LSFM_LSF(rc);
+        LSFM_LSF(rc2);
         LSFM_HIP(hipEventRecord(R.done[q], R.compute));
     };
     auto one_sweep = [&](int s) {
@@ -723,10 +642,7 @@ int run(lsf_multi* M, std::vector<RankState<T>>& ranks, int iter, double dx, dou
     const int nr = (int)ranks.size();
     RunShared S;
     S.dx = dx, S.h = h, S.tol = tol, S.iter = iter, S.mode = mode;
-    // the reference divides by the INTEGER*4 product nx*ny*nz (subs.f90:914), which wraps; fp32 fields have no reference
-    // to mirror and use the true product (include/lsf.h)
-    S.den = sizeof(T) == 4 ? (double)M->nx * M->ny * M->nz
-                           : (double)(int32_t)((uint32_t)M->nx * (uint32_t)M->ny * (uint32_t)M->nz);
+    S.den = rms_denominator(M->nx, M->ny, M->nz, sizeof(T) == 4);
     S.vals.assign((size_t)nr * MAX_CHECK, 0.0);
     S.seq0 = M->posted[0].load();
     for (auto& R : ranks) { // phiS = phi on entry (subs.f90:731)
@@ -784,8 +700,9 @@ int run(lsf_multi* M, std::vector<RankState<T>>& ranks, int iter, double dx, dou
 
 // host <-> blocks: every block receives its local box (ghost layers included) / returns its owned points
 template <typename T>
-int scatter(std::vector<RankState<T>>& ranks, const T* host, int nx, int ny, std::string* err)
+int scatter(std::vector<RankState<T>>& ranks, const void* host_phi, int nx, int ny, std::string* err)
 {
+    const T* host = (const T*)host_phi;
     const size_t sx = (size_t)nx + 1, sxy = sx * ((size_t)ny + 1);
     std::vector<T> tmp;
     for (auto& R : ranks) {
@@ -804,8 +721,9 @@ int scatter(std::vector<RankState<T>>& ranks, const T* host, int nx, int ny, std
     return LSF_OK;
 }
 template <typename T>
-int gather(std::vector<RankState<T>>& ranks, int parity, T* host, int nx, int ny, std::string* err)
+int gather(std::vector<RankState<T>>& ranks, int parity, void* host_phi, int nx, int ny, std::string* err)
 {
+    T* host = (T*)host_phi;
     const size_t sx = (size_t)nx + 1, sxy = sx * ((size_t)ny + 1);
     std::vector<T> tmp;
     for (auto& R : ranks) {

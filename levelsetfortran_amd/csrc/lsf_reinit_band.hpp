@@ -51,7 +51,7 @@ __global__ __launch_bounds__(MB_CH) void k_reinit_band(const double* __restrict_
                                                        double* __restrict__ partials, const int* __restrict__ done)
 {
     __shared__ double red[MB_CH / 64];
-    if (*done) return;
+    if (done[CTL_STOP]) return;
     const int e = blockIdx.x * MB_CH + threadIdx.x;
     double acc = 0.0;
     if (e < nL) {
