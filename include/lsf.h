@@ -282,6 +282,63 @@ int lsf_distance_fill_device(double *d_phi, const int32_t *d_mask, int nx, int n
                              int max_rounds, int *rounds_done, int64_t *changed_trace, int trace_cap,
                              int64_t *frozen_points, void *stream);
 
+/* ---- extension off the surface: a quantity carried constant along the normals of phi ----------
+ * No reference counterpart.  Solves grad(q) . grad(phi) = 0 on every point that is not FROZEN, with q on the frozen points as boundary
+ * data, by rounds of 8 in-place raster sweeps of the first-order upwind update in |phi| (extension velocities of Adalsteinsson and
+ * Sethian in the fast-sweeping form of Zhao): what gives lsf_advect_field its `speed` or u, v, w AT EVERY GRID POINT from values known
+ * on or next to the surface only, and a speed that is constant along the normals keeps phi a distance while it moves.  q, phi and
+ * mask have the layout of every other entry point.  rounds_done, changed_trace and info may be NULL.
+ *   FROZEN   the rule of lsf_distance_fill.  mask == NULL: the points, wall points included, with |phi| < far; far = band * dx,
+ *            computed once on the host.  With a mask: the points with mask == 1, and band is ignored.  Frozen points hold the
+ *            caller's q and are never written.  phi and mask are inputs only: read, never written.
+ *   start    every other point is UNKNOWN: whatever q holds there on entry is ignored (a NaN there is legal).  Unknown is
+ *            represented in the field by NaN.
+ *   round    8 in-place raster sweeps over all points 0..n of each axis, in the direction order of lsf_distance_fill:
+ *            (+,+,+) (+,+,-) (+,-,-) (-,-,-) (-,+,-) (-,-,+) (-,+,+) (+,-,+).
+ *   visit    of a non-frozen point p, with f = |phi| (a neighbour outside the grid has f = +inf) and q as it is at that moment of
+ *            the sweep.  For each axis A: n_A is the one of the two neighbours with the smaller f, the one at the lower index on
+ *            a tie;  w_A = f(p) - f(n_A);  the axis is USED when w_A > 0 and q(n_A) is not NaN;
+ *              t_A = w_A * q(n_A) and s_A = w_A when used, both 0.0 otherwise;
+ *              den = (s_x + s_y) + s_z;  den == 0: nothing happens.  Otherwise new = ((t_x + t_y) + t_z) / den;
+ *              if !(new == old) -- true for an unknown old -- new is stored and the visit is counted.
+ *            Evaluated exactly as written, left to right, without contraction; / is the IEEE division.
+ *   trace    changed_trace[r], r < trace_cap: the number of counted visits of round r (an integer: no arrival order in it).
+ *   stop     after the first round whose count is 0 (that round is counted) or after max_rounds; rounds_done = rounds run.
+ *            Reaching max_rounds is LSF_OK.  A point depends only on neighbours of strictly smaller |phi|, so the dependency
+ *            graph has no cycle and the fixed point is reached EXACTLY: the rounds stop by themselves, with a count of 0.
+ *   info     [0] frozen points  [1] non-frozen points that hold a value on return  [2] UNREACHED points, still NaN on return.
+ *            Written on LSF_OK only.  Unreached points are left NaN, loudly, and reported -- never filled with a guess: a point
+ *            none of whose neighbours has a smaller |phi| than its own has nothing to take a value from, so a PLATEAU of |phi|
+ *            can never be reached.  Such a plateau is the +-far of a clamped lsf_mesh_distance field or the 1.0 of lsf_phi0: run
+ *            lsf_distance_fill or lsf_reinit first.
+ *   result   field, rounds_done, trace and info are those of the serial loops above, bit for bit, on both seams, on any stream,
+ *            from run to run -- after every round, not only at the fixed point (tests/extend_ref.py is that serial statement).
+ *   range    the bit promise is stated for finite q on the frozen points and finite phi whose products w * q do not overflow
+ *            (every new value is then a weighted mean of finite values); nothing is promised beyond it.
+ *   errors   LSF_ERR_INVALID, all detected before q is written, the offending count in lsf_last_error() where there is one: a NULL
+ *            q or phi; nx, ny or nz < 1 or more than 2^31 - 1 points; dx not finite or <= 0; mask == NULL with band not finite or
+ *            <= 0; max_rounds < 1; no frozen point; a non-finite q on a frozen point (count); a non-finite phi anywhere (count).
+ *            Unlike lsf_distance_fill the frozen set need NOT separate the signs: |phi| orders the points on both sides.  No
+ *            device: LSF_ERR_NO_DEVICE -- there is no CPU fallback.
+ *   seams    lsf_extend_field takes phi, an input only, through its twin under lsf_mirror exactly as lsf_extract_surface takes its
+ *            phi, and the mask as lsf_distance_fill takes its mask.  q has NO twin and lsf_mirror does not apply to it: it is staged
+ *            in a workspace slot of its own, copied in on every call and copied back on LSF_OK only, LSF_MIRROR_LAZY or not.
+ *            lsf_extend_field_device returns after the stream is synchronised (the host reads one count per round).
+ * Guidance: the scheme is FIRST ORDER; every value is a convex combination of frozen values, so the result stays inside their
+ * [min, max].  A caller with u, v, w calls three times.  Convergence took 2 - 4 rounds on the test inputs (6 on two spheres at 512^3).
+ * Workspace beyond the caller's arrays: the bit per point of lsf_distance_fill plus 48 bytes of counters; the host seam adds one
+ * field for q.  Work: a round is 8 * (tiles_x + tiles_y + tiles_z - 2) dependent launches of 32 x 8 x 8-point tiles, as in
+ * lsf_distance_fill, each tile loading two fields.  Out of scope: several quantities in one call, higher order, fp32, multi-GPU,
+ * q taken from mesh-node data.
+ * Timed once beside lsf_distance_fill on the same field (profiles/extend_field_time.txt, from profiles/micro/extend_field_time.py):
+ * 19.2 ms per round at 256^3 against 14.4, 110 ms at 512^3 against 36.  No speed is claimed beyond that record. */
+#define LSF_EXTEND_INFO_LEN 3
+int lsf_extend_field(double *q, const double *phi, const int32_t *mask, int nx, int ny, int nz, double dx, double band,
+                     int max_rounds, int *rounds_done, int64_t *changed_trace, int trace_cap, int64_t info[LSF_EXTEND_INFO_LEN]);
+int lsf_extend_field_device(double *d_q, const double *d_phi, const int32_t *d_mask, int nx, int ny, int nz, double dx,
+                            double band, int max_rounds, int *rounds_done, int64_t *changed_trace, int trace_cap,
+                            int64_t info[LSF_EXTEND_INFO_LEN], void *stream);
+
 /* ---- level-set transport: WENO5 / TVD-RK3 advection by a velocity field and along the normal ----------
  * No reference counterpart ("Currently has no capability to do moving geometry", the reference's README).  Advances
  *     phi_t + u . grad(phi) + F |grad(phi)| = 0

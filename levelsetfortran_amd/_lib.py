@@ -23,6 +23,7 @@ LSF_MIRROR_TRUST, LSF_MIRROR_LAZY = 1, 2  # include/lsf.h: lsf_mirror flags
 LSF_MESH_UNSIGNED, LSF_MESH_INFO_LEN = 1, 4  # include/lsf.h: lsf_mesh_distance
 LSF_ADVECT_RK3, LSF_ADVECT_EULER = 0, 1  # include/lsf.h: lsf_advect_field
 LSF_SURF_INFO_LEN = 4  # include/lsf.h: lsf_extract_surface
+LSF_EXTEND_INFO_LEN = 3  # include/lsf.h: lsf_extend_field
 LSF_TRANSPORT_PEER, LSF_TRANSPORT_RCCL, LSF_TRANSPORT_MOCK = 0, 1, 2  # include/lsf.h: lsf_multi_configure
 
 
@@ -84,6 +85,10 @@ SIGNATURES = {
                                   POINTER(ctypes.c_int64)]),
     "lsf_distance_fill_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p,
                                          c_int, POINTER(ctypes.c_int64), c_void_p]),
+    "lsf_extend_field": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p, c_int,
+                                 c_void_p]),
+    "lsf_extend_field_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p,
+                                        c_int, c_void_p, c_void_p]),
     "lsf_advect_field": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_int, c_int,
                                  POINTER(c_int), POINTER(c_double), c_void_p, c_int]),
     "lsf_advect_field_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_int,

@@ -26,6 +26,7 @@
 #include "lsf_reinit_band.hpp"
 #include "lsf_mesh_distance.hpp"
 #include "lsf_distance_fill.hpp"
+#include "lsf_extend_field.hpp"
 #include "lsf_advect_field.hpp"
 #include "lsf_extract_surface.hpp"
 
@@ -184,7 +185,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -726,6 +727,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_mesh.hpp"
 
 #include "lsf_host_distance_fill.hpp"
+
+#include "lsf_host_extend_field.hpp"
 
 #include "lsf_host_advect_field.hpp"
 
@@ -1419,6 +1422,47 @@ int lsf_distance_fill(double* phi, const int32_t* mask, int nx, int ny, int nz, 
     if (rc == LSF_OK) return twin_out(c, c.twin_phi, S_HPHI, phi, n * sizeof(double));
     twin_drop(c.twin_phi);
     return rc;
+}
+
+int lsf_extend_field_device(double* d_q, const double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, double band,
+                            int max_rounds, int* rounds_done, int64_t* changed_trace, int trace_cap, int64_t info[LSF_EXTEND_INFO_LEN],
+                            void* stream)
+{
+    Trace trace_("lsf_extend_field_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = extend_field_args_ok(d_q, d_phi, d_mask, nx, ny, nz, dx, band, max_rounds))) return rc;
+    return extend_field_core(d_q, d_phi, d_mask, nx, ny, nz, dx, band, max_rounds, rounds_done, changed_trace, trace_cap, info,
+                             (hipStream_t)stream);
+}
+
+int lsf_extend_field(double* q, const double* phi, const int32_t* mask, int nx, int ny, int nz, double dx, double band, int max_rounds,
+                     int* rounds_done, int64_t* changed_trace, int trace_cap, int64_t info[LSF_EXTEND_INFO_LEN])
+{
+    Trace trace_("lsf_extend_field");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = extend_field_args_ok(q, phi, mask, nx, ny, nz, dx, band, max_rounds))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    // q has no twin: it is staged in a slot of its own from the host on every call and comes home on LSF_OK, lsf_mirror or not.
+    // Staged before phi's twin is touched, as lsf_advect_field stages its inputs.
+    if ((rc = ws(c.slot[S_EXT_Q], n * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpy(c.slot[S_EXT_Q].p, q, n * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // phi is an input only, as in lsf_extract_surface
+    const int32_t* d_mask = nullptr;
+    if (mask) { // as in lsf_distance_fill
+        const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+        Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+        const Slot sm = is_nb ? S_HNB : S_HSB;
+        if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+        d_mask = (const int32_t*)c.slot[sm].p;
+    }
+    if ((rc = extend_field_core((double*)c.slot[S_EXT_Q].p, (const double*)c.slot[S_HPHI].p, d_mask, nx, ny, nz, dx, band, max_rounds,
+                                rounds_done, changed_trace, trace_cap, info, nullptr)))
+        return rc;
+    HIPCHK(hipMemcpy(q, c.slot[S_EXT_Q].p, n * sizeof(double), hipMemcpyDeviceToHost));
+    return LSF_OK;
 }
 
 int lsf_advect_field_device(double* d_phi, const double* d_u, const double* d_v, const double* d_w, const double* d_speed, int nx, int ny, int nz,

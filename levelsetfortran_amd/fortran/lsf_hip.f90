@@ -19,6 +19,8 @@
 !                                                        triangles, clamped at width*dx (include/lsf.h: lsf_mesh_distance)
 !   distanceFill(phi,nx,ny,nz,dx,band)                   no reference counterpart: first-order distance on every point with
 !                                                        |phi| >= band*dx by fast sweeping (include/lsf.h: lsf_distance_fill)
+!   extendField(q,phi,nx,ny,nz,dx,band)                  no reference counterpart: q carried off the points with |phi| < band*dx
+!                                                        constant along the normals of phi (include/lsf.h: lsf_extend_field)
 !   advectField(phi,u,v,w,nx,ny,nz,dx,dt,steps)          no reference counterpart: transport of phi by the velocity field
 !                                                        (u,v,w), WENO5 / TVD-RK3 (include/lsf.h: lsf_advect_field)
 !   extractSurface(phi,nx,ny,nz,dx,xLo,iso,surfX,nSurfNode,surfElem,nSurfElem)
@@ -85,6 +87,7 @@ PUBLIC :: reinit, narrowBand, minmaxFlow, phi0Init, advectNodes, lsf_env_real, l
 PUBLIC :: reinitBand
 PUBLIC :: meshDistance
 PUBLIC :: distanceFill
+PUBLIC :: extendField
 PUBLIC :: advectField
 PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
@@ -199,6 +202,19 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: changed_trace(*),frozen_points
       INTEGER(c_int) :: rc
    END FUNCTION lsf_distance_fill
+   ! int lsf_extend_field(double*,const double*,const int32_t*,int,int,int,double,double,int,int*,int64_t*,int,int64_t[3])
+   FUNCTION lsf_extend_field(q,phi,mask,nx,ny,nz,dx,band,max_rounds,rounds_done,changed_trace,trace_cap,info) &
+            BIND(C,NAME='lsf_extend_field') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(INOUT) :: q(*)
+      REAL(c_double), INTENT(IN) :: phi(*)
+      TYPE(c_ptr), VALUE :: mask             ! NULL: the frozen set is |phi| < band*dx
+      INTEGER(c_int), VALUE :: nx,ny,nz,max_rounds,trace_cap
+      REAL(c_double), VALUE :: dx,band
+      INTEGER(c_int), INTENT(OUT) :: rounds_done
+      INTEGER(c_int64_t), INTENT(OUT) :: changed_trace(*),info(3)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_extend_field
    ! int lsf_advect_field(double*,const double*,const double*,const double*,const double*,int,int,int,double,double,int,int,int,
    !                      int*,double*,double*,int)
    FUNCTION lsf_advect_field(phi,u,v,w,speed,nx,ny,nz,dx,dt,steps,scheme,mode,steps_done,cfl,change_trace,trace_cap) &
@@ -634,6 +650,32 @@ PRINT*, " Distance fill: ",done," rounds, ",frozen," frozen points, last round l
 PRINT*
 
 END SUBROUTINE distanceFill
+
+!*************************************************************************************!
+! A quantity carried off the surface constant along the normals of phi (include/lsf.h:
+! lsf_extend_field; no reference counterpart).  The points with |phi| < band*dx hold the
+! caller's q and are never written; every other point receives the value that reaches it
+! along the normal, at most 64 rounds of 8 raster sweeps.  phi is not written.  Points a
+! plateau of |phi| keeps out of reach stay NaN and are counted.  Prints the rounds run,
+! the visits the last one changed (0: converged) and the unreached points.
+!*************************************************************************************!
+SUBROUTINE extendField(q,phi,nx,ny,nz,dx,band)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+REAL,INTENT(IN) :: dx,band
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: q
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+INTEGER(c_int), PARAMETER :: max_rounds = 64
+INTEGER(c_int64_t) :: trace(max_rounds),info(3)
+INTEGER(c_int) :: rc,done
+
+CALL lsf_set_mirror()
+rc = lsf_extend_field(q,phi,c_null_ptr,nx,ny,nz,dx,band,max_rounds,done,trace,max_rounds,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_extend_field',rc)
+PRINT*, " Extend field: ",done," rounds, ",info(1)," frozen points, last round changed ",trace(done),", unreached ",info(3)
+PRINT*
+
+END SUBROUTINE extendField
 
 !*************************************************************************************!
 ! Transport of the level set by a velocity field, phi_t + u.grad(phi) = 0 (include/lsf.h:

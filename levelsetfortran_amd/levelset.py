@@ -20,6 +20,10 @@ and the first-order distance on the rest of the grid from a frozen band (fast sw
 
   distanceFill(phi, nx, ny, nz, dx, band=... | mask=...)        include/lsf.h: lsf_distance_fill
 
+and a quantity known on that band carried to the rest of the grid constant along the normals (no reference counterpart):
+
+  extendField(q, phi, nx, ny, nz, dx, band=... | mask=...)      include/lsf.h: lsf_extend_field
+
 Fields are updated IN PLACE like the INTENT(INOUT) dummies of the reference.  A field is either
   * a numpy float64 array, Fortran-ordered with shape (nx+1, ny+1, nz+1) (or 1-D of that size):
     the host seam -- the library copies it to HBM and back (lsf_reinit / lsf_minmax), or
@@ -42,7 +46,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "advectField", "AdvectReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "advectField", "AdvectReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -404,6 +408,59 @@ def distanceFill(phi, nx: int, ny: int, nz: int, dx: float, *, band: Optional[fl
     n = done.value
     changed = [int(v) for v in trace[:n]]
     return FillReport(n, changed, int(frozen.value), bool(n and changed[-1] == 0))
+
+
+class ExtendReport(NamedTuple):
+    """What lsf_extend_field reports (include/lsf.h): rounds of 8 sweeps run, the visits that changed a value in each of them, the
+    size of the frozen set, the other points that hold a value / are still NaN, and whether the last round changed nothing."""
+    rounds: int
+    changed: List[int]
+    frozen_points: int
+    reached: int
+    unreached: int
+    converged: bool
+
+
+def extendField(q, phi, nx: int, ny: int, nz: int, dx: float, *, band: Optional[float] = None, mask=None, max_rounds: int = 64) -> ExtendReport:
+    """Carries `q` off a frozen set constant along the normals of `phi`, grad(q) . grad(phi) = 0 (include/lsf.h: lsf_extend_field);
+    `q` is updated in place, `phi` and `mask` are read only.
+
+    Exactly one of `band` / `mask`, as in distanceFill: band=w freezes the points with |phi| < w*dx, mask (int32, same layout)
+    freezes the points where it is 1.  Frozen points keep the caller's q; what q holds elsewhere on entry is ignored.  Every other
+    point receives the first-order upwind value, rounds of 8 raster sweeps until a round changes nothing or max_rounds is reached
+    (then converged is False).  A point that a plateau of |phi| keeps out of reach stays NaN and is counted in `unreached`: run
+    distanceFill or reinit on phi first.  q and phi are both numpy arrays or both torch CUDA tensors.
+    """
+    if (band is None) == (mask is None):
+        raise ValueError("give exactly one of band= (cells; freezes |phi| < band*dx) and mask= (int32; freezes mask == 1)")
+    if _is_torch(q) != _is_torch(phi) or (mask is not None and _is_torch(mask) != _is_torch(q)):
+        raise TypeError("q, phi and mask must all be numpy arrays (host seam) or all be torch CUDA tensors (device seam)")
+    lib = _lib.load()
+    cap = max(int(max_rounds), 1)
+    trace = np.zeros(cap, dtype=np.int64)
+    done = ctypes.c_int(0)
+    info = np.zeros(_lib.LSF_EXTEND_INFO_LEN, dtype=np.int64)
+    tail = (nx, ny, nz, float(dx), 0.0 if band is None else float(band), int(max_rounds), ctypes.byref(done), trace.ctypes.data, cap,
+            info.ctypes.data)
+    if _is_torch(q):
+        import torch
+
+        p = _dev_ptr(q, torch.float64, nx, ny, nz, "q")
+        f = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask") if mask is not None else None
+        if phi.device != q.device or (mask is not None and mask.device != q.device):
+            raise ValueError("q, phi and mask must live on one device")
+        st = _stream_and_device(q)
+        rc = lib.lsf_extend_field_device(p, f, m, *tail, st)
+    else:
+        p = _host_ptr(q, np.float64, nx, ny, nz, "q")
+        f = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
+        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask") if mask is not None else None
+        rc = lib.lsf_extend_field(p, f, m, *tail)
+    _lib.check(rc)
+    n = done.value
+    changed = [int(v) for v in trace[:n]]
+    return ExtendReport(n, changed, int(info[0]), int(info[1]), int(info[2]), bool(n and changed[-1] == 0))
 
 
 class AdvectReport(NamedTuple):
