@@ -389,7 +389,8 @@ int lsf_extend_field_device(double *d_q, const double *d_phi, const int32_t *d_m
  * Workspace beyond the caller's fields: two fields for LSF_ADVECT_RK3 (stage 3 writes the caller's field in place: it reads the old
  * phi at its own point only), one for LSF_ADVECT_EULER; the host seam adds one field per input given.  The result always ends in
  * the caller's field.  Work: one launch per stage over the interior + the boundary condition, one small launch per step for the
- * trace.  Out of scope here: a band or mask variant, fp32, multi-GPU, a CFL-chosen dt.
+ * trace.  The same operator on the cells of a mask: lsf_advect_field_band below.  Out of scope: fp32,
+ * multi-GPU, a CFL-chosen dt.
  * Not timed on hardware yet: no speed is claimed (the measurement is profiles/micro/advect_field_time.py). */
 #define LSF_ADVECT_RK3 0 /* scheme */
 #define LSF_ADVECT_EULER 1
@@ -399,6 +400,71 @@ int lsf_advect_field(double *phi, const double *u, const double *v, const double
 int lsf_advect_field_device(double *d_phi, const double *d_u, const double *d_v, const double *d_w, const double *d_speed,
                             int nx, int ny, int nz, double dx, double dt, int steps, int scheme, int mode, int *steps_done,
                             double *cfl, double *change_trace, int trace_cap, void *stream);
+
+/* ---- level-set transport on the cells of a caller's mask only: lsf_advect_field on a list ----------
+ * No reference counterpart.  In a time loop "advect, repair the distance on the tube (lsf_reinit_band), rebuild the tube
+ * (lsf_narrowband)" lsf_advect_field pays (n+1)^3 per stage; this call applies the same operator to the cells of a mask and
+ * reports when the mask was too narrow.  steps_done, cfl, change_trace, info and margin may be NULL.
+ *   LIST     the rule of lsf_reinit_band: the interior points (1..n-1 on each axis) with mask == 1 on entry, fixed for the whole
+ *            call.  Any other mask value means "not in the list"; a 1 on a wall point is ignored.  The mask is read once and
+ *            never written.
+ *   operator D-, D+, T, N, R and t = phi - dt*R are exactly those of lsf_advect_field: STRICT and FAST, the joint WENO rule (cells
+ *            4..n-5 on all three axes, first-order differences on all three otherwise), no y quirk.  All stencil values are taken
+ *            from the stage's input field, whether the stencil point is in the list or not.
+ *   stages   S(a) = t computed from the field a:
+ *              LSF_ADVECT_EULER  list cells of phi <- S(phi)
+ *              LSF_ADVECT_RK3    a = phi with its list cells replaced by S(phi);
+ *                                b = phi with its list cells replaced by 0.75*phi + 0.25*S(a);
+ *                                list cells of phi <- (1./3.)*phi + (2./3.)*S(b)
+ *            Points outside LIST are NEVER written, wall points included: the extrapolation boundary condition is NOT applied, as
+ *            in lsf_reinit_band.
+ *   inputs   u, v, w, speed have phi's layout and are given as in lsf_advect_field (u, v, w together or all NULL, speed optional,
+ *            at least one group).  They are read AT LIST CELLS ONLY: whatever they hold elsewhere is ignored and a NaN there is
+ *            legal -- what lsf_extend_field leaves on unreached points.  Never written.
+ *   cfl      (dt * max over LIST cells of (|u| + |v| + |w| + |speed|)) / dx, added left to right, absent fields left out.
+ *            Reported, never judged.
+ *   trace    change_trace[s], s < trace_cap: the largest |new - old| over the list cells of step s, NaN if any of them is NaN; the
+ *            bit-pattern maximum of lsf_advect_field.  A NaN ends the call with LSF_ERR_NAN after that step; steps_done counts
+ *            it and phi holds the state after it.
+ *   EDGE     a list cell is an edge cell when at least one of its six axis neighbours is not in LIST (a wall point never is).
+ *   info     [0] list cells; [1] edge cells; [2] edge cells whose (phi < 0) on return differs from (phi < 0) on entry: the surface
+ *            reached the edge of the list and the result next to it is not to be trusted.
+ *   margin   the smallest |phi| over the edge cells on return (the minimum of bit patterns: no order in it).  The caller compares
+ *            it with a few dx before the next call and rebuilds the mask (lsf_narrowband) when it shrinks.
+ *            info and margin are written on LSF_OK only; on LSF_OK no list cell is NaN, so both are well defined.
+ *   steps=0  LSF_OK, phi untouched; cfl, info and margin are still reported: info[2] = 0, margin that of the field as it came.
+ *   empty    LIST empty: LSF_OK, steps_done = 0, nothing written, cfl = 0, info = {0,0,0}, margin = +inf.
+ *   mode     LSF_ORDER_JACOBI | LSF_ARITH_STRICT or | LSF_ARITH_FAST.  LSF_ORDER_GS is LSF_ERR_INVALID.
+ *   result   with LSF_ARITH_STRICT field, trace, cfl, info and margin are those of the serial statement tests/advect_band_ref.py
+ *            bit for bit, on both seams, on any stream, from run to run.  One call of n steps equals n calls of one step for phi,
+ *            trace and cfl; info[2] is relative to each call's own entry.
+ *   errors   those of lsf_advect_field; a NULL mask; a non-finite u, v, w or speed AT A LIST CELL, with the count in
+ *            lsf_last_error().  All detected before phi is written.  No device: LSF_ERR_NO_DEVICE.
+ *   seams    phi and the mask are treated as lsf_reinit_band treats them under lsf_mirror; u, v, w, speed as lsf_advect_field
+ *            treats them.  lsf_advect_field_band_device returns after the stream is synchronised.
+ * Guidance: one stage carries information three cells along an axis.  A list cell farther than 9 cells per RK3 step (3 per Euler
+ * step) from every non-list point -- city-block distance, walls count as non-list -- holds exactly the value lsf_advect_field
+ * would give it; cells nearer than that read frozen neighbours.  Make the mask WIDER than the band whose values are trusted and
+ * keep steps * cfl well below the width.  Serial statement, a sphere translated at CFL 0.49 on 49^3 points (the translate case of
+ * tests/advect_ref.py), largest difference from the full-grid run over the cells with |exact| < 2 dx: with the mask
+ * |phi| < 8.1 dx 0 after 1 step, 1.5e-7 (2.3e-6 dx) after 4 and 5.6e-6 (8.9e-5 dx) after 8 (margin 6.9, 6.0 and 4.7 dx); with
+ * |phi| < 4.1 dx 1.6e-5 (2.6e-4 dx) after 1 step, 2.1e-4 (3.4e-3 dx) after 4 and 0.16 (2.6 dx) after 8, when the surface has left
+ * the list (margin 2.9, 1.9 and 0.65 dx; no edge cell has changed sign yet: watch the margin, not only info[2]).
+ * Work: beyond the list build and one copy of the field per workspace field (two for RK3, one for Euler), nothing is proportional
+ * to the grid; a stage visits the list cells only.  Measured on one MI355X (profiles/advect_band_time.txt, made by
+ * profiles/micro/advect_band_time.py: a sphere, the mask |phi| < 8.1 dx, RK3, STRICT, ms per step against lsf_advect_field on the
+ * same field): 0.08 against 1.47 at 256^3 (2.2 % of the grid in the list) and 0.24 against 12.1 at 512^3 (1.1 %) inside a call of
+ * 20 steps; a call of ONE step, which pays the list build and the copies each time, 0.49 against 1.59 and 1.59 against 13.0.
+ * No automatic rebuilding of the list, no dispatch to lsf_advect_field. */
+#define LSF_ADVECT_BAND_INFO_LEN 3
+int lsf_advect_field_band(double *phi, const int32_t *mask, const double *u, const double *v, const double *w,
+                          const double *speed, int nx, int ny, int nz, double dx, double dt, int steps, int scheme, int mode,
+                          int *steps_done, double *cfl, double *change_trace, int trace_cap,
+                          int64_t info[LSF_ADVECT_BAND_INFO_LEN], double *margin);
+int lsf_advect_field_band_device(double *d_phi, const int32_t *d_mask, const double *d_u, const double *d_v, const double *d_w,
+                                 const double *d_speed, int nx, int ny, int nz, double dx, double dt, int steps, int scheme,
+                                 int mode, int *steps_done, double *cfl, double *change_trace, int trace_cap,
+                                 int64_t info[LSF_ADVECT_BAND_INFO_LEN], double *margin, void *stream);
 
 /* ---- iso-surface extraction: the zero (or iso) level of a field as an indexed triangle mesh (marching tetrahedra) ----------
  * No reference counterpart.  What gives the moved geometry back after lsf_advect_field: the level set phi = iso as nodes

@@ -28,6 +28,7 @@
 #include "lsf_distance_fill.hpp"
 #include "lsf_extend_field.hpp"
 #include "lsf_advect_field.hpp"
+#include "lsf_advect_band.hpp"
 #include "lsf_extract_surface.hpp"
 
 using namespace lsf;
@@ -731,6 +732,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_extend_field.hpp"
 
 #include "lsf_host_advect_field.hpp"
+
+#include "lsf_host_advect_band.hpp"
 
 #include "lsf_host_extract_surface.hpp"
 
@@ -1516,6 +1519,60 @@ int lsf_advect_field(double* phi, const double* u, const double* v, const double
         if (rc2) return rc2;
         g_err = keep;
     } else
+        twin_drop(c.twin_phi);
+    return rc;
+}
+
+int lsf_advect_field_band_device(double* d_phi, const int32_t* d_mask, const double* d_u, const double* d_v, const double* d_w,
+                                 const double* d_speed, int nx, int ny, int nz, double dx, double dt, int steps, int scheme, int mode,
+                                 int* steps_done, double* cfl, double* change_trace, int trace_cap, int64_t info[LSF_ADVECT_BAND_INFO_LEN],
+                                 double* margin, void* stream)
+{
+    Trace trace_("lsf_advect_field_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    return advect_band_core(d_phi, d_mask, d_u, d_v, d_w, d_speed, nx, ny, nz, dx, dt, steps, scheme, mode, steps_done, cfl, change_trace,
+                            trace_cap, info, margin, (hipStream_t)stream);
+}
+
+int lsf_advect_field_band(double* phi, const int32_t* mask, const double* u, const double* v, const double* w, const double* speed, int nx,
+                          int ny, int nz, double dx, double dt, int steps, int scheme, int mode, int* steps_done, double* cfl,
+                          double* change_trace, int trace_cap, int64_t info[LSF_ADVECT_BAND_INFO_LEN], double* margin)
+{
+    Trace trace_("lsf_advect_field_band");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = advect_field_args_ok(phi, u, v, w, speed, nx, ny, nz, dx, dt, steps, scheme, mode))) return rc;
+    if (!mask) return fail(LSF_ERR_INVALID, "lsf_advect_field_band: mask is NULL");
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
+    // u, v, w, speed travel as in lsf_advect_field: each into a slot of its own, from a current device twin under LSF_MIRROR_TRUST / LAZY,
+    // from the host otherwise; staged before phi's twin is touched
+    const double* h_in[4] = {u, v, w, speed};
+    const Slot s_in[4] = {S_AF_U, S_AF_V, S_AF_W, S_AF_F};
+    const double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int q = 0; q < 4; ++q) {
+        if (!h_in[q]) continue;
+        if ((rc = ws(c.slot[s_in[q]], bytes))) return rc;
+        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, h_in[q], bytes) : nullptr;
+        HIPCHK(hipMemcpy(c.slot[s_in[q]].p, twin ? twin : (const void*)h_in[q], bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        d_in[q] = (const double*)c.slot[s_in[q]].p;
+    }
+    // phi and the mask travel as in lsf_reinit_band: the mask through the twin of phiNB when it IS that array, through the twin of phiSB
+    // otherwise; never copied back
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc;
+    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+    const Slot sm = is_nb ? S_HNB : S_HSB;
+    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+    rc = advect_band_core((double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, steps,
+                          scheme, mode, steps_done, cfl, change_trace, trace_cap, info, margin, nullptr);
+    if (rc == LSF_OK || rc == LSF_ERR_NAN) {
+        const std::string keep = g_err;
+        const int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
+        if (rc2) return rc2;
+        g_err = keep;
+    } else if (rc != LSF_ERR_INVALID) // (an invalid call is found before the twin is written: it stays what it was)
         twin_drop(c.twin_phi);
     return rc;
 }

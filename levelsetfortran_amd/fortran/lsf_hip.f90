@@ -23,6 +23,8 @@
 !                                                        constant along the normals of phi (include/lsf.h: lsf_extend_field)
 !   advectField(phi,u,v,w,nx,ny,nz,dx,dt,steps)          no reference counterpart: transport of phi by the velocity field
 !                                                        (u,v,w), WENO5 / TVD-RK3 (include/lsf.h: lsf_advect_field)
+!   advectFieldBand(phi,mask,u,v,w,nx,ny,nz,dx,dt,steps) no reference counterpart: advectField on the cells with mask == 1
+!                                                        only (include/lsf.h: lsf_advect_field_band)
 !   extractSurface(phi,nx,ny,nz,dx,xLo,iso,surfX,nSurfNode,surfElem,nSurfElem)
 !                                                        no reference counterpart: the level set phi = iso as a triangle mesh,
 !                                                        marching tetrahedra (include/lsf.h: lsf_extract_surface)
@@ -89,6 +91,7 @@ PUBLIC :: meshDistance
 PUBLIC :: distanceFill
 PUBLIC :: extendField
 PUBLIC :: advectField
+PUBLIC :: advectFieldBand
 PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
@@ -230,6 +233,24 @@ INTERFACE
       REAL(c_double), INTENT(OUT) :: change_trace(*)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_advect_field
+   ! int lsf_advect_field_band(double*,const int32_t*,const double*,const double*,const double*,const double*,int,int,int,double,double,
+   !                           int,int,int,int*,double*,double*,int,int64_t[3],double*)
+   FUNCTION lsf_advect_field_band(phi,mask,u,v,w,speed,nx,ny,nz,dx,dt,steps,scheme,mode,steps_done,cfl,change_trace,trace_cap, &
+                                  info,margin) BIND(C,NAME='lsf_advect_field_band') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(INOUT) :: phi(*)
+      INTEGER(c_int), INTENT(IN) :: mask(*)
+      REAL(c_double), INTENT(IN) :: u(*),v(*),w(*)
+      TYPE(c_ptr), VALUE :: speed            ! NULL: no motion along the normal
+      INTEGER(c_int), VALUE :: nx,ny,nz,steps,scheme,mode,trace_cap
+      REAL(c_double), VALUE :: dx,dt
+      INTEGER(c_int), INTENT(OUT) :: steps_done
+      REAL(c_double), INTENT(OUT) :: cfl
+      REAL(c_double), INTENT(OUT) :: change_trace(*)
+      INTEGER(c_int64_t), INTENT(OUT) :: info(3)
+      REAL(c_double), INTENT(OUT) :: margin
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_advect_field_band
    FUNCTION lsf_advect_nodes(phi,phiSB,nx,ny,nz,dx,xLo,surfXX,nSurfNode,iters) &
             BIND(C,NAME='lsf_advect_nodes') RESULT(rc)
       IMPORT :: c_int, c_double
@@ -710,6 +731,48 @@ IF (rc == LSF_ERR_NAN) STOP
 DEALLOCATE(trace)
 
 END SUBROUTINE advectField
+
+!*************************************************************************************!
+! advectField on the cells of a mask only (include/lsf.h: lsf_advect_field_band; no
+! reference counterpart): the interior points with mask == 1 (e.g. phiSB of narrowBand)
+! take `steps` steps of size dt, WENO5 / TVD-RK3 in the reference's own arithmetic
+! (LSF_ARITH_STRICT); every other point keeps its value and no boundary condition is
+! applied.  u, v, w are read at those cells only.  Prints the steps, the CFL number over
+! the list, the last change, the list and edge cells, the edge cells whose sign changed
+! (> 0: the surface reached the edge of the mask -- rebuild it) and the smallest |phi|
+! over the edge cells in units of dx.  A NaN stops the run like advectField.
+!*************************************************************************************!
+SUBROUTINE advectFieldBand(phi,mask,u,v,w,nx,ny,nz,dx,dt,steps)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,steps
+REAL,INTENT(IN) :: dx,dt
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: mask
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: u,v,w
+INTEGER(c_int), PARAMETER :: LSF_ADVECT_RK3 = 0
+REAL,ALLOCATABLE :: trace(:)
+REAL :: cfl,margin
+INTEGER(c_int64_t) :: info(3)
+INTEGER(c_int) :: rc,done,mode
+
+ALLOCATE(trace(MAX(steps,1)))
+trace = 0.
+cfl = 0.
+margin = 0.
+info = 0
+done = 0
+CALL lsf_set_mirror()
+mode = IOR(LSF_ARITH_STRICT,LSF_ORDER_JACOBI)
+rc = lsf_advect_field_band(phi,mask,u,v,w,c_null_ptr,nx,ny,nz,dx,dt,steps,LSF_ADVECT_RK3,mode,done,cfl,trace,MAX(steps,1), &
+                           info,margin)
+IF (rc /= LSF_OK .AND. rc /= LSF_ERR_NAN) CALL lsf_fail('lsf_advect_field_band',rc)
+PRINT*, " Level-set transport on the band: ",done," steps, CFL ",cfl,", last change ",trace(MAX(done,1))
+IF (rc == LSF_OK) PRINT*, "   list cells ",info(1),", edge cells ",info(2),", edge sign flips ",info(3),", margin/dx ",margin/dx
+PRINT*
+IF (rc == LSF_ERR_NAN) STOP
+DEALLOCATE(trace)
+
+END SUBROUTINE advectFieldBand
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

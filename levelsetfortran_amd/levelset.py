@@ -20,6 +20,10 @@ and the first-order distance on the rest of the grid from a frozen band (fast sw
 
   distanceFill(phi, nx, ny, nz, dx, band=... | mask=...)        include/lsf.h: lsf_distance_fill
 
+and the transport of lsf_advect_field on the cells of a mask only (no reference counterpart):
+
+  advectFieldBand(phi, mask, nx, ny, nz, dx, dt, steps, ...)    include/lsf.h: lsf_advect_field_band
+
 and a quantity known on that band carried to the rest of the grid constant along the normals (no reference counterpart):
 
   extendField(q, phi, nx, ny, nz, dx, band=... | mask=...)      include/lsf.h: lsf_extend_field
@@ -46,7 +50,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "advectField", "AdvectReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -521,6 +525,84 @@ def advectField(phi, nx: int, ny: int, nz: int, dx: float, dt: float, steps: int
         rc = lib.lsf_advect_field(p, *tail)
     n = done.value
     rep = AdvectReport(n, float(cfl.value), [float(x) for x in trace[:n]])
+    try:
+        _lib.check(rc)
+    except LsfNaNError as e:
+        e.report = rep  # the steps run, the NaN one included
+        raise
+    return rep
+
+
+class AdvectBandReport(NamedTuple):
+    """What lsf_advect_field_band reports (include/lsf.h): steps run, the CFL number of the inputs over the list cells, the largest
+    |new - old| over the list cells of each step, the list cells, the edge cells among them (a neighbour outside the list), the edge
+    cells whose sign changed during the call (> 0: the surface reached the edge of the list) and the smallest |phi| over the edge
+    cells on return.  cells, edge_cells, edge_flips and margin are None where the library did not report them (LsfNaNError)."""
+    steps: int
+    cfl: float
+    change: List[float]
+    cells: Optional[int]
+    edge_cells: Optional[int]
+    edge_flips: Optional[int]
+    margin: Optional[float]
+
+
+def advectFieldBand(phi, mask, nx: int, ny: int, nz: int, dx: float, dt: float, steps: int, *, velocity=None, speed=None,
+                    scheme: str = "rk3", arith: str = "strict") -> AdvectBandReport:
+    """advectField on the cells of `mask` only (include/lsf.h: lsf_advect_field_band); `phi` is updated in place.
+
+    mask: int32, phi's layout and kind (e.g. phiSB of narrowBand); the interior points where it is 1 take the steps of advectField,
+    every other point -- wall points included -- keeps its value and no boundary condition is applied.  velocity, speed, scheme and
+    arith as in advectField; the inputs are read at the list cells only (a NaN elsewhere is legal).  Make the mask wider than the band
+    whose values are trusted and keep steps * cfl well below its width: `edge_flips` > 0 says the surface reached the edge of the
+    list, and `margin` (compare it with a few dx) says when to rebuild the mask.  Raises LsfNaNError when a step produced a NaN (phi
+    holds that step; the exception carries the AdvectBandReport as `.report`).
+    """
+    if scheme not in ("rk3", "euler"):
+        raise ValueError("scheme must be 'rk3' or 'euler'")
+    if arith not in ("strict", "fast"):
+        raise ValueError("arith must be 'strict' or 'fast'")
+    if velocity is None and speed is None:
+        raise ValueError("give velocity=(u, v, w), speed=F, or both")
+    if velocity is not None:
+        if not isinstance(velocity, (tuple, list)) or len(velocity) != 3 or any(c is None for c in velocity):
+            raise ValueError("velocity must be a 3-tuple (u, v, w) of fields")
+    if mask is None:
+        raise ValueError("mask must be an int32 field of phi's shape")
+    dev = _is_torch(phi)
+    inputs = [(n, f) for n, f in zip("uvw", velocity or ())] + ([("speed", speed)] if speed is not None else [])
+    if any(_is_torch(f) != dev for _, f in inputs + [("mask", mask)]):
+        raise TypeError("phi, mask, velocity and speed must all be numpy arrays or all be CUDA tensors")
+    cap = max(int(steps), 1)
+    trace = np.zeros(cap, dtype=np.float64)
+    done = ctypes.c_int(0)
+    cfl = ctypes.c_double(0.0)
+    info = np.full(_lib.LSF_ADVECT_BAND_INFO_LEN, -1, dtype=np.int64)
+    margin = ctypes.c_double(float("nan"))
+    if dev:
+        import torch
+
+        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
+        if any(f.device != phi.device for _, f in inputs + [("mask", mask)]):
+            raise ValueError("phi, mask, velocity and speed must live on one device")
+        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+    else:
+        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
+        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+    p = ptr(phi, "phi")
+    q = {n: ptr(f, n) for n, f in inputs}
+    lib = _lib.load()
+    tail = (m, q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps),
+            {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}[scheme], mode_word("jacobi", arith), ctypes.byref(done),
+            ctypes.byref(cfl), trace.ctypes.data, cap, info.ctypes.data, ctypes.byref(margin))
+    if dev:
+        rc = lib.lsf_advect_field_band_device(p, *tail, _stream_and_device(phi))
+    else:
+        rc = lib.lsf_advect_field_band(p, *tail)
+    n = done.value
+    told = rc == _lib.LSF_OK  # info and margin are written on LSF_OK only
+    rep = AdvectBandReport(n, float(cfl.value), [float(x) for x in trace[:n]], *((int(v) for v in info) if told else (None, None, None)),
+                           float(margin.value) if told else None)
     try:
         _lib.check(rc)
     except LsfNaNError as e:
