@@ -466,6 +466,81 @@ int lsf_advect_field_band_device(double *d_phi, const int32_t *d_mask, const dou
                                  int mode, int *steps_done, double *cfl, double *change_trace, int trace_cap,
                                  int64_t info[LSF_ADVECT_BAND_INFO_LEN], double *margin, void *stream);
 
+/* ---- the band time loop: transport, repair of the distance and the cell list moving with the surface ----------
+ * No reference counterpart.  lsf_advect_field_band and lsf_reinit_band each build the list from the mask and copy the field on every
+ * call, and a list made from |phi| < w dx cannot follow the surface: points outside it are never written, so ahead of the surface
+ * they keep the distance of time 0.  This call keeps ONE list on the device for all its steps, runs the stages of the one and the
+ * sweeps of the other on it, watches the edge of the list and rebuilds the list when the surface comes near it (the local level
+ * set method of Peng, Merriman, Osher, Zhao and Kang, J. Comput. Phys. 155, 1999: dilate the trusted core, give entering cells a
+ * placeholder that the reinitialisation corrects).  steps_done, cfl, change_trace, info and margin may be NULL.
+ *   LIST     on entry the rule of lsf_reinit_band: the interior points (1..n-1 on each axis) with mask == 1.  From the first
+ *            rebuild on, LIST is the last rebuilt list.
+ *   step s   in this order:
+ *            1. one step of lsf_advect_field_band's stages on LIST: operator, schemes, STRICT and FAST unchanged; no boundary
+ *               condition, nothing outside LIST is written.  change_trace[s] as there.  A NaN ends the call with LSF_ERR_NAN after
+ *               this transport: the sweeps of the step are not run, steps_done counts the step, info and margin are not written.
+ *            2. reinit_sweeps (>= 0) sweeps of lsf_reinit_band's sweep on LIST with pseudo-time step h; phiS is the field after 1
+ *               at the list cells.  No RMS, no early stop.
+ *            3. the CHECK, if (s+1) % check_every == 0 or s == steps-1.
+ *   CHECK    An OPEN EDGE cell is a list cell with at least one of its six axis neighbours an INTERIOR point outside LIST.  A wall
+ *            neighbour does not open an edge: the list cannot grow there (without this rule a surface near a wall rebuilds in every
+ *            step).  flips = the number of open-edge cells whose (phi < 0) differs from that at the last build of the list (entry,
+ *            or the last rebuild); margin = the smallest |phi| over the open-edge cells, the minimum of bit patterns, +inf when
+ *            there are none.  flips > 0: the call ends with LSF_OK, steps_done = s+1 (< steps possible), info[2] = flips, no
+ *            rebuild -- the loud ending: the surface reached the edge between two checks.  Else, margin < core*dx: REBUILD.
+ *   REBUILD  CORE = the list cells with |phi| < core*dx.  NEW = the interior points within Chebyshev distance `ring` of a CORE
+ *            cell.  Entering cells (NEW \ LIST) take phi < 0 ? -far : +far with far = (core + (double)ring) * dx, computed once on
+ *            the host (-0.0 and every positive value give +far); leaving cells keep the value they hold.  LIST becomes NEW and the
+ *            sign reference becomes the field as it is now.  A rebuild after the last step is done like any other, so with no flips
+ *            one call of n steps equals two calls of n/2 for phi, mask and trace whenever check_every divides n/2.
+ *   inputs   u, v, w, speed are given as in lsf_advect_field.  The list moves, so they must be finite at ALL points: checked once
+ *            per call, before anything is written, by the pass lsf_advect_field uses, and cfl is that call's, over all points.
+ *            They are frozen for the call: a caller with a time-dependent speed calls once per few steps.
+ *   outputs  on LSF_OK and LSF_ERR_NAN phi is the state after the last step run and mask is 1 on the cells of the current LIST and 0
+ *            on every other point (the mask is in/out).  On LSF_ERR_INVALID both are untouched.
+ *   info     on LSF_OK only: [0] list cells, [1] open-edge cells, [2] flips of the last check, [3] rebuilds, [4] entering cells
+ *            summed over the rebuilds, [5] list cells adjacent to a wall with |phi| < core*dx ([0], [1] and [5] of the list on
+ *            return).  [5] > 0: the surface is near a wall, where this call applies no boundary condition and the result next to it
+ *            is the caller's risk.  margin (LSF_OK only) is taken over the open-edge cells of the list on return.
+ *   errors   LSF_ERR_INVALID, all detected before anything is written: those of lsf_advect_field_band; core not finite or <= 0; ring
+ *            outside 1..8; reinit_sweeps < 0; h not finite or <= 0 when reinit_sweeps > 0; check_every < 1; non-finite inputs, with
+ *            their count in lsf_last_error().  No device: LSF_ERR_NO_DEVICE.
+ *   empty    LIST empty on entry: LSF_OK, steps_done = 0, phi untouched, the mask all 0, cfl = 0, info zero, margin = +inf.
+ *   steps=0  LSF_OK, phi untouched, the mask normalised to 0/1, cfl reported, one check without rebuild for info and margin.
+ *   mode     LSF_ORDER_JACOBI | LSF_ARITH_STRICT or | LSF_ARITH_FAST.
+ *   result   with LSF_ARITH_STRICT phi, mask, trace, cfl, info and margin are those of the serial statement
+ *            tests/evolve_band_ref.py bit for bit, on both seams, on any stream, from run to run: all reductions are bit-pattern
+ *            minima / maxima or integer counts, so the order of the list reaches no result.
+ *   seams    phi and mask are in/out under lsf_mirror, as phi is for lsf_reinit_band (the mask through the twin of phiNB when it
+ *            IS that array, of phiSB otherwise); u, v, w, speed as lsf_advect_field treats them.  lsf_evolve_band_device returns
+ *            after the stream is synchronised.
+ * Guidance: the field must be a distance for |phi| < far; a clamped one (what lsf_mesh_distance(width) gives) is fine.  Keep
+ * check_every * cfl well below core: the surface may move that many cells between two looks at the edge.  Use ring >= 3, so a core
+ * cell's WENO stencil stays in the list.  The placeholders are corrected by the sweeps and by nothing else.  Serial statement, the
+ * distance to a sphere of radius 0.5 clamped to +-6 dx on 49^3 points, mask |phi| < 6 dx, u = (1,0,0) at CFL 0.5, 36 steps (the
+ * surface moves 18 cells, three times the list's half-width), core = 3, ring = 3, h = 0.5 dx: with 2 sweeps per step 6 rebuilds,
+ * no flips, every cell with |exact| < 2 dx in the final list and the largest error there 0.029 dx (lsf_advect_field alone, every
+ * cell and no reinitialisation: 0.014 dx); with reinit_sweeps = 0 the same run ends 3.3 dx off.
+ * Work: between rebuilds nothing is proportional to the grid: the stage buffers are copied from phi once per call, a step enqueues
+ * its stages and sweeps on the resident list, and the host reads one 64-byte record per check.  A rebuild clears and collects a
+ * 4-byte scratch mask (the list build of lsf_reinit_band) and makes no pass over a field.  Workspace: the stage buffers of
+ * lsf_advect_field_band and one 4-byte mask.  Measured on one MI355X (profiles/evolve_band_time.txt, made by
+ * profiles/micro/evolve_band_time.py: the sphere and mask of lsf_advect_field_band's measurement, RK3, STRICT, 2 sweeps, 20 steps,
+ * ms per step against the same steps done with one lsf_advect_field_band step and one lsf_reinit_band(iter = 1) per step): 0.15
+ * against 0.78 at 256^3 and 0.40 against 2.51 at 512^3, no rebuild in those runs; with core = 6, where one rebuild falls inside
+ * the 20 steps and the list grows by a third, 0.16 and 0.46.  Out of scope: a boundary condition at the walls or a surface that
+ * leaves through one, inputs that are NaN off the list, a CFL-chosen dt, a time-dependent velocity inside one call, fp32,
+ * multi-GPU, a rebuild without the pass over the mask. */
+#define LSF_EVOLVE_INFO_LEN 6
+int lsf_evolve_band(double *phi, int32_t *mask, const double *u, const double *v, const double *w, const double *speed, int nx,
+                    int ny, int nz, double dx, double dt, int steps, int scheme, int mode, double core, int ring,
+                    int reinit_sweeps, double h, int check_every, int *steps_done, double *cfl, double *change_trace,
+                    int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN], double *margin);
+int lsf_evolve_band_device(double *d_phi, int32_t *d_mask, const double *d_u, const double *d_v, const double *d_w,
+                           const double *d_speed, int nx, int ny, int nz, double dx, double dt, int steps, int scheme, int mode,
+                           double core, int ring, int reinit_sweeps, double h, int check_every, int *steps_done, double *cfl,
+                           double *change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN], double *margin, void *stream);
+
 /* ---- iso-surface extraction: the zero (or iso) level of a field as an indexed triangle mesh (marching tetrahedra) ----------
  * No reference counterpart.  What gives the moved geometry back after lsf_advect_field: the level set phi = iso as nodes
  * surfX(nSurfNode,3) and triangles surfElem(nSurfElem,3), 1-based INTEGER*4, both Fortran-ordered -- the format lsf_phi0,

@@ -29,6 +29,7 @@
 #include "lsf_extend_field.hpp"
 #include "lsf_advect_field.hpp"
 #include "lsf_advect_band.hpp"
+#include "lsf_evolve_band.hpp"
 #include "lsf_extract_surface.hpp"
 
 using namespace lsf;
@@ -186,7 +187,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -734,6 +735,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_advect_field.hpp"
 
 #include "lsf_host_advect_band.hpp"
+
+#include "lsf_host_evolve_band.hpp"
 
 #include "lsf_host_extract_surface.hpp"
 
@@ -1574,6 +1577,61 @@ int lsf_advect_field_band(double* phi, const int32_t* mask, const double* u, con
         g_err = keep;
     } else if (rc != LSF_ERR_INVALID) // (an invalid call is found before the twin is written: it stays what it was)
         twin_drop(c.twin_phi);
+    return rc;
+}
+
+int lsf_evolve_band_device(double* d_phi, int32_t* d_mask, const double* d_u, const double* d_v, const double* d_w, const double* d_speed, int nx,
+                           int ny, int nz, double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h,
+                           int check_every, int* steps_done, double* cfl, double* change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN],
+                           double* margin, void* stream)
+{
+    Trace trace_("lsf_evolve_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    return evolve_band_core(d_phi, d_mask, d_u, d_v, d_w, d_speed, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h, check_every,
+                            steps_done, cfl, change_trace, trace_cap, info, margin, (hipStream_t)stream);
+}
+
+int lsf_evolve_band(double* phi, int32_t* mask, const double* u, const double* v, const double* w, const double* speed, int nx, int ny, int nz,
+                    double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h, int check_every,
+                    int* steps_done, double* cfl, double* change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN], double* margin)
+{
+    Trace trace_("lsf_evolve_band");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = evolve_band_args_ok(phi, mask, u, v, w, speed, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h, check_every)))
+        return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
+    // u, v, w, speed travel as in lsf_advect_field: each into a slot of its own, from a current device twin under LSF_MIRROR_TRUST / LAZY,
+    // from the host otherwise; staged before phi's twin is touched
+    const double* h_in[4] = {u, v, w, speed};
+    const Slot s_in[4] = {S_AF_U, S_AF_V, S_AF_W, S_AF_F};
+    const double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int q = 0; q < 4; ++q) {
+        if (!h_in[q]) continue;
+        if ((rc = ws(c.slot[s_in[q]], bytes))) return rc;
+        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, h_in[q], bytes) : nullptr;
+        HIPCHK(hipMemcpy(c.slot[s_in[q]].p, twin ? twin : (const void*)h_in[q], bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        d_in[q] = (const double*)c.slot[s_in[q]].p;
+    }
+    // phi and the mask are both in/out and travel as phi does in lsf_reinit_band: the mask through the twin of phiNB when it IS that
+    // array, through the twin of phiSB otherwise
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc;
+    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+    const Slot sm = is_nb ? S_HNB : S_HSB;
+    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+    rc = evolve_band_core((double*)c.slot[S_HPHI].p, (int32_t*)c.slot[sm].p, d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, steps, scheme,
+                          mode, core, ring, reinit_sweeps, h, check_every, steps_done, cfl, change_trace, trace_cap, info, margin, nullptr);
+    if (rc == LSF_OK || rc == LSF_ERR_NAN) {
+        const std::string keep = g_err;
+        int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
+        if (!rc2) rc2 = twin_out(c, tm, sm, mask, n * sizeof(int32_t));
+        if (rc2) return rc2;
+        g_err = keep;
+    } else if (rc != LSF_ERR_INVALID) // (an invalid call is found before the twins are written: they stay what they were)
+        twin_drop(c.twin_phi), twin_drop(tm);
     return rc;
 }
 

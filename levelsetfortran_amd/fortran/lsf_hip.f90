@@ -25,6 +25,9 @@
 !                                                        (u,v,w), WENO5 / TVD-RK3 (include/lsf.h: lsf_advect_field)
 !   advectFieldBand(phi,mask,u,v,w,nx,ny,nz,dx,dt,steps) no reference counterpart: advectField on the cells with mask == 1
 !                                                        only (include/lsf.h: lsf_advect_field_band)
+!   evolveBand(phi,mask,u,v,w,nx,ny,nz,dx,dt,steps)      no reference counterpart: the band time loop -- transport, two sweeps of
+!                                                        the reinitialisation and the list following the surface; phi and mask
+!                                                        are both updated (include/lsf.h: lsf_evolve_band)
 !   extractSurface(phi,nx,ny,nz,dx,xLo,iso,surfX,nSurfNode,surfElem,nSurfElem)
 !                                                        no reference counterpart: the level set phi = iso as a triangle mesh,
 !                                                        marching tetrahedra (include/lsf.h: lsf_extract_surface)
@@ -92,6 +95,7 @@ PUBLIC :: distanceFill
 PUBLIC :: extendField
 PUBLIC :: advectField
 PUBLIC :: advectFieldBand
+PUBLIC :: evolveBand
 PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
@@ -251,6 +255,24 @@ INTERFACE
       REAL(c_double), INTENT(OUT) :: margin
       INTEGER(c_int) :: rc
    END FUNCTION lsf_advect_field_band
+   ! int lsf_evolve_band(double*,int32_t*,const double*,const double*,const double*,const double*,int,int,int,double,double,int,int,int,
+   !                     double,int,int,double,int,int*,double*,double*,int,int64_t[6],double*)
+   FUNCTION lsf_evolve_band(phi,mask,u,v,w,speed,nx,ny,nz,dx,dt,steps,scheme,mode,core,ring,reinit_sweeps,h,check_every, &
+                            steps_done,cfl,change_trace,trace_cap,info,margin) BIND(C,NAME='lsf_evolve_band') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(INOUT) :: phi(*)
+      INTEGER(c_int), INTENT(INOUT) :: mask(*)
+      REAL(c_double), INTENT(IN) :: u(*),v(*),w(*)
+      TYPE(c_ptr), VALUE :: speed            ! NULL: no motion along the normal
+      INTEGER(c_int), VALUE :: nx,ny,nz,steps,scheme,mode,ring,reinit_sweeps,check_every,trace_cap
+      REAL(c_double), VALUE :: dx,dt,core,h
+      INTEGER(c_int), INTENT(OUT) :: steps_done
+      REAL(c_double), INTENT(OUT) :: cfl
+      REAL(c_double), INTENT(OUT) :: change_trace(*)
+      INTEGER(c_int64_t), INTENT(OUT) :: info(6)
+      REAL(c_double), INTENT(OUT) :: margin
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_evolve_band
    FUNCTION lsf_advect_nodes(phi,phiSB,nx,ny,nz,dx,xLo,surfXX,nSurfNode,iters) &
             BIND(C,NAME='lsf_advect_nodes') RESULT(rc)
       IMPORT :: c_int, c_double
@@ -773,6 +795,51 @@ IF (rc == LSF_ERR_NAN) STOP
 DEALLOCATE(trace)
 
 END SUBROUTINE advectFieldBand
+
+!*************************************************************************************!
+! The band time loop (include/lsf.h: lsf_evolve_band; no reference counterpart): `steps`
+! steps of size dt, each the transport of advectFieldBand followed by two sweeps of the
+! reinitialisation (pseudo-time step 0.5 dx) on ONE list of cells that stays on the device
+! and is rebuilt when the surface comes within 3 dx of its open edge (core 3, ring 3, a
+! check after every step).  phi AND mask are updated: on return mask is 1 on the cells of
+! the current list and 0 elsewhere.  u, v, w must be finite at all points.  Prints the
+! steps, the CFL number, the last change, the list and open-edge cells, the sign flips of
+! the last check (> 0: the surface reached the edge and the run ended early), the
+! rebuilds, the cells that entered, the near-wall cells and the margin in units of dx.
+! A NaN stops the run like advectField.
+!*************************************************************************************!
+SUBROUTINE evolveBand(phi,mask,u,v,w,nx,ny,nz,dx,dt,steps)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,steps
+REAL,INTENT(IN) :: dx,dt
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: mask
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: u,v,w
+INTEGER(c_int), PARAMETER :: LSF_ADVECT_RK3 = 0
+REAL,ALLOCATABLE :: trace(:)
+REAL :: cfl,margin
+INTEGER(c_int64_t) :: info(6)
+INTEGER(c_int) :: rc,done,mode
+
+ALLOCATE(trace(MAX(steps,1)))
+trace = 0.
+cfl = 0.
+margin = 0.
+info = 0
+done = 0
+CALL lsf_set_mirror()
+mode = IOR(LSF_ARITH_STRICT,LSF_ORDER_JACOBI)
+rc = lsf_evolve_band(phi,mask,u,v,w,c_null_ptr,nx,ny,nz,dx,dt,steps,LSF_ADVECT_RK3,mode,3.0_c_double,3,2,0.5_c_double*dx,1, &
+                     done,cfl,trace,MAX(steps,1),info,margin)
+IF (rc /= LSF_OK .AND. rc /= LSF_ERR_NAN) CALL lsf_fail('lsf_evolve_band',rc)
+PRINT*, " Band time loop: ",done," of ",steps," steps, CFL ",cfl,", last change ",trace(MAX(done,1))
+IF (rc == LSF_OK) PRINT*, "   list cells ",info(1),", open-edge cells ",info(2),", sign flips ",info(3),", rebuilds ",info(4), &
+                          ", entered ",info(5),", near a wall ",info(6),", margin/dx ",margin/dx
+PRINT*
+IF (rc == LSF_ERR_NAN) STOP
+DEALLOCATE(trace)
+
+END SUBROUTINE evolveBand
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

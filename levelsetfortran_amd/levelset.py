@@ -23,6 +23,7 @@ and the first-order distance on the rest of the grid from a frozen band (fast sw
 and the transport of lsf_advect_field on the cells of a mask only (no reference counterpart):
 
   advectFieldBand(phi, mask, nx, ny, nz, dx, dt, steps, ...)    include/lsf.h: lsf_advect_field_band
+  evolveBand(phi, mask, nx, ny, nz, dx, dt, steps, ...)         include/lsf.h: lsf_evolve_band
 
 and a quantity known on that band carried to the rest of the grid constant along the normals (no reference counterpart):
 
@@ -50,7 +51,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -602,6 +603,105 @@ def advectFieldBand(phi, mask, nx: int, ny: int, nz: int, dx: float, dt: float, 
     n = done.value
     told = rc == _lib.LSF_OK  # info and margin are written on LSF_OK only
     rep = AdvectBandReport(n, float(cfl.value), [float(x) for x in trace[:n]], *((int(v) for v in info) if told else (None, None, None)),
+                           float(margin.value) if told else None)
+    try:
+        _lib.check(rc)
+    except LsfNaNError as e:
+        e.report = rep  # the steps run, the NaN one included
+        raise
+    return rep
+
+
+class EvolveBandReport(NamedTuple):
+    """What lsf_evolve_band reports (include/lsf.h): steps run, the CFL number of the inputs over all points, the largest |new - old|
+    over the list cells of each step's transport, then info[0..5] -- the list cells on return, the open-edge cells among them (an
+    interior neighbour outside the list), the open-edge cells whose sign had changed at the last check (> 0: the surface reached the
+    edge between two checks and the call ended there), the rebuilds, the cells that entered over all rebuilds, the wall-adjacent list
+    cells with |phi| < core dx -- and the smallest |phi| over the open-edge cells on return.  The last seven are None where the
+    library did not report them (LsfNaNError)."""
+    steps: int
+    cfl: float
+    change: List[float]
+    cells: Optional[int]
+    open_cells: Optional[int]
+    flips: Optional[int]
+    rebuilds: Optional[int]
+    entered: Optional[int]
+    near_wall: Optional[int]
+    margin: Optional[float]
+
+
+def evolveBand(phi, mask, nx: int, ny: int, nz: int, dx: float, dt: float, steps: int, *, velocity=None, speed=None, scheme: str = "rk3",
+               arith: str = "strict", core: float = 3.0, ring: int = 3, reinit_sweeps: int = 2, h: Optional[float] = None,
+               check_every: int = 1) -> EvolveBandReport:
+    """The band time loop (include/lsf.h: lsf_evolve_band): per step the transport of advectFieldBand, `reinit_sweeps` sweeps of
+    reinitBand and, every `check_every` steps, a look at the open edge of the list; `phi` AND `mask` are updated in place.
+
+    mask: int32, phi's layout and kind; on entry the interior points where it is 1 are the list, on return it is 1 on the cells of
+    the current list and 0 elsewhere.  When the smallest |phi| over the open-edge cells falls below core*dx the list is rebuilt: the
+    cells with |phi| < core*dx dilated by `ring` cells, entering cells set to -+(core + ring)*dx for the sweeps to correct (so keep
+    reinit_sweeps > 0, ring >= 3 and check_every * cfl well below core).  h: the pseudo-time step of the sweeps, 0.5*dx when None.
+    velocity, speed, scheme and arith as in advectField; the inputs must be finite at all points.  `flips` > 0 in the report says the
+    call ended early (`steps` < the steps asked for).  Raises LsfNaNError when a step produced a NaN (phi holds that step; the
+    exception carries the EvolveBandReport as `.report`).
+    """
+    if scheme not in ("rk3", "euler"):
+        raise ValueError("scheme must be 'rk3' or 'euler'")
+    if arith not in ("strict", "fast"):
+        raise ValueError("arith must be 'strict' or 'fast'")
+    if velocity is None and speed is None:
+        raise ValueError("give velocity=(u, v, w), speed=F, or both")
+    if velocity is not None:
+        if not isinstance(velocity, (tuple, list)) or len(velocity) != 3 or any(c is None for c in velocity):
+            raise ValueError("velocity must be a 3-tuple (u, v, w) of fields")
+    if mask is None:
+        raise ValueError("mask must be an int32 field of phi's shape")
+    if h is None:
+        h = 0.5 * float(dx)
+    if not (float(core) > 0.0 and np.isfinite(float(core))):
+        raise ValueError("core must be finite and > 0")
+    if int(ring) != ring or not 1 <= int(ring) <= 8:
+        raise ValueError("ring must be an integer in 1..8")
+    if int(reinit_sweeps) != reinit_sweeps or reinit_sweeps < 0:
+        raise ValueError("reinit_sweeps must be an integer >= 0")
+    if reinit_sweeps > 0 and not (float(h) > 0.0 and np.isfinite(float(h))):
+        raise ValueError("h must be finite and > 0")
+    if int(check_every) != check_every or check_every < 1:
+        raise ValueError("check_every must be an integer >= 1")
+    dev = _is_torch(phi)
+    inputs = [(n, f) for n, f in zip("uvw", velocity or ())] + ([("speed", speed)] if speed is not None else [])
+    if any(_is_torch(f) != dev for _, f in inputs + [("mask", mask)]):
+        raise TypeError("phi, mask, velocity and speed must all be numpy arrays or all be CUDA tensors")
+    cap = max(int(steps), 1)
+    trace = np.zeros(cap, dtype=np.float64)
+    done = ctypes.c_int(0)
+    cfl = ctypes.c_double(0.0)
+    info = np.full(_lib.LSF_EVOLVE_INFO_LEN, -1, dtype=np.int64)
+    margin = ctypes.c_double(float("nan"))
+    if dev:
+        import torch
+
+        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
+        if any(f.device != phi.device for _, f in inputs + [("mask", mask)]):
+            raise ValueError("phi, mask, velocity and speed must live on one device")
+        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+    else:
+        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
+        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+    p = ptr(phi, "phi")
+    q = {n: ptr(f, n) for n, f in inputs}
+    lib = _lib.load()
+    tail = (m, q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps),
+            {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}[scheme], mode_word("jacobi", arith), float(core), int(ring),
+            int(reinit_sweeps), float(h), int(check_every), ctypes.byref(done), ctypes.byref(cfl), trace.ctypes.data, cap, info.ctypes.data,
+            ctypes.byref(margin))
+    if dev:
+        rc = lib.lsf_evolve_band_device(p, *tail, _stream_and_device(phi))
+    else:
+        rc = lib.lsf_evolve_band(p, *tail)
+    n = done.value
+    told = rc == _lib.LSF_OK  # info and margin are written on LSF_OK only
+    rep = EvolveBandReport(n, float(cfl.value), [float(x) for x in trace[:n]], *((int(v) for v in info) if told else (None,) * 6),
                            float(margin.value) if told else None)
     try:
         _lib.check(rc)
