@@ -541,6 +541,76 @@ int lsf_evolve_band_device(double *d_phi, int32_t *d_mask, const double *d_u, co
                            double core, int ring, int reinit_sweeps, double h, int check_every, int *steps_done, double *cfl,
                            double *change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN], double *margin, void *stream);
 
+/* ---- mean and Gaussian curvature of the level sets on the cells of a caller's mask ----------
+ * The reference computed its "true curvature" once and commented it out (subs.f90:426-448; setSurfCurv interpolates a `curv`
+ * that nothing fills any more); the ingredients are its second-order secondDeriv (subs.f90:382-398).  This call gives the shape
+ * of the surface where a speed law F = a - b*kappa needs it: kappa = div(grad(phi)/|grad(phi)|) = k1 + k2, the Gaussian curvature
+ * k1 * k2 and |grad(phi)|, at the list cells only.  gauss, gmag, info and kappa_max may be NULL; kappa is required.
+ *   LIST     the rule of lsf_reinit_band: the interior points (1..n-1 on each axis) with mask == 1.  Any other mask value means
+ *            "not in the list"; a 1 on a wall point is ignored.  The mask is read once and never written.  Every stencil point
+ *            of an interior cell -- +-1 on each axis and the 12 edge diagonals -- lies inside the field: one rule for every list
+ *            cell, no WENO rule, no first-order cells.
+ *   outputs  phi and mask are inputs only.  Each output that is given is written AT LIST CELLS and nowhere else: what it holds at
+ *            every other point stays bit for bit, NaNs included -- a kappa written on the cells of a mask plugs straight into the
+ *            `speed` of lsf_advect_field_band on the same mask (which reads it at list cells only) and, on a thin frozen band, into
+ *            the q of lsf_extend_field.
+ *   values   evaluated exactly as written, left to right, without contraction; / and sqrt are the IEEE ones; c is the value at
+ *            the cell and s(a,b,c) the neighbour at that offset; 2.*dx, dx*dx and 4.*(dx*dx) are computed once:
+ *              px  = (s(1,0,0) - s(-1,0,0)) / (2.*dx)                                          likewise py, pz
+ *              pxx = ((s(1,0,0) - 2.*c) + s(-1,0,0)) / (dx*dx)                                 likewise pyy, pzz
+ *              pxy = (((s(1,1,0) - s(1,-1,0)) - s(-1,1,0)) + s(-1,-1,0)) / (4.*(dx*dx))        likewise pxz (x,z), pyz (y,z)
+ *              g2  = (px*px + py*py) + pz*pz;  g = sqrt(g2)                                    -> gmag
+ *              num = ((px*px)*(pyy+pzz) + (py*py)*(pxx+pzz)) + (pz*pz)*(pxx+pyy)
+ *              mix = ((px*py)*pxy + (px*pz)*pxz) + (py*pz)*pyz
+ *              H   = (num - 2.*mix) / (g2*g)                                                   -> kappa
+ *              A   = ((px*px)*(pyy*pzz - pyz*pyz) + (py*py)*(pxx*pzz - pxz*pxz)) + (pz*pz)*(pxx*pyy - pxy*pxy)
+ *              B   = ((px*py)*(pxz*pyz - pxy*pzz) + (py*pz)*(pxy*pxz - pyz*pxx)) + (px*pz)*(pxy*pyz - pxz*pyy)
+ *              K   = (A + 2.*B) / (g2*g2)                                                      -> gauss
+ *            Signs: a sphere of radius r with phi < 0 inside has kappa = +2/r and gauss = 1/r^2.
+ *   DEGENERATE  a cell with g2 < 1e-24 (a flat spot, e.g. the inside of a plateau): H = K = 0.0, gmag gets its g.  A NaN g2 is
+ *            not degenerate and gives NaN.
+ *   CLAMP    clamp == 0: none.  Otherwise lim = clamp / dx, computed once on the host, and
+ *              if (H > lim) H = lim;  if (H < -lim) H = -lim;      K likewise with lim*lim
+ *            -- comparisons, so a NaN stays NaN.  A cell is CLAMPED when a written value differs from the unclamped one (K counts
+ *            only where gauss is given).  gmag is never clamped.  A grid cannot resolve |kappa| > 1/dx, so clamp = 1 is the
+ *            usual choice: on the distance to a sphere with every interior point listed the largest unclamped |kappa|*dx is
+ *            10.8, at the cells next to the centre.
+ *   info     [0] list cells; [1] degenerate cells; [2] clamped cells; [3] 0, reserved.
+ *   kappa_max  the largest |kappa| AS STORED over the list cells: the maximum of bit patterns, so no order of reduction shows
+ *            in it.  info and kappa_max are written on LSF_OK only.
+ *   NaN      a non-finite stored value at a list cell -- kappa, or gauss or gmag where given -- gives LSF_ERR_NAN with the number
+ *            of such cells in lsf_last_error().  The outputs then hold what was computed; info and kappa_max are not written.
+ *   empty    LIST empty: LSF_OK, nothing written, info all 0, kappa_max = 0.0.
+ *   errors   LSF_ERR_INVALID, all detected before anything is written: a NULL phi, mask or kappa; an output that overlaps phi
+ *            or another output; the dimensions lsf_reinit_band refuses (nx, ny or nz < 2, a k-plane above 2 GB, more than
+ *            2^31 - 1 points); dx not finite or <= 0; clamp not finite or < 0.  No device: LSF_ERR_NO_DEVICE -- there is no CPU
+ *            fallback.
+ *   result   the outputs, info and kappa_max are those of the serial statement tests/curvature_ref.py bit for bit, on both
+ *            seams, on any stream, from run to run.  There is one arithmetic and no mode word.
+ *   seams    lsf_curvature_band takes phi, an input only, through its twin under lsf_mirror exactly as lsf_extract_surface takes
+ *            its phi, and the mask as lsf_reinit_band takes its mask.  The outputs have NO twin: each one given is staged as
+ *            lsf_extend_field stages q, copied in on every call and copied back on LSF_OK and on LSF_ERR_NAN.
+ *            lsf_curvature_band_device returns after the stream is synchronised (the host finishes the per-block counts).
+ * Guidance: the scheme is SECOND ORDER on a smooth phi (serial statement, distance to a sphere of radius R = 0.6, cells with
+ * |phi| < 2.1 dx against the level set through the cell, 2/r and 1/r^2: largest error of kappa 5.0e-2 of the surface's 2/R on 25^3
+ * points and 5.3e-3 on 49^3, of gauss 1.7e-1 of 1/R^2 and 1.3e-2).  phi need not be a distance, but the kinks of one (the medial axis, the clamp of
+ * lsf_mesh_distance(width)) give large values: that is what the clamp and info[2] are for.  kappa handed to lsf_advect_field_band
+ * as speed = a - b*kappa is UPWINDED by that call's Godunov term, which is fine for a small b; a centrally differenced parabolic
+ * term b*kappa*|grad(phi)| inside the transport stages is out of scope -- kappa and gmag are its ingredients.
+ * Work: the list build of lsf_reinit_band and ONE launch over the list, one lane per cell, 19 gathered loads and up to three
+ * stores; the host reads 32 bytes per 256 list cells.  Workspace: that of the list; the host seam adds one field per output given.
+ * Also out of scope: principal directions, fp32, multi-GPU, a dense call without a mask.
+ * Timed once on one MI355X beside ONE Euler step of lsf_advect_field_band on the same sphere and mask |phi| < 8.1 dx
+ * (profiles/curvature_band_time.txt, from profiles/micro/curvature_band_time.py; device seam, ms per call, list build included):
+ * 0.25 against 0.39 at 256^3 (2.2 % of the grid in the list) and 0.51 against 1.00 at 512^3 (1.1 %), with one output or all three.
+ * No speed is claimed beyond that record. */
+#define LSF_CURV_INFO_LEN 4
+int lsf_curvature_band(const double *phi, const int32_t *mask, double *kappa, double *gauss, double *gmag, int nx, int ny, int nz,
+                       double dx, double clamp, int64_t info[LSF_CURV_INFO_LEN], double *kappa_max);
+int lsf_curvature_band_device(const double *d_phi, const int32_t *d_mask, double *d_kappa, double *d_gauss, double *d_gmag, int nx,
+                              int ny, int nz, double dx, double clamp, int64_t info[LSF_CURV_INFO_LEN], double *kappa_max,
+                              void *stream);
+
 /* ---- iso-surface extraction: the zero (or iso) level of a field as an indexed triangle mesh (marching tetrahedra) ----------
  * No reference counterpart.  What gives the moved geometry back after lsf_advect_field: the level set phi = iso as nodes
  * surfX(nSurfNode,3) and triangles surfElem(nSurfElem,3), 1-based INTEGER*4, both Fortran-ordered -- the format lsf_phi0,

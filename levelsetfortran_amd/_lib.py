@@ -24,6 +24,7 @@ LSF_MESH_UNSIGNED, LSF_MESH_INFO_LEN = 1, 4  # include/lsf.h: lsf_mesh_distance
 LSF_ADVECT_RK3, LSF_ADVECT_EULER = 0, 1  # include/lsf.h: lsf_advect_field
 LSF_ADVECT_BAND_INFO_LEN = 3  # include/lsf.h: lsf_advect_field_band
 LSF_EVOLVE_INFO_LEN = 6  # include/lsf.h: lsf_evolve_band
+LSF_CURV_INFO_LEN = 4  # include/lsf.h: lsf_curvature_band
 LSF_SURF_INFO_LEN = 4  # include/lsf.h: lsf_extract_surface
 LSF_EXTEND_INFO_LEN = 3  # include/lsf.h: lsf_extend_field
 LSF_TRANSPORT_PEER, LSF_TRANSPORT_RCCL, LSF_TRANSPORT_MOCK = 0, 1, 2  # include/lsf.h: lsf_multi_configure
@@ -100,6 +101,10 @@ SIGNATURES = {
     "lsf_advect_field_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double,
                                              c_int, c_int, c_int, POINTER(c_int), POINTER(c_double), c_void_p, c_int, c_void_p,
                                              POINTER(c_double), c_void_p]),
+    "lsf_curvature_band": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p,
+                                   POINTER(c_double)]),
+    "lsf_curvature_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p,
+                                          POINTER(c_double), c_void_p]),
     "lsf_evolve_band": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_int,
                                 c_int, c_double, c_int, c_int, c_double, c_int, POINTER(c_int), POINTER(c_double), c_void_p, c_int, c_void_p,
                                 POINTER(c_double)]),

@@ -30,6 +30,7 @@
 #include "lsf_advect_field.hpp"
 #include "lsf_advect_band.hpp"
 #include "lsf_evolve_band.hpp"
+#include "lsf_curvature_band.hpp"
 #include "lsf_extract_surface.hpp"
 
 using namespace lsf;
@@ -187,7 +188,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -737,6 +738,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_advect_band.hpp"
 
 #include "lsf_host_evolve_band.hpp"
+
+#include "lsf_host_curvature_band.hpp"
 
 #include "lsf_host_extract_surface.hpp"
 
@@ -1632,6 +1635,53 @@ int lsf_evolve_band(double* phi, int32_t* mask, const double* u, const double* v
         g_err = keep;
     } else if (rc != LSF_ERR_INVALID) // (an invalid call is found before the twins are written: they stay what they were)
         twin_drop(c.twin_phi), twin_drop(tm);
+    return rc;
+}
+
+int lsf_curvature_band_device(const double* d_phi, const int32_t* d_mask, double* d_kappa, double* d_gauss, double* d_gmag, int nx, int ny, int nz,
+                              double dx, double clamp, int64_t info[LSF_CURV_INFO_LEN], double* kappa_max, void* stream)
+{
+    Trace trace_("lsf_curvature_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = curvature_band_args_ok(d_phi, d_mask, d_kappa, d_gauss, d_gmag, nx, ny, nz, dx, clamp))) return rc;
+    return curvature_band_core(d_phi, d_mask, d_kappa, d_gauss, d_gmag, nx, ny, nz, dx, clamp, info, kappa_max, (hipStream_t)stream);
+}
+
+int lsf_curvature_band(const double* phi, const int32_t* mask, double* kappa, double* gauss, double* gmag, int nx, int ny, int nz, double dx,
+                       double clamp, int64_t info[LSF_CURV_INFO_LEN], double* kappa_max)
+{
+    Trace trace_("lsf_curvature_band");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = curvature_band_args_ok(phi, mask, kappa, gauss, gmag, nx, ny, nz, dx, clamp))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
+    // The outputs have no twin: as lsf_extend_field stages q, each one given is staged in a slot of its own from the host on every call
+    // (what it holds outside the list stays bit for bit) and comes home on LSF_OK and on LSF_ERR_NAN, lsf_mirror or not.  Staged before
+    // phi's twin is touched.
+    double* h_out[3] = {kappa, gauss, gmag};
+    const Slot s_out[3] = {S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG};
+    double* d_out[3] = {nullptr, nullptr, nullptr};
+    for (int q = 0; q < 3; ++q) {
+        if (!h_out[q]) continue;
+        if ((rc = ws(c.slot[s_out[q]], bytes))) return rc;
+        HIPCHK(hipMemcpy(c.slot[s_out[q]].p, h_out[q], bytes, hipMemcpyHostToDevice));
+        d_out[q] = (double*)c.slot[s_out[q]].p;
+    }
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_extract_surface
+    // the mask travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
+    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+    const Slot sm = is_nb ? S_HNB : S_HSB;
+    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+    rc = curvature_band_core((const double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, d_out[0], d_out[1], d_out[2], nx, ny, nz, dx, clamp, info,
+                             kappa_max, nullptr);
+    if (rc != LSF_OK && rc != LSF_ERR_NAN) return rc;
+    const std::string keep = g_err;
+    for (int q = 0; q < 3; ++q)
+        if (h_out[q]) HIPCHK(hipMemcpy(h_out[q], d_out[q], bytes, hipMemcpyDeviceToHost));
+    g_err = keep;
     return rc;
 }
 

@@ -28,6 +28,9 @@
 !   evolveBand(phi,mask,u,v,w,nx,ny,nz,dx,dt,steps)      no reference counterpart: the band time loop -- transport, two sweeps of
 !                                                        the reinitialisation and the list following the surface; phi and mask
 !                                                        are both updated (include/lsf.h: lsf_evolve_band)
+!   curvatureBand(phi,mask,kappa,nx,ny,nz,dx,clamp)      the reference's own is commented out (subs.f90:426-448): the mean
+!                                                        curvature div(grad(phi)/|grad(phi)|) on the cells with mask == 1
+!                                                        only (include/lsf.h: lsf_curvature_band)
 !   extractSurface(phi,nx,ny,nz,dx,xLo,iso,surfX,nSurfNode,surfElem,nSurfElem)
 !                                                        no reference counterpart: the level set phi = iso as a triangle mesh,
 !                                                        marching tetrahedra (include/lsf.h: lsf_extract_surface)
@@ -96,6 +99,7 @@ PUBLIC :: extendField
 PUBLIC :: advectField
 PUBLIC :: advectFieldBand
 PUBLIC :: evolveBand
+PUBLIC :: curvatureBand
 PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
@@ -273,6 +277,20 @@ INTERFACE
       REAL(c_double), INTENT(OUT) :: margin
       INTEGER(c_int) :: rc
    END FUNCTION lsf_evolve_band
+   ! int lsf_curvature_band(const double*,const int32_t*,double*,double*,double*,int,int,int,double,double,int64_t[4],double*)
+   FUNCTION lsf_curvature_band(phi,mask,kappa,gauss,gmag,nx,ny,nz,dx,clamp,info,kappa_max) &
+            BIND(C,NAME='lsf_curvature_band') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(IN) :: phi(*)
+      INTEGER(c_int), INTENT(IN) :: mask(*)
+      REAL(c_double), INTENT(INOUT) :: kappa(*)
+      TYPE(c_ptr), VALUE :: gauss,gmag       ! NULL: not wanted
+      INTEGER(c_int), VALUE :: nx,ny,nz
+      REAL(c_double), VALUE :: dx,clamp
+      INTEGER(c_int64_t), INTENT(OUT) :: info(4)
+      REAL(c_double), INTENT(OUT) :: kappa_max
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_curvature_band
    FUNCTION lsf_advect_nodes(phi,phiSB,nx,ny,nz,dx,xLo,surfXX,nSurfNode,iters) &
             BIND(C,NAME='lsf_advect_nodes') RESULT(rc)
       IMPORT :: c_int, c_double
@@ -840,6 +858,41 @@ IF (rc == LSF_ERR_NAN) STOP
 DEALLOCATE(trace)
 
 END SUBROUTINE evolveBand
+
+!*************************************************************************************!
+! Mean curvature of the level sets on the cells of a mask only (include/lsf.h:
+! lsf_curvature_band; the reference's own "true curvature" is commented out,
+! subs.f90:426-448): kappa = div(grad(phi)/|grad(phi)|) = k1 + k2 from second-order central
+! differences at the interior points with mask == 1 (e.g. phiNB of narrowBand); a sphere
+! with phi < 0 inside has kappa = +2/r.  kappa is written at those cells only: every
+! other point keeps what it held.  phi and mask are read only.  clamp > 0 limits |kappa|
+! to clamp/dx (1. is the usual choice: a grid resolves no more), 0. means no clamp.
+! Prints the list cells, the flat cells (kappa = 0 there), the clamped cells and the
+! largest |kappa| in units of 1/dx.  A non-finite kappa stops the run like advectField.
+!*************************************************************************************!
+SUBROUTINE curvatureBand(phi,mask,kappa,nx,ny,nz,dx,clamp)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+REAL,INTENT(IN) :: dx,clamp
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: mask
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: kappa
+REAL :: kmax
+INTEGER(c_int64_t) :: info(4)
+INTEGER(c_int) :: rc
+
+kmax = 0.
+info = 0
+CALL lsf_set_mirror()
+rc = lsf_curvature_band(phi,mask,kappa,c_null_ptr,c_null_ptr,nx,ny,nz,dx,clamp,info,kmax)
+IF (rc /= LSF_OK .AND. rc /= LSF_ERR_NAN) CALL lsf_fail('lsf_curvature_band',rc)
+IF (rc == LSF_OK) PRINT*, " Curvature on the band: list cells ",info(1),", flat cells ",info(2),", clamped cells ",info(3), &
+                          ", largest |kappa|*dx ",kmax*dx
+IF (rc == LSF_ERR_NAN) PRINT*, " Curvature on the band: a list cell holds a non-finite kappa"
+PRINT*
+IF (rc == LSF_ERR_NAN) STOP
+
+END SUBROUTINE curvatureBand
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

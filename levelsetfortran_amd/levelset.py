@@ -25,6 +25,10 @@ and the transport of lsf_advect_field on the cells of a mask only (no reference 
   advectFieldBand(phi, mask, nx, ny, nz, dx, dt, steps, ...)    include/lsf.h: lsf_advect_field_band
   evolveBand(phi, mask, nx, ny, nz, dx, dt, steps, ...)         include/lsf.h: lsf_evolve_band
 
+and the mean and Gaussian curvature of the level sets on the cells of a mask (the reference's own is commented out, subs.f90:426-448):
+
+  curvatureBand(phi, mask, nx, ny, nz, dx, kappa, ...)          include/lsf.h: lsf_curvature_band
+
 and a quantity known on that band carried to the rest of the grid constant along the normals (no reference counterpart):
 
   extendField(q, phi, nx, ny, nz, dx, band=... | mask=...)      include/lsf.h: lsf_extend_field
@@ -51,7 +55,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -709,6 +713,60 @@ def evolveBand(phi, mask, nx: int, ny: int, nz: int, dx: float, dt: float, steps
         e.report = rep  # the steps run, the NaN one included
         raise
     return rep
+
+
+class CurvatureReport(NamedTuple):
+    """What lsf_curvature_band reports (include/lsf.h): the list cells, those with |grad(phi)|^2 < 1e-24 (kappa = gauss = 0 there),
+    those where the clamp changed a written value, and the largest |kappa| as stored over the list cells."""
+    cells: int
+    degenerate: int
+    clamped: int
+    kappa_max: float
+
+
+def curvatureBand(phi, mask, nx: int, ny: int, nz: int, dx: float, kappa, *, gauss=None, gmag=None, clamp: float = 0.0) -> CurvatureReport:
+    """Mean curvature k1 + k2 = div(grad(phi)/|grad(phi)|) of the level sets of `phi` on the cells of `mask` only (include/lsf.h:
+    lsf_curvature_band), written into `kappa`; optionally the Gaussian curvature k1 * k2 into `gauss` and |grad(phi)| into `gmag`.
+
+    mask: int32, phi's layout and kind; the interior points where it is 1 are the list.  kappa, gauss, gmag: fields of phi's layout
+    and kind, written at the list cells and nowhere else -- what they hold at other points stays, NaNs included, so kappa can be
+    handed to advectFieldBand as (part of) `speed` on the same mask.  phi and mask are read only.  Second-order central differences;
+    a sphere with phi < 0 inside has kappa = +2/r.  clamp=c > 0 limits |kappa| to c/dx and |gauss| to (c/dx)^2 (a grid cannot resolve
+    more than 1/dx: clamp=1 is the usual choice); 0 means no clamp.  Raises LsfNaNError when a list cell received a non-finite
+    value (the outputs hold what was computed; the message carries the count).  All arrays are numpy arrays (host seam) or all are
+    torch CUDA tensors (device seam, on the tensor's current stream).
+    """
+    if mask is None or kappa is None:
+        raise ValueError("mask (int32) and kappa (float64) must be fields of phi's shape")
+    dev = _is_torch(phi)
+    outs = [("kappa", kappa)] + [(n, a) for n, a in (("gauss", gauss), ("gmag", gmag)) if a is not None]
+    if any(_is_torch(a) != dev for _, a in outs + [("mask", mask)]):
+        raise TypeError("phi, mask, kappa, gauss and gmag must all be numpy arrays or all be CUDA tensors")
+    clamp = float(clamp)
+    if not (clamp >= 0.0) or clamp == float("inf"):
+        raise ValueError("clamp must be finite and >= 0 (0: no clamp)")
+    if dev:
+        import torch
+
+        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
+        if any(a.device != phi.device for _, a in outs + [("mask", mask)]):
+            raise ValueError("phi, mask, kappa, gauss and gmag must live on one device")
+        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+    else:
+        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
+        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+    p = ptr(phi, "phi")
+    q = {n: ptr(a, n) for n, a in outs}
+    lib = _lib.load()
+    info = np.zeros(_lib.LSF_CURV_INFO_LEN, dtype=np.int64)
+    kmax = ctypes.c_double(0.0)
+    args = (p, m, q["kappa"], q.get("gauss"), q.get("gmag"), nx, ny, nz, float(dx), clamp, info.ctypes.data, ctypes.byref(kmax))
+    if dev:
+        rc = lib.lsf_curvature_band_device(*args, _stream_and_device(phi))
+    else:
+        rc = lib.lsf_curvature_band(*args)
+    _lib.check(rc)
+    return CurvatureReport(int(info[0]), int(info[1]), int(info[2]), float(kmax.value))
 
 
 class SurfaceInfo(NamedTuple):
