@@ -611,6 +611,77 @@ int lsf_curvature_band_device(const double *d_phi, const int32_t *d_mask, double
                               int ny, int nz, double dx, double clamp, int64_t info[LSF_CURV_INFO_LEN], double *kappa_max,
                               void *stream);
 
+/* ---- extension on a cell list: a quantity carried off the frozen cells of a caller's mask, constant along the normals ----------
+ * No reference counterpart.  lsf_extend_field on the list of lsf_reinit_band: what carries a speed known on or next to the surface
+ * only -- F = a - b*kappa from lsf_curvature_band, a growth rate, a solver's velocity -- to every cell of the mask that
+ * lsf_advect_field_band or lsf_evolve_band moves the surface on, at a cost proportional to the list and not to the grid.  The
+ * operator is lsf_extend_field's visit; the raster sweeps are replaced by JACOBI passes over the list.  q, phi, mask and known have
+ * the layout of every other entry point.  known, passes_done, changed_trace and info may be NULL; mask is required.
+ *   LIST     the rule of lsf_reinit_band: the interior points (1..n-1 on each axis) with mask == 1.  Any other mask value means
+ *            "not in the list"; a 1 on a wall point is ignored.
+ *   FROZEN   with known != NULL: the list cells with known == 1; band is ignored, and so is known off the list.  With
+ *            known == NULL: the list cells with |phi| < far; far = band * dx, computed once on the host.  Frozen cells hold the
+ *            caller's q and are never written.  phi, mask and known are inputs only: read, never written.
+ *   off list q is never read and never written at a point that is not in the list: what it holds there stays bit for bit, and a NaN
+ *            there is legal -- what lsf_curvature_band leaves.  phi is read at list cells and at their six axis neighbours only.
+ *   start    every non-frozen list cell is UNKNOWN: whatever q holds there on entry is ignored.  Unknown is represented in the
+ *            field by NaN.
+ *   pass     every non-frozen list cell is visited with q AS IT WAS AT THE START OF THE PASS: all reads of a pass come before its
+ *            writes.  The visit of a cell p is that of lsf_extend_field, with f = |phi|.  For each axis A: n_A is the one of the
+ *            two neighbours with the smaller f, the one at the lower index on a tie;  w_A = f(p) - f(n_A);  the axis is USED when
+ *            w_A > 0, n_A is in the LIST and q(n_A) is not NaN.  The neighbour is chosen by f first: if it is not in the list
+ *            the axis is unused, the other neighbour is not tried.
+ *              t_A = w_A * q(n_A) and s_A = w_A when used, both 0.0 otherwise;
+ *              den = (s_x + s_y) + s_z;  den == 0: nothing happens.  Otherwise new = ((t_x + t_y) + t_z) / den;
+ *              if !(new == old) -- true for an unknown old -- new is stored and the visit is counted.
+ *            Evaluated exactly as written, left to right, without contraction; / is the IEEE division.
+ *   trace    changed_trace[p], p < trace_cap: the number of counted visits of pass p (an integer: no arrival order in it).
+ *   stop     after the first pass whose count is 0 (that pass is counted) or after max_passes; passes_done = passes run.
+ *            Reaching max_passes is LSF_OK.  A cell depends only on neighbours of strictly smaller |phi|, so the dependency graph
+ *            has no cycle, the fixed point is unique, and Jacobi passes reach it EXACTLY in as many passes as the longest chain
+ *            of dependent cells plus one: the passes stop by themselves, with a count of 0.
+ *   info     [0] list cells  [1] frozen cells  [2] non-frozen list cells that hold a value on return  [3] UNREACHED list cells,
+ *            still NaN on return: stored as NaN and reported, never filled with a guess (a cell all of whose chosen neighbours
+ *            are outside the list, unknown themselves or not below it in |phi|).  Written on LSF_OK only, and so are
+ *            passes_done and the trace.
+ *   result   field, passes_done, trace and info are those of the serial statement tests/extend_band_ref.py bit for bit, on both
+ *            seams, on any stream, from run to run -- after every pass, not only at the fixed point.  On a list that keeps clear
+ *            of the walls and holds every point the full-grid call would draw on, the converged result at list cells equals the
+ *            converged lsf_extend_field with the same frozen set.
+ *   range    as in lsf_extend_field: the bit promise is stated for finite frozen q and finite phi whose products w * q do not
+ *            overflow.
+ *   errors   LSF_ERR_INVALID, all decided before q is written, the offending count in lsf_last_error() where there is one: a NULL
+ *            q, phi or mask; the dimensions lsf_reinit_band refuses (nx, ny or nz < 2, a k-plane above 2 GB, more than 2^31 - 1
+ *            points); dx not finite or <= 0; known == NULL with band not finite or <= 0; max_passes < 1; trace_cap < 0; q sharing
+ *            a byte with phi; an empty list; no frozen cell; a non-finite q on a frozen cell (count); list cells that see a
+ *            non-finite phi at themselves or at one of their six neighbours (count of such cells).  No device:
+ *            LSF_ERR_NO_DEVICE -- there is no CPU fallback.
+ *   seams    lsf_extend_field_band takes phi through its twin under lsf_mirror as lsf_extend_field does, and the mask as
+ *            lsf_reinit_band takes its mask.  known is staged in a workspace slot of its own on every call.  q has NO twin: it is
+ *            staged as lsf_extend_field stages it, copied in on every call and copied back on LSF_OK only.
+ *            lsf_extend_field_band_device returns after the stream is synchronised (the host reads the counts of 8 passes at a time).
+ * Guidance: FIRST ORDER, every value a convex combination of frozen values, as in lsf_extend_field.  The recipe on ONE mask:
+ * lsf_curvature_band (kappa at list cells, NaN elsewhere) -> speed = a - b*kappa -> lsf_extend_field_band with known = the cells
+ * next to the surface -> lsf_advect_field_band or lsf_evolve_band with that speed.  The number of passes is the longest chain of
+ * dependent cells plus one: about twice the width of the list in cells beyond the frozen band (12 for a 4.1-cell mask around a
+ * 1.5-cell band, 20 for 8.1, serial statement).  Work: the list build of lsf_reinit_band, one plan launch (7 gathered loads of phi
+ * per cell) and two launches per pass over the list (4 gathered loads of q, one division); the host reads 64 bytes per 8 passes.
+ * Workspace beyond the list's: 46 bytes per list cell; the host seam adds one field for q and one for known.  Out of scope: several
+ * quantities in one call, higher order, fp32, multi-GPU, keeping the list on the device across calls or inside lsf_evolve_band,
+ * single-buffer passes.
+ * Timed once on one MI355X beside lsf_extend_field on the same two-sphere field, frozen band 3.5 cells, mask |phi| < 8.1 dx
+ * (profiles/extend_band_time.txt, from profiles/micro/extend_band_time.py; device seam, ms per call to convergence, list build
+ * included): 1.10 against 115.8 at 256^3 (514 594 list cells, 3.1 % of the grid, 26 passes of 0.030 ms, 0.33 ms of list build, plan
+ * and counts) and 3.05 against 660.8 at 512^3 (2 048 561 cells, 1.5 %, 28 passes of 0.086 ms, 0.64 ms fixed).  No speed is claimed
+ * beyond that record. */
+#define LSF_EXTEND_BAND_INFO_LEN 4
+int lsf_extend_field_band(double *q, const double *phi, const int32_t *mask, const int32_t *known, int nx, int ny, int nz, double dx,
+                          double band, int max_passes, int *passes_done, int64_t *changed_trace, int trace_cap,
+                          int64_t info[LSF_EXTEND_BAND_INFO_LEN]);
+int lsf_extend_field_band_device(double *d_q, const double *d_phi, const int32_t *d_mask, const int32_t *d_known, int nx, int ny,
+                                 int nz, double dx, double band, int max_passes, int *passes_done, int64_t *changed_trace,
+                                 int trace_cap, int64_t info[LSF_EXTEND_BAND_INFO_LEN], void *stream);
+
 /* ---- iso-surface extraction: the zero (or iso) level of a field as an indexed triangle mesh (marching tetrahedra) ----------
  * No reference counterpart.  What gives the moved geometry back after lsf_advect_field: the level set phi = iso as nodes
  * surfX(nSurfNode,3) and triangles surfElem(nSurfElem,3), 1-based INTEGER*4, both Fortran-ordered -- the format lsf_phi0,

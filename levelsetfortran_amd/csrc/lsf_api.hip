@@ -31,6 +31,7 @@
 #include "lsf_advect_band.hpp"
 #include "lsf_evolve_band.hpp"
 #include "lsf_curvature_band.hpp"
+#include "lsf_extend_band.hpp"
 #include "lsf_extract_surface.hpp"
 
 using namespace lsf;
@@ -188,7 +189,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -740,6 +741,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_evolve_band.hpp"
 
 #include "lsf_host_curvature_band.hpp"
+
+#include "lsf_host_extend_band.hpp"
 
 #include "lsf_host_extract_surface.hpp"
 
@@ -1683,6 +1686,50 @@ int lsf_curvature_band(const double* phi, const int32_t* mask, double* kappa, do
         if (h_out[q]) HIPCHK(hipMemcpy(h_out[q], d_out[q], bytes, hipMemcpyDeviceToHost));
     g_err = keep;
     return rc;
+}
+
+int lsf_extend_field_band_device(double* d_q, const double* d_phi, const int32_t* d_mask, const int32_t* d_known, int nx, int ny, int nz, double dx,
+                                 double band, int max_passes, int* passes_done, int64_t* changed_trace, int trace_cap,
+                                 int64_t info[LSF_EXTEND_BAND_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_extend_field_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = extend_band_args_ok(d_q, d_phi, d_mask, d_known, nx, ny, nz, dx, band, max_passes, trace_cap))) return rc;
+    return extend_band_core(d_q, d_phi, d_mask, d_known, nx, ny, nz, dx, band, max_passes, passes_done, changed_trace, trace_cap, info,
+                            (hipStream_t)stream);
+}
+
+int lsf_extend_field_band(double* q, const double* phi, const int32_t* mask, const int32_t* known, int nx, int ny, int nz, double dx, double band,
+                          int max_passes, int* passes_done, int64_t* changed_trace, int trace_cap, int64_t info[LSF_EXTEND_BAND_INFO_LEN])
+{
+    Trace trace_("lsf_extend_field_band");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = extend_band_args_ok(q, phi, mask, known, nx, ny, nz, dx, band, max_passes, trace_cap))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    // q is staged as lsf_extend_field stages it: no twin, copied in from the host on every call (what it holds off the list stays bit
+    // for bit) and copied back on LSF_OK only.  known is an input only and has a slot of its own.  Both before phi's twin is touched.
+    if ((rc = ws(c.slot[S_EXT_Q], n * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpy(c.slot[S_EXT_Q].p, q, n * sizeof(double), hipMemcpyHostToDevice));
+    const int32_t* d_known = nullptr;
+    if (known) {
+        if ((rc = ws(c.slot[S_XB_KNOWN], n * sizeof(int32_t)))) return rc;
+        HIPCHK(hipMemcpy(c.slot[S_XB_KNOWN].p, known, n * sizeof(int32_t), hipMemcpyHostToDevice));
+        d_known = (const int32_t*)c.slot[S_XB_KNOWN].p;
+    }
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // phi is an input only, as in lsf_extend_field
+    // the mask travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
+    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+    const Slot sm = is_nb ? S_HNB : S_HSB;
+    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+    if ((rc = extend_band_core((double*)c.slot[S_EXT_Q].p, (const double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, d_known, nx, ny, nz, dx, band,
+                               max_passes, passes_done, changed_trace, trace_cap, info, nullptr)))
+        return rc;
+    HIPCHK(hipMemcpy(q, c.slot[S_EXT_Q].p, n * sizeof(double), hipMemcpyDeviceToHost));
+    return LSF_OK;
 }
 
 int lsf_extract_surface_device(const double* d_phi, int nx, int ny, int nz, double dx, const double xLo[3], double iso, int* nSurfNode,

@@ -31,6 +31,9 @@
 !   curvatureBand(phi,mask,kappa,nx,ny,nz,dx,clamp)      the reference's own is commented out (subs.f90:426-448): the mean
 !                                                        curvature div(grad(phi)/|grad(phi)|) on the cells with mask == 1
 !                                                        only (include/lsf.h: lsf_curvature_band)
+!   extendFieldBand(q,phi,mask,nx,ny,nz,dx,band)         no reference counterpart: extendField on the cells with mask == 1
+!                                                        only, by Jacobi passes over the list: q carried off the list cells
+!                                                        with |phi| < band*dx (include/lsf.h: lsf_extend_field_band)
 !   extractSurface(phi,nx,ny,nz,dx,xLo,iso,surfX,nSurfNode,surfElem,nSurfElem)
 !                                                        no reference counterpart: the level set phi = iso as a triangle mesh,
 !                                                        marching tetrahedra (include/lsf.h: lsf_extract_surface)
@@ -100,6 +103,7 @@ PUBLIC :: advectField
 PUBLIC :: advectFieldBand
 PUBLIC :: evolveBand
 PUBLIC :: curvatureBand
+PUBLIC :: extendFieldBand
 PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
@@ -291,6 +295,21 @@ INTERFACE
       REAL(c_double), INTENT(OUT) :: kappa_max
       INTEGER(c_int) :: rc
    END FUNCTION lsf_curvature_band
+   ! int lsf_extend_field_band(double*,const double*,const int32_t*,const int32_t*,int,int,int,double,double,int,int*,int64_t*,int,
+   !                           int64_t[4])
+   FUNCTION lsf_extend_field_band(q,phi,mask,known,nx,ny,nz,dx,band,max_passes,passes_done,changed_trace,trace_cap,info) &
+            BIND(C,NAME='lsf_extend_field_band') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(INOUT) :: q(*)
+      REAL(c_double), INTENT(IN) :: phi(*)
+      INTEGER(c_int), INTENT(IN) :: mask(*)
+      TYPE(c_ptr), VALUE :: known            ! NULL: the frozen cells are the list cells with |phi| < band*dx
+      INTEGER(c_int), VALUE :: nx,ny,nz,max_passes,trace_cap
+      REAL(c_double), VALUE :: dx,band
+      INTEGER(c_int), INTENT(OUT) :: passes_done
+      INTEGER(c_int64_t), INTENT(OUT) :: changed_trace(*),info(4)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_extend_field_band
    FUNCTION lsf_advect_nodes(phi,phiSB,nx,ny,nz,dx,xLo,surfXX,nSurfNode,iters) &
             BIND(C,NAME='lsf_advect_nodes') RESULT(rc)
       IMPORT :: c_int, c_double
@@ -737,6 +756,35 @@ PRINT*, " Extend field: ",done," rounds, ",info(1)," frozen points, last round c
 PRINT*
 
 END SUBROUTINE extendField
+
+!*************************************************************************************!
+! extendField on the cells with mask == 1 only (include/lsf.h: lsf_extend_field_band; no
+! reference counterpart): the list cells with |phi| < band*dx hold the caller's q and are
+! never written; every other list cell receives the value that reaches it along the normal
+! through list cells, at most 256 Jacobi passes over the list.  q is neither read nor
+! written outside the list; phi and mask are not written.  List cells no value reaches
+! stay NaN and are counted.  Prints the passes run, the visits the last one changed
+! (0: converged) and the unreached cells.
+!*************************************************************************************!
+SUBROUTINE extendFieldBand(q,phi,mask,nx,ny,nz,dx,band)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+REAL,INTENT(IN) :: dx,band
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: q
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: mask
+INTEGER(c_int), PARAMETER :: max_passes = 256
+INTEGER(c_int64_t) :: trace(max_passes),info(4)
+INTEGER(c_int) :: rc,done
+
+CALL lsf_set_mirror()
+rc = lsf_extend_field_band(q,phi,mask,c_null_ptr,nx,ny,nz,dx,band,max_passes,done,trace,max_passes,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_extend_field_band',rc)
+PRINT*, " Extend field on the band: ",info(1)," list cells, ",info(2)," frozen, ",done," passes, last pass changed ",trace(done), &
+        ", unreached ",info(4)
+PRINT*
+
+END SUBROUTINE extendFieldBand
 
 !*************************************************************************************!
 ! Transport of the level set by a velocity field, phi_t + u.grad(phi) = 0 (include/lsf.h:

@@ -55,7 +55,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -470,6 +470,89 @@ def extendField(q, phi, nx: int, ny: int, nz: int, dx: float, *, band: Optional[
     n = done.value
     changed = [int(v) for v in trace[:n]]
     return ExtendReport(n, changed, int(info[0]), int(info[1]), int(info[2]), bool(n and changed[-1] == 0))
+
+
+class ExtendBandReport(NamedTuple):
+    """What lsf_extend_field_band reports (include/lsf.h): Jacobi passes run, whether the last one changed nothing, the visits that
+    changed a value in each pass (at most trace_cap of them), the list cells, the frozen ones among them, and the other list cells
+    that hold a value / are still NaN."""
+    passes: int
+    converged: bool
+    trace: List[int]
+    cells: int
+    frozen: int
+    reached: int
+    unreached: int
+
+
+_EXTEND_BAND_TRACE = 1 << 16  # passes whose counts the Python layer keeps at most
+
+
+def extendFieldBand(q, phi, mask, dx: float, known=None, band: Optional[float] = None, max_passes: int = 256, trace_cap: Optional[int] = None):
+    """Carries `q` off the frozen cells of the list of `mask` constant along the normals of `phi`, on the list only (include/lsf.h:
+    lsf_extend_field_band).  Returns (q, ExtendBandReport); `q` is updated in place, `phi`, `mask` and `known` are read only.
+
+    q, phi: 3-D float64 fields of one shape -- numpy, Fortran-ordered (nx+1, ny+1, nz+1), or torch CUDA tensors (nz+1, ny+1, nx+1);
+    mask and known: int32, same layout and kind.  The list is the interior points with mask == 1, as in reinitBand, advectFieldBand
+    and curvatureBand.  Exactly one of `known` / `band`: known freezes the list cells where it is 1, band=w those with
+    |phi| < w*dx.  Frozen cells keep the caller's q; every other list cell receives the first-order upwind value by Jacobi passes
+    until a pass changes nothing or max_passes is reached (then converged is False).  Points outside the list are neither read nor
+    written in q -- NaN is fine there, which is what curvatureBand leaves -- and a list cell no value reaches stays NaN and is
+    counted in `unreached`.  The recipe on one mask: curvatureBand -> extendFieldBand -> advectFieldBand / evolveBand.
+    """
+    if mask is None:
+        raise ValueError("mask (int32) must be a field of phi's shape")
+    if (known is None) == (band is None):
+        raise ValueError("give exactly one of known= (int32; freezes the list cells with known == 1) and band= (cells; freezes |phi| < band*dx)")
+    dev = _is_torch(q)
+    if any(_is_torch(a) != dev for a in (phi, mask) + (() if known is None else (known,))):
+        raise TypeError("q, phi, mask and known must all be numpy arrays (host seam) or all be torch CUDA tensors (device seam)")
+    if not dev and not isinstance(q, np.ndarray):
+        raise TypeError("q must be a numpy array of float64 or a CUDA tensor of torch.float64")
+    if (q.dim() if dev else q.ndim) != 3:
+        raise ValueError("q must be a 3-D field: the grid size is taken from its shape")
+    nx, ny, nz = (int(s) - 1 for s in (tuple(q.shape)[::-1] if dev else q.shape))
+    dx = float(dx)
+    if not (dx > 0.0) or dx == float("inf"):
+        raise ValueError("dx must be finite and > 0")
+    if band is not None and (not (float(band) > 0.0) or float(band) == float("inf")):
+        raise ValueError("band must be finite and > 0")
+    max_passes = int(max_passes)
+    if max_passes < 1:
+        raise ValueError("max_passes must be >= 1")
+    if trace_cap is not None and int(trace_cap) < 0:
+        raise ValueError("trace_cap must be >= 0")
+    if dev:
+        import torch
+
+        p = _dev_ptr(q, torch.float64, nx, ny, nz, "q")
+        f = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+        k = _dev_ptr(known, torch.int32, nx, ny, nz, "known") if known is not None else None
+        if any(a.device != q.device for a in (phi, mask) + (() if known is None else (known,))):
+            raise ValueError("q, phi, mask and known must live on one device")
+    else:
+        p = _host_ptr(q, np.float64, nx, ny, nz, "q")
+        f = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
+        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+        k = _host_ptr(known, np.int32, nx, ny, nz, "known") if known is not None else None
+    if p == f:
+        raise ValueError("q and phi must be different arrays")
+    lib = _lib.load()
+    cap = min(max_passes, _EXTEND_BAND_TRACE)
+    trace = np.zeros(cap, dtype=np.int64)
+    done = ctypes.c_int(0)
+    info = np.zeros(_lib.LSF_EXTEND_BAND_INFO_LEN, dtype=np.int64)
+    args = (p, f, m, k, nx, ny, nz, dx, 0.0 if band is None else float(band), max_passes, ctypes.byref(done), trace.ctypes.data, cap, info.ctypes.data)
+    if dev:
+        rc = lib.lsf_extend_field_band_device(*args, _stream_and_device(q))
+    else:
+        rc = lib.lsf_extend_field_band(*args)
+    _lib.check(rc)
+    n = done.value
+    converged = n < max_passes or bool(0 < n <= cap and trace[n - 1] == 0)
+    keep = min(n, cap if trace_cap is None else min(cap, int(trace_cap)))
+    return q, ExtendBandReport(n, converged, [int(v) for v in trace[:keep]], int(info[0]), int(info[1]), int(info[2]), int(info[3]))
 
 
 class AdvectReport(NamedTuple):
