@@ -804,9 +804,17 @@ int lsf_mirror_sync(void *host);
  * an un-synced result is written through that address by lsf_release_workspace, by lsf_mirror() when LAZY is switched
  * off and by a later seam call that needs the slot for another array -- so an array with a twin must be synced
  * (lsf_mirror_sync) or forgotten (lsf_mirror_forget) BEFORE it is freed, and a new array that happens to get the same
- * address must not be taken for the old one (forget, or keep LSF_MIRROR_TRUST off).  A seam call that FAILS drops the
- * twins it touched: nothing of a failed call is ever copied to the host, and an un-synced earlier result in those slots is
- * lost with it (the error is the caller's signal). */
+ * address must not be taken for the old one (forget, or keep LSF_MIRROR_TRUST off).  Nothing of a FAILED seam call is ever
+ * copied to the host.  What becomes of the twins it touched depends on how far the call came:
+ *   - a call refused before it wrote anything keeps them as they were, an un-synced earlier result included, which a later
+ *     lsf_mirror_sync still brings home: every LSF_ERR_INVALID of lsf_advect_field, lsf_advect_field_band, lsf_evolve_band,
+ *     lsf_curvature_band, lsf_extend_field, lsf_extend_field_band and lsf_extract_surface (argument checks and the checks of
+ *     u, v, w, speed, q and the list alike: all are made before phi or the mask is written), and the argument checks of
+ *     every other call, which come before the twins are looked at;
+ *   - any other failure -- LSF_ERR_HIP anywhere, and an error that lsf_reinit, lsf_minmax, lsf_reinit_band or
+ *     lsf_distance_fill find after their arrays were staged (iter < 0, say) -- drops the twins of the in/out arrays: an
+ *     un-synced earlier result in those slots is lost with it (the error is the caller's signal).
+ * LSF_ERR_NAN is a result, not a failure: the arrays come home (or stay on the device under LSF_MIRROR_LAZY) as on LSF_OK. */
 int lsf_mirror_forget(const void *host);
 int lsf_snapshot(const double *phi, double *phiO, int nx, int ny, int nz);
 int lsf_sumsq_diff(const double *phi, const double *phiO, int nx, int ny, int nz, double *sum);
