@@ -595,8 +595,8 @@ int lsf_evolve_band_device(double *d_phi, int32_t *d_mask, const double *d_u, co
  * |phi| < 2.1 dx against the level set through the cell, 2/r and 1/r^2: largest error of kappa 5.0e-2 of the surface's 2/R on 25^3
  * points and 5.3e-3 on 49^3, of gauss 1.7e-1 of 1/R^2 and 1.3e-2).  phi need not be a distance, but the kinks of one (the medial axis, the clamp of
  * lsf_mesh_distance(width)) give large values: that is what the clamp and info[2] are for.  kappa handed to lsf_advect_field_band
- * as speed = a - b*kappa is UPWINDED by that call's Godunov term, which is fine for a small b; a centrally differenced parabolic
- * term b*kappa*|grad(phi)| inside the transport stages is out of scope -- kappa and gmag are its ingredients.
+ * as speed = a - b*kappa is UPWINDED by that call's Godunov term, which is fine for a small b; the centrally differenced parabolic
+ * term b*kappa*|grad(phi)| inside the transport stages is lsf_evolve_band_curv below, built from this call's H and g.
  * Work: the list build of lsf_reinit_band and ONE launch over the list, one lane per cell, 19 gathered loads and up to three
  * stores; the host reads 32 bytes per 256 list cells.  Workspace: that of the list; the host seam adds one field per output given.
  * Also out of scope: principal directions, fp32, multi-GPU, a dense call without a mask.
@@ -610,6 +610,62 @@ int lsf_curvature_band(const double *phi, const int32_t *mask, double *kappa, do
 int lsf_curvature_band_device(const double *d_phi, const int32_t *d_mask, double *d_kappa, double *d_gauss, double *d_gmag, int nx,
                               int ny, int nz, double dx, double clamp, int64_t info[LSF_CURV_INFO_LEN], double *kappa_max,
                               void *stream);
+
+/* ---- the band time loop with a curvature term: F = a - b*kappa run inside lsf_evolve_band's loop ----------
+ * No reference counterpart.  lsf_evolve_band freezes `speed` for a call, and a kappa handed in through `speed` is upwinded; motion
+ * by mean curvature needs kappa*|grad(phi)| differenced centrally from every stage's own input field.  This call is lsf_evolve_band
+ * with that term in the stage.  EVERYTHING NOT NAMED HERE IS lsf_evolve_band'S CONTRACT, word for word: the list, the step order, the
+ * check, the open-edge rule, the rebuild, the outputs, info, margin, the empty list, steps = 0, the seams and LSF_ERR_NAN.
+ *   equation phi_t + u . grad(phi) + F |grad(phi)| = bcurv * kappa * |grad(phi)|.  A sphere with phi < 0 inside has kappa = +2/r
+ *            and shrinks: its radius is sqrt(R0^2 - 4*bcurv*t).
+ *   stage    S(a) at a list cell, a being the stage's input field:
+ *              t0 = a - dt*R0     R0 = T, N or T + N exactly as in lsf_advect_field_band (joint WENO rule, STRICT and FAST
+ *                                 unchanged); with neither a velocity nor a speed t0 = a
+ *              C  = bcurv * (H * g)   H and g of lsf_curvature_band's statement evaluated on a at the cell: the 19 values, px ... pyz,
+ *                                 g2, g = sqrt(g2), num, mix, H = (num - 2.*mix)/(g2*g); DEGENERATE (g2 < 1e-24) gives H = 0.0; CLAMP
+ *                                 with lim = clamp / dx, computed once on the host, is applied to H by the same comparisons
+ *                                 (clamp == 0: none).  One rule for every interior cell, no first-order variant.
+ *              t  = t0 + dt*C
+ *            The RK3 / Euler blends are those of lsf_advect_field_band with this S.
+ *   mode     STRICT evaluates as written, left to right, without contraction; / and sqrt are the IEEE ones.  FAST keeps R0 in the
+ *            existing FAST arithmetic; C is computed uncontracted in FAST too (one arithmetic for the term) and enters as
+ *            fma(dt, C, t0).
+ *   inputs   u, v, w come together or all NULL and speed is optional, as before; BOTH groups may be absent when bcurv > 0 (pure
+ *            curvature flow).  cfl is lsf_evolve_band's, and 0 when both groups are absent.
+ *   diffusion  (may be NULL) (bcurv*dt)/(dx*dx), computed once on the host: reported, never judged; written wherever cfl is.
+ *   bcurv==0 with a velocity or a speed: the stage kernel of lsf_evolve_band is launched, every output equals that call's bit for
+ *            bit, clamp is ignored and diffusion = 0.
+ *   errors   those of lsf_evolve_band, and LSF_ERR_INVALID before anything is written for: bcurv not finite or < 0; bcurv == 0 with
+ *            neither a velocity nor a speed; clamp not finite or < 0.
+ *   result   with LSF_ARITH_STRICT phi, mask, trace, cfl, diffusion, info and margin are those of the serial statement
+ *            tests/evolve_band_curv_ref.py bit for bit, on both seams.
+ *   seams    phi, mask and the inputs go through exactly the twins lsf_evolve_band uses (one staging function serves both calls).
+ * Guidance: the term is explicit.  The explicit bound of the linear 3-D heat stencil is diffusion <= 1/6 for Euler; RK3 reaches
+ * further.  The sweeps keep |grad(phi)| = 1 near the surface, where the term is bcurv*kappa; at the kinks of a distance (medial axis,
+ * the +-far plateau) kappa is large and meaningless: clamp = 1 bounds it at 1/dx.  Serial statement, a sphere of radius 0.6 on 33^3
+ * points over [-1.5,1.5]^3, the distance clamped to +-6 dx, mask |phi| < 6 dx, core = 3, ring = 3, 2 sweeps, h = 0.5 dx, bcurv = 1,
+ * clamp = 1, RK3, no velocity and no speed, the radius read off the +x axis by linear interpolation against sqrt(R0^2 - 4*b*t):
+ * t = 0.04 in 30 steps (diffusion 0.152): off by 0.012 dx, no rebuild; in 11 steps (0.414): 0.001 dx, and with Euler 0.061 dx;
+ * t = 0.07 in 53 steps (0.150): one rebuild (after step 41), no flips, 0.048 dx (tests/test_evolve_band_curv_cpu.py asserts twice
+ * that); with the term left out the same run stays 3.4 dx from the closed form.
+ * Work: that of lsf_evolve_band; a stage gathers 31 values instead of 19 where a velocity or a speed is present (19 without).
+ * Measured on one MI355X (profiles/evolve_band_curv_time.txt, made by profiles/micro/evolve_band_curv_time.py: the sphere, mask, velocity
+ * and speed of lsf_evolve_band's measurement, RK3, STRICT, 2 sweeps, 20 steps, diffusion 0.15, ms per step): 0.17 at 256^3 and 0.44 at
+ * 512^3, against 0.14 and 0.39 for lsf_evolve_band on the same inputs and 0.93 and 3.50 for the loop of public calls it replaces (per
+ * step lsf_curvature_band, speed = a - b*kappa, lsf_evolve_band(steps = 1)); no rebuild in those runs.  No speed is claimed beyond
+ * that record.
+ * Out of scope: the term in lsf_advect_field / lsf_advect_field_band, a cutoff of the term towards the list's edge, implicit or
+ * semi-implicit time stepping, a dt chosen from diffusion, anisotropic or Gaussian-curvature laws, fp32, multi-GPU (DESIGN.md
+ * section 8). */
+int lsf_evolve_band_curv(double *phi, int32_t *mask, const double *u, const double *v, const double *w, const double *speed, int nx,
+                         int ny, int nz, double dx, double dt, int steps, int scheme, int mode, double core, int ring,
+                         int reinit_sweeps, double h, int check_every, double bcurv, double clamp, int *steps_done, double *cfl,
+                         double *diffusion, double *change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN], double *margin);
+int lsf_evolve_band_curv_device(double *d_phi, int32_t *d_mask, const double *d_u, const double *d_v, const double *d_w,
+                                const double *d_speed, int nx, int ny, int nz, double dx, double dt, int steps, int scheme, int mode,
+                                double core, int ring, int reinit_sweeps, double h, int check_every, double bcurv, double clamp,
+                                int *steps_done, double *cfl, double *diffusion, double *change_trace, int trace_cap,
+                                int64_t info[LSF_EVOLVE_INFO_LEN], double *margin, void *stream);
 
 /* ---- extension on a cell list: a quantity carried off the frozen cells of a caller's mask, constant along the normals ----------
  * No reference counterpart.  lsf_extend_field on the list of lsf_reinit_band: what carries a speed known on or next to the surface
@@ -808,7 +864,7 @@ int lsf_mirror_sync(void *host);
  * copied to the host.  What becomes of the twins it touched depends on how far the call came:
  *   - a call refused before it wrote anything keeps them as they were, an un-synced earlier result included, which a later
  *     lsf_mirror_sync still brings home: every LSF_ERR_INVALID of lsf_advect_field, lsf_advect_field_band, lsf_evolve_band,
- *     lsf_curvature_band, lsf_extend_field, lsf_extend_field_band and lsf_extract_surface (argument checks and the checks of
+ *     lsf_evolve_band_curv, lsf_curvature_band, lsf_extend_field, lsf_extend_field_band and lsf_extract_surface (argument checks and the checks of
  *     u, v, w, speed, q and the list alike: all are made before phi or the mask is written), and the argument checks of
  *     every other call, which come before the twins are looked at;
  *   - any other failure -- LSF_ERR_HIP anywhere, and an error that lsf_reinit, lsf_minmax, lsf_reinit_band or

@@ -116,6 +116,12 @@ SIGNATURES = {
     "lsf_evolve_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int,
                                        c_int, c_int, c_double, c_int, c_int, c_double, c_int, POINTER(c_int), POINTER(c_double), c_void_p, c_int,
                                        c_void_p, POINTER(c_double), c_void_p]),
+    "lsf_evolve_band_curv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int,
+                                     c_int, c_int, c_double, c_int, c_int, c_double, c_int, c_double, c_double, POINTER(c_int), POINTER(c_double),
+                                     POINTER(c_double), c_void_p, c_int, c_void_p, POINTER(c_double)]),
+    "lsf_evolve_band_curv_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double,
+                                            c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_int, c_double, c_double, POINTER(c_int),
+                                            POINTER(c_double), POINTER(c_double), c_void_p, c_int, c_void_p, POINTER(c_double), c_void_p]),
     "lsf_extract_surface": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, POINTER(c_int), POINTER(c_int), c_void_p]),
     "lsf_extract_surface_device": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, POINTER(c_int), POINTER(c_int), c_void_p,
                                            c_void_p]),

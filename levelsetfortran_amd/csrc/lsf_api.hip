@@ -31,6 +31,7 @@
 #include "lsf_advect_band.hpp"
 #include "lsf_evolve_band.hpp"
 #include "lsf_curvature_band.hpp"
+#include "lsf_evolve_band_curv.hpp"
 #include "lsf_extend_band.hpp"
 #include "lsf_extract_surface.hpp"
 
@@ -1586,26 +1587,16 @@ int lsf_advect_field_band(double* phi, const int32_t* mask, const double* u, con
     return rc;
 }
 
-int lsf_evolve_band_device(double* d_phi, int32_t* d_mask, const double* d_u, const double* d_v, const double* d_w, const double* d_speed, int nx,
-                           int ny, int nz, double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h,
-                           int check_every, int* steps_done, double* cfl, double* change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN],
-                           double* margin, void* stream)
+// the host seam of lsf_evolve_band and lsf_evolve_band_curv: the staging of the inputs, the twins of phi and the mask, the call, the way home
+static int evolve_band_host(double* phi, int32_t* mask, const double* u, const double* v, const double* w, const double* speed, int nx, int ny,
+                            int nz, double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h,
+                            int check_every, double bcurv, double clamp, int* steps_done, double* cfl, double* diffusion, double* change_trace,
+                            int trace_cap, int64_t* info, double* margin)
 {
-    Trace trace_("lsf_evolve_band_device");
     int rc = ensure_device();
     if (rc) return rc;
-    return evolve_band_core(d_phi, d_mask, d_u, d_v, d_w, d_speed, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h, check_every,
-                            steps_done, cfl, change_trace, trace_cap, info, margin, (hipStream_t)stream);
-}
-
-int lsf_evolve_band(double* phi, int32_t* mask, const double* u, const double* v, const double* w, const double* speed, int nx, int ny, int nz,
-                    double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h, int check_every,
-                    int* steps_done, double* cfl, double* change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN], double* margin)
-{
-    Trace trace_("lsf_evolve_band");
-    int rc = ensure_device();
-    if (rc) return rc;
-    if ((rc = evolve_band_args_ok(phi, mask, u, v, w, speed, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h, check_every)))
+    if ((rc = evolve_band_args_ok(phi, mask, u, v, w, speed, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h, check_every,
+                                  bcurv, clamp)))
         return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
@@ -1629,7 +1620,8 @@ int lsf_evolve_band(double* phi, int32_t* mask, const double* u, const double* v
     const Slot sm = is_nb ? S_HNB : S_HSB;
     if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
     rc = evolve_band_core((double*)c.slot[S_HPHI].p, (int32_t*)c.slot[sm].p, d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, steps, scheme,
-                          mode, core, ring, reinit_sweeps, h, check_every, steps_done, cfl, change_trace, trace_cap, info, margin, nullptr);
+                          mode, core, ring, reinit_sweeps, h, check_every, bcurv, clamp, steps_done, cfl, diffusion, change_trace, trace_cap, info,
+                          margin, nullptr);
     if (rc == LSF_OK || rc == LSF_ERR_NAN) {
         const std::string keep = g_err;
         int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
@@ -1639,6 +1631,50 @@ int lsf_evolve_band(double* phi, int32_t* mask, const double* u, const double* v
     } else if (rc != LSF_ERR_INVALID) // (an invalid call is found before the twins are written: they stay what they were)
         twin_drop(c.twin_phi), twin_drop(tm);
     return rc;
+}
+
+int lsf_evolve_band_device(double* d_phi, int32_t* d_mask, const double* d_u, const double* d_v, const double* d_w, const double* d_speed, int nx,
+                           int ny, int nz, double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h,
+                           int check_every, int* steps_done, double* cfl, double* change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN],
+                           double* margin, void* stream)
+{
+    Trace trace_("lsf_evolve_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    return evolve_band_core(d_phi, d_mask, d_u, d_v, d_w, d_speed, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h, check_every,
+                            0.0, 0.0, steps_done, cfl, nullptr, change_trace, trace_cap, info, margin, (hipStream_t)stream);
+}
+
+int lsf_evolve_band(double* phi, int32_t* mask, const double* u, const double* v, const double* w, const double* speed, int nx, int ny, int nz,
+                    double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h, int check_every,
+                    int* steps_done, double* cfl, double* change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN], double* margin)
+{
+    Trace trace_("lsf_evolve_band");
+    return evolve_band_host(phi, mask, u, v, w, speed, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h, check_every, 0.0, 0.0,
+                            steps_done, cfl, nullptr, change_trace, trace_cap, info, margin);
+}
+
+int lsf_evolve_band_curv_device(double* d_phi, int32_t* d_mask, const double* d_u, const double* d_v, const double* d_w, const double* d_speed,
+                                int nx, int ny, int nz, double dx, double dt, int steps, int scheme, int mode, double core, int ring,
+                                int reinit_sweeps, double h, int check_every, double bcurv, double clamp, int* steps_done, double* cfl,
+                                double* diffusion, double* change_trace, int trace_cap, int64_t info[LSF_EVOLVE_INFO_LEN], double* margin,
+                                void* stream)
+{
+    Trace trace_("lsf_evolve_band_curv_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    return evolve_band_core(d_phi, d_mask, d_u, d_v, d_w, d_speed, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h, check_every,
+                            bcurv, clamp, steps_done, cfl, diffusion, change_trace, trace_cap, info, margin, (hipStream_t)stream);
+}
+
+int lsf_evolve_band_curv(double* phi, int32_t* mask, const double* u, const double* v, const double* w, const double* speed, int nx, int ny, int nz,
+                         double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h, int check_every,
+                         double bcurv, double clamp, int* steps_done, double* cfl, double* diffusion, double* change_trace, int trace_cap,
+                         int64_t info[LSF_EVOLVE_INFO_LEN], double* margin)
+{
+    Trace trace_("lsf_evolve_band_curv");
+    return evolve_band_host(phi, mask, u, v, w, speed, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h, check_every, bcurv,
+                            clamp, steps_done, cfl, diffusion, change_trace, trace_cap, info, margin);
 }
 
 int lsf_curvature_band_device(const double* d_phi, const int32_t* d_mask, double* d_kappa, double* d_gauss, double* d_gmag, int nx, int ny, int nz,

@@ -31,6 +31,44 @@ namespace lsf {
 constexpr double CURV_DEGENERATE_G2 = 1e-24; // g2 below this: a flat spot, H = K = 0
 constexpr int CURV_NPART = 4;                // partials per block: degenerate, clamped, non-finite, max |kappa| (bits)
 
+// The nine derivatives of the header's statement at one interior point q: second-order central differences of the 19 values
+// s(a, b, c), evaluated as written, without contraction.  Shared with k_advect_band_curv_stage (lsf_evolve_band_curv.hpp).
+struct CurvD {
+    double px, py, pz, pxx, pyy, pzz, pxy, pxz, pyz;
+};
+
+__device__ __forceinline__ CurvD curv_derivs(const double* __restrict__ q, long rs, long ps, double two_dx, double dx2, double four_dx2)
+{
+#pragma clang fp contract(off)
+    // s(a, b, c) of the header: an interior point, so +-1 on every axis lies inside the field
+    const double c = q[0];
+    const double xm = q[-1], xp = q[1], ym = q[-rs], yp = q[rs], zm = q[-ps], zp = q[ps];
+    const double xpyp = q[1 + rs], xpym = q[1 - rs], xmyp = q[-1 + rs], xmym = q[-1 - rs];
+    const double xpzp = q[1 + ps], xpzm = q[1 - ps], xmzp = q[-1 + ps], xmzm = q[-1 - ps];
+    const double ypzp = q[rs + ps], ypzm = q[rs - ps], ymzp = q[-rs + ps], ymzm = q[-rs - ps];
+    CurvD d;
+    d.px = (xp - xm) / two_dx, d.py = (yp - ym) / two_dx, d.pz = (zp - zm) / two_dx;
+    d.pxx = ((xp - 2. * c) + xm) / dx2, d.pyy = ((yp - 2. * c) + ym) / dx2, d.pzz = ((zp - 2. * c) + zm) / dx2;
+    d.pxy = (((xpyp - xpym) - xmyp) + xmym) / four_dx2;
+    d.pxz = (((xpzp - xpzm) - xmzp) + xmzm) / four_dx2;
+    d.pyz = (((ypzp - ypzm) - ymzp) + ymzm) / four_dx2;
+    return d;
+}
+
+// H of the statement before the clamp, with g2, g = sqrt(g2) and the DEGENERATE flag (then H = 0.0)
+__device__ __forceinline__ double curv_mean(const CurvD& d, double& g2, double& g, bool& deg)
+{
+#pragma clang fp contract(off)
+    const double px = d.px, py = d.py, pz = d.pz, pxx = d.pxx, pyy = d.pyy, pzz = d.pzz;
+    g2 = (px * px + py * py) + pz * pz;
+    g = __builtin_sqrt(g2);
+    deg = g2 < CURV_DEGENERATE_G2; // a NaN g2 is not degenerate
+    const double num = ((px * px) * (pyy + pzz) + (py * py) * (pxx + pzz)) + (pz * pz) * (pxx + pyy);
+    const double mix = ((px * py) * d.pxy + (px * pz) * d.pxz) + (py * pz) * d.pyz;
+    const double H = (num - 2. * mix) / (g2 * g);
+    return deg ? 0.0 : H;
+}
+
 // List cell e of chunk blockIdx.x.  two_dx = 2.*dx, dx2 = dx*dx, four_dx2 = 4.*(dx*dx), computed once on the host; lim = clamp / dx
 // and lim2 = lim*lim likewise, used when CLAMP.  part: CURV_NPART words per block.
 template <bool HASK, bool HASG, bool CLAMP>
@@ -46,25 +84,10 @@ __global__ __launch_bounds__(MB_CH) void k_curvature_band(const double* __restri
     if (e < nL) {
         const unsigned p = (unsigned)L[e];
         const long rs = nx + 1, ps = (long)(nx + 1) * (ny + 1);
-        const double* q = phi + p;
-        // s(a, b, c) of the header: an interior point, so +-1 on every axis lies inside the field
-        const double c = q[0];
-        const double xm = q[-1], xp = q[1], ym = q[-rs], yp = q[rs], zm = q[-ps], zp = q[ps];
-        const double xpyp = q[1 + rs], xpym = q[1 - rs], xmyp = q[-1 + rs], xmym = q[-1 - rs];
-        const double xpzp = q[1 + ps], xpzm = q[1 - ps], xmzp = q[-1 + ps], xmzm = q[-1 - ps];
-        const double ypzp = q[rs + ps], ypzm = q[rs - ps], ymzp = q[-rs + ps], ymzm = q[-rs - ps];
-        const double px = (xp - xm) / two_dx, py = (yp - ym) / two_dx, pz = (zp - zm) / two_dx;
-        const double pxx = ((xp - 2. * c) + xm) / dx2, pyy = ((yp - 2. * c) + ym) / dx2, pzz = ((zp - 2. * c) + zm) / dx2;
-        const double pxy = (((xpyp - xpym) - xmyp) + xmym) / four_dx2;
-        const double pxz = (((xpzp - xpzm) - xmzp) + xmzm) / four_dx2;
-        const double pyz = (((ypzp - ypzm) - ymzp) + ymzm) / four_dx2;
-        const double g2 = (px * px + py * py) + pz * pz;
-        const double g = __builtin_sqrt(g2);
-        const bool deg = g2 < CURV_DEGENERATE_G2; // a NaN g2 is not degenerate
-        const double num = ((px * px) * (pyy + pzz) + (py * py) * (pxx + pzz)) + (pz * pz) * (pxx + pyy);
-        const double mix = ((px * py) * pxy + (px * pz) * pxz) + (py * pz) * pyz;
-        double H = (num - 2. * mix) / (g2 * g);
-        if (deg) H = 0.0;
+        bool deg;
+        double g2, g;
+        const CurvD d = curv_derivs(phi + p, rs, ps, two_dx, dx2, four_dx2);
+        double H = curv_mean(d, g2, g, deg);
         bool clamped = false;
         if constexpr (CLAMP) {
             clamped = H > lim || H < -lim;
@@ -74,6 +97,7 @@ __global__ __launch_bounds__(MB_CH) void k_curvature_band(const double* __restri
         bool bad = !__builtin_isfinite(H);
         kappa[p] = H;
         if constexpr (HASK) {
+            const double px = d.px, py = d.py, pz = d.pz, pxx = d.pxx, pyy = d.pyy, pzz = d.pzz, pxy = d.pxy, pxz = d.pxz, pyz = d.pyz;
             const double A = ((px * px) * (pyy * pzz - pyz * pyz) + (py * py) * (pxx * pzz - pxz * pxz)) + (pz * pz) * (pxx * pyy - pxy * pxy);
             const double B = ((px * py) * (pxz * pyz - pxy * pzz) + (py * pz) * (pxy * pxz - pyz * pxx)) + (px * pz) * (pxy * pyz - pxz * pyy);
             double K = (A + 2. * B) / (g2 * g2);

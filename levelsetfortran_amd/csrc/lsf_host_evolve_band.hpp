@@ -1,14 +1,46 @@
-// lsf_host_evolve_band.hpp -- host side of lsf_evolve_band (kernels and design: lsf_evolve_band.hpp): validation, the scan of the
+// lsf_host_evolve_band.hpp -- host side of lsf_evolve_band and lsf_evolve_band_curv (kernels and design: lsf_evolve_band.hpp; the
+// stage with the curvature term: lsf_evolve_band_curv.hpp; lsf_evolve_band is bcurv = clamp = 0): validation, the scan of the
 // inputs over all points, the first list, the steps (stages and sweeps enqueued on the resident list), the checks (one 64-byte
 // record read per check) and the rebuilds.  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
 
-// what can be decided without the device
+// one stage launch over the list with the curvature term: the instance for the arithmetic and the terms present
+void advect_band_curv_stage_launch(bool strict, const double* A, double* B, const double* P0, const double* d_u, const double* d_v,
+                                   const double* d_w, const double* d_f, const int* L, int nL, int nchunks, int nx, int ny, int nz, double dx,
+                                   double dt, double c_old, double c_new, double bcurv, double lim, unsigned long long* part, const int* ctl,
+                                   hipStream_t st)
+{
+    const dim3 grid((unsigned)nchunks), blk(MB_CH);
+    const double two_dx = 2. * dx, dx2 = dx * dx, four_dx2 = 4. * dx2;
+#define LSF_ADVC_CALL(S, HV, HF)                                                                                                                  \
+    hipLaunchKernelGGL((k_advect_band_curv_stage<S, HV, HF>), grid, blk, 0, st, A, B, P0, d_u, d_v, d_w, d_f, L, nL, nx, ny, nz, dx, dt, c_old, \
+                       c_new, bcurv, two_dx, dx2, four_dx2, lim, part, ctl)
+    const bool hv = d_u != nullptr, hf = d_f != nullptr;
+    if (strict) {
+        if (hv && hf) LSF_ADVC_CALL(true, true, true);
+        else if (hv) LSF_ADVC_CALL(true, true, false);
+        else if (hf) LSF_ADVC_CALL(true, false, true);
+        else LSF_ADVC_CALL(true, false, false);
+    } else {
+        if (hv && hf) LSF_ADVC_CALL(false, true, true);
+        else if (hv) LSF_ADVC_CALL(false, true, false);
+        else if (hf) LSF_ADVC_CALL(false, false, true);
+        else LSF_ADVC_CALL(false, false, false);
+    }
+#undef LSF_ADVC_CALL
+}
+
+// what can be decided without the device (lsf_evolve_band: bcurv = clamp = 0)
 int evolve_band_args_ok(const void* phi, const void* mask, const void* u, const void* v, const void* w, const void* speed, int nx, int ny, int nz,
-                        double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h, int check_every)
+                        double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h, int check_every,
+                        double bcurv, double clamp)
 {
     int rc;
-    if ((rc = advect_field_args_ok(phi, u, v, w, speed, nx, ny, nz, dx, dt, steps, scheme, mode))) return rc;
+    if (!(bcurv >= 0.0) || !std::isfinite(bcurv)) return fail(LSF_ERR_INVALID, "lsf_evolve_band_curv: bcurv must be finite and >= 0");
+    if (!(clamp >= 0.0) || !std::isfinite(clamp)) return fail(LSF_ERR_INVALID, "lsf_evolve_band_curv: clamp must be finite and >= 0 (0: no clamp)");
+    // with bcurv > 0 the term moves the surface and both input groups may be absent: that check alone is answered here
+    const bool none = !u && !v && !w && !speed;
+    if ((rc = advect_field_args_ok(phi, u, v, w, none && bcurv > 0.0 ? phi : speed, nx, ny, nz, dx, dt, steps, scheme, mode))) return rc;
     if (!mask) return fail(LSF_ERR_INVALID, "lsf_evolve_band: mask is NULL");
     if (!(core > 0.0) || !std::isfinite(core)) return fail(LSF_ERR_INVALID, "lsf_evolve_band: core must be finite and > 0");
     if (ring < 1 || ring > 8) return fail(LSF_ERR_INVALID, "lsf_evolve_band: ring must be in 1..8");
@@ -22,15 +54,17 @@ int evolve_band_args_ok(const void* phi, const void* mask, const void* u, const 
 // LSF_OK only; phi and the mask on LSF_OK and LSF_ERR_NAN.
 int evolve_band_core(double* d_phi, int32_t* d_mask, const double* d_u, const double* d_v, const double* d_w, const double* d_f, int nx, int ny,
                      int nz, double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h,
-                     int check_every, int* steps_done, double* cfl, double* change_trace, int trace_cap, int64_t* info, double* margin,
-                     hipStream_t st)
+                     int check_every, double bcurv, double clamp, int* steps_done, double* cfl, double* diffusion, double* change_trace,
+                     int trace_cap, int64_t* info, double* margin, hipStream_t st)
 {
     int rc;
     if ((rc = evolve_band_args_ok(d_phi, d_mask, d_u, d_v, d_w, d_f, nx, ny, nz, dx, dt, steps, scheme, mode, core, ring, reinit_sweeps, h,
-                                  check_every)))
+                                  check_every, bcurv, clamp)))
         return rc;
-    double cfl_all = 0.0;
-    if ((rc = advect_field_scan(d_u, d_v, d_w, d_f, nx, ny, nz, dx, dt, &cfl_all, st))) return rc;
+    double cfl_all = 0.0; // stays 0 without a velocity and a speed: nothing to scan
+    if ((d_u || d_f) && (rc = advect_field_scan(d_u, d_v, d_w, d_f, nx, ny, nz, dx, dt, &cfl_all, st))) return rc;
+    const double diff = (bcurv * dt) / (dx * dx);                   // reported, never judged
+    const double lim = clamp != 0.0 ? clamp / dx : HUGE_VAL; // no clamp: a bound that no H exceeds
     Ctx& c = ctx();
     const bool strict = (mode & LSF_ARITH_STRICT) != 0, rk3 = scheme == LSF_ADVECT_RK3;
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
@@ -42,6 +76,7 @@ int evolve_band_core(double* d_phi, int32_t* d_mask, const double* d_u, const do
         HIPCHK(hipStreamSynchronize(st));
         if (steps_done) *steps_done = 0;
         if (cfl) *cfl = 0.0;
+        if (diffusion) *diffusion = diff;
         if (info)
             for (int q = 0; q < LSF_EVOLVE_INFO_LEN; ++q) info[q] = 0;
         if (margin) *margin = HUGE_VAL;
@@ -81,6 +116,7 @@ int evolve_band_core(double* d_phi, int32_t* d_mask, const double* d_u, const do
 
     // from here on phi and the mask are written
     if (cfl) *cfl = cfl_all;
+    if (diffusion) *diffusion = diff;
     if (steps_done) *steps_done = 0;
     HIPCHK(hipMemsetAsync(d_mask, 0, n * sizeof(int32_t), st));
     HIPCHK(hipMemsetAsync(rec, 0, EVB_R_WORDS * sizeof(unsigned long long), st));
@@ -129,8 +165,12 @@ int evolve_band_core(double* d_phi, int32_t* d_mask, const double* d_u, const do
         HIPCHK(hipMemcpyAsync(w1, d_phi, n * sizeof(double), hipMemcpyDeviceToDevice, st));
         if (rk3) HIPCHK(hipMemcpyAsync(w2, d_phi, n * sizeof(double), hipMemcpyDeviceToDevice, st));
         auto stage = [&](const double* A, double* B, const double* P0, double c_old, double c_new, bool last) {
-            advect_band_stage_launch(strict, A, B, P0, d_u, d_v, d_w, d_f, L, nL, nchunks, nx, ny, nz, dx, dt, c_old, c_new, last ? part : nullptr, ctl,
-                                     st);
+            if (bcurv == 0.0) // lsf_evolve_band's stage kernel, bit for bit
+                advect_band_stage_launch(strict, A, B, P0, d_u, d_v, d_w, d_f, L, nL, nchunks, nx, ny, nz, dx, dt, c_old, c_new, last ? part : nullptr,
+                                         ctl, st);
+            else
+                advect_band_curv_stage_launch(strict, A, B, P0, d_u, d_v, d_w, d_f, L, nL, nchunks, nx, ny, nz, dx, dt, c_old, c_new, bcurv, lim,
+                                              last ? part : nullptr, ctl, st);
         };
         for (int s = 0; s < steps; ++s) {
             const dim3 gl((unsigned)nchunks);

@@ -28,6 +28,9 @@
 !   evolveBand(phi,mask,u,v,w,nx,ny,nz,dx,dt,steps)      no reference counterpart: the band time loop -- transport, two sweeps of
 !                                                        the reinitialisation and the list following the surface; phi and mask
 !                                                        are both updated (include/lsf.h: lsf_evolve_band)
+!   evolveBandCurv(phi,mask,speed,nx,ny,nz,dx,dt,steps,b) no reference counterpart: evolveBand for the speed law F = speed - b*kappa,
+!                                                        the curvature term differenced centrally inside the stages
+!                                                        (include/lsf.h: lsf_evolve_band_curv)
 !   curvatureBand(phi,mask,kappa,nx,ny,nz,dx,clamp)      the reference's own is commented out (subs.f90:426-448): the mean
 !                                                        curvature div(grad(phi)/|grad(phi)|) on the cells with mask == 1
 !                                                        only (include/lsf.h: lsf_curvature_band)
@@ -102,6 +105,7 @@ PUBLIC :: extendField
 PUBLIC :: advectField
 PUBLIC :: advectFieldBand
 PUBLIC :: evolveBand
+PUBLIC :: evolveBandCurv
 PUBLIC :: curvatureBand
 PUBLIC :: extendFieldBand
 PUBLIC :: extractSurface, stlWrite
@@ -281,6 +285,25 @@ INTERFACE
       REAL(c_double), INTENT(OUT) :: margin
       INTEGER(c_int) :: rc
    END FUNCTION lsf_evolve_band
+   ! int lsf_evolve_band_curv(double*,int32_t*,const double*,const double*,const double*,const double*,int,int,int,double,double,int,int,
+   !                          int,double,int,int,double,int,double,double,int*,double*,double*,double*,int,int64_t[6],double*)
+   FUNCTION lsf_evolve_band_curv(phi,mask,u,v,w,speed,nx,ny,nz,dx,dt,steps,scheme,mode,core,ring,reinit_sweeps,h,check_every, &
+                                 bcurv,clamp,steps_done,cfl,diffusion,change_trace,trace_cap,info,margin) &
+            BIND(C,NAME='lsf_evolve_band_curv') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(INOUT) :: phi(*)
+      INTEGER(c_int), INTENT(INOUT) :: mask(*)
+      TYPE(c_ptr), VALUE :: u,v,w            ! NULL: no velocity
+      REAL(c_double), INTENT(IN) :: speed(*)
+      INTEGER(c_int), VALUE :: nx,ny,nz,steps,scheme,mode,ring,reinit_sweeps,check_every,trace_cap
+      REAL(c_double), VALUE :: dx,dt,core,h,bcurv,clamp
+      INTEGER(c_int), INTENT(OUT) :: steps_done
+      REAL(c_double), INTENT(OUT) :: cfl,diffusion
+      REAL(c_double), INTENT(OUT) :: change_trace(*)
+      INTEGER(c_int64_t), INTENT(OUT) :: info(6)
+      REAL(c_double), INTENT(OUT) :: margin
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_evolve_band_curv
    ! int lsf_curvature_band(const double*,const int32_t*,double*,double*,double*,int,int,int,double,double,int64_t[4],double*)
    FUNCTION lsf_curvature_band(phi,mask,kappa,gauss,gmag,nx,ny,nz,dx,clamp,info,kappa_max) &
             BIND(C,NAME='lsf_curvature_band') RESULT(rc)
@@ -906,6 +929,50 @@ IF (rc == LSF_ERR_NAN) STOP
 DEALLOCATE(trace)
 
 END SUBROUTINE evolveBand
+
+!*************************************************************************************!
+! The band time loop with a curvature term (include/lsf.h: lsf_evolve_band_curv; no
+! reference counterpart): evolveBand for phi_t + speed |grad(phi)| = b kappa |grad(phi)|,
+! the speed law F = speed - b*kappa with the curvature term differenced centrally from
+! every stage's own field.  No velocity, |kappa| limited to 1/dx (clamp 1), everything else
+! evolveBand's defaults: RK3, two sweeps with pseudo-time step 0.5 dx, core 3, ring 3, a
+! check after every step.  phi AND mask are updated; speed must be finite at all points.
+! Prints evolveBand's lines with the number b dt/dx^2 of the explicit term after the CFL
+! number.  A NaN stops the run like advectField.
+!*************************************************************************************!
+SUBROUTINE evolveBandCurv(phi,mask,speed,nx,ny,nz,dx,dt,steps,b)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,steps
+REAL,INTENT(IN) :: dx,dt,b
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: mask
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: speed
+INTEGER(c_int), PARAMETER :: LSF_ADVECT_RK3 = 0
+REAL,ALLOCATABLE :: trace(:)
+REAL :: cfl,diffusion,margin
+INTEGER(c_int64_t) :: info(6)
+INTEGER(c_int) :: rc,done,mode
+
+ALLOCATE(trace(MAX(steps,1)))
+trace = 0.
+cfl = 0.
+diffusion = 0.
+margin = 0.
+info = 0
+done = 0
+CALL lsf_set_mirror()
+mode = IOR(LSF_ARITH_STRICT,LSF_ORDER_JACOBI)
+rc = lsf_evolve_band_curv(phi,mask,c_null_ptr,c_null_ptr,c_null_ptr,speed,nx,ny,nz,dx,dt,steps,LSF_ADVECT_RK3,mode,3.0_c_double,3,2, &
+                          0.5_c_double*dx,1,b,1.0_c_double,done,cfl,diffusion,trace,MAX(steps,1),info,margin)
+IF (rc /= LSF_OK .AND. rc /= LSF_ERR_NAN) CALL lsf_fail('lsf_evolve_band_curv',rc)
+PRINT*, " Band time loop: ",done," of ",steps," steps, CFL ",cfl,", b dt/dx^2 ",diffusion,", last change ",trace(MAX(done,1))
+IF (rc == LSF_OK) PRINT*, "   list cells ",info(1),", open-edge cells ",info(2),", sign flips ",info(3),", rebuilds ",info(4), &
+                          ", entered ",info(5),", near a wall ",info(6),", margin/dx ",margin/dx
+PRINT*
+IF (rc == LSF_ERR_NAN) STOP
+DEALLOCATE(trace)
+
+END SUBROUTINE evolveBandCurv
 
 !*************************************************************************************!
 ! Mean curvature of the level sets on the cells of a mask only (include/lsf.h:

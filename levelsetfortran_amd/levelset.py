@@ -24,6 +24,7 @@ and the transport of lsf_advect_field on the cells of a mask only (no reference 
 
   advectFieldBand(phi, mask, nx, ny, nz, dx, dt, steps, ...)    include/lsf.h: lsf_advect_field_band
   evolveBand(phi, mask, nx, ny, nz, dx, dt, steps, ...)         include/lsf.h: lsf_evolve_band
+  evolveBandCurv(phi, mask, nx, ny, nz, dx, dt, steps, curvature=b, ...)  include/lsf.h: lsf_evolve_band_curv
 
 and the mean and Gaussian curvature of the level sets on the cells of a mask (the reference's own is commented out, subs.f90:426-448):
 
@@ -55,7 +56,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -732,11 +733,24 @@ def evolveBand(phi, mask, nx: int, ny: int, nz: int, dx: float, dt: float, steps
     call ended early (`steps` < the steps asked for).  Raises LsfNaNError when a step produced a NaN (phi holds that step; the
     exception carries the EvolveBandReport as `.report`).
     """
+    return _evolve_band(phi, mask, nx, ny, nz, dx, dt, steps, velocity, speed, scheme, arith, core, ring, reinit_sweeps, h, check_every, None)
+
+
+def _evolve_band(phi, mask, nx, ny, nz, dx, dt, steps, velocity, speed, scheme, arith, core, ring, reinit_sweeps, h, check_every, curv):
+    """evolveBand (curv is None) and evolveBandCurv (curv = (curvature, clamp)): validation, the pointers, the call, the report"""
     if scheme not in ("rk3", "euler"):
         raise ValueError("scheme must be 'rk3' or 'euler'")
     if arith not in ("strict", "fast"):
         raise ValueError("arith must be 'strict' or 'fast'")
-    if velocity is None and speed is None:
+    if curv is not None:
+        bcurv, clamp = (float(x) for x in curv)
+        if not (bcurv >= 0.0) or bcurv == float("inf"):
+            raise ValueError("curvature must be finite and >= 0")
+        if not (clamp >= 0.0) or clamp == float("inf"):
+            raise ValueError("clamp must be finite and >= 0 (0: no clamp)")
+        if velocity is None and speed is None and bcurv == 0.0:
+            raise ValueError("give velocity=(u, v, w), speed=F, a curvature > 0, or several of them")
+    elif velocity is None and speed is None:
         raise ValueError("give velocity=(u, v, w), speed=F, or both")
     if velocity is not None:
         if not isinstance(velocity, (tuple, list)) or len(velocity) != 3 or any(c is None for c in velocity):
@@ -778,24 +792,61 @@ def evolveBand(phi, mask, nx: int, ny: int, nz: int, dx: float, dt: float, steps
     p = ptr(phi, "phi")
     q = {n: ptr(f, n) for n, f in inputs}
     lib = _lib.load()
-    tail = (m, q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps),
+    diffusion = ctypes.c_double(0.0)
+    head = (p, m, q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps),
             {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}[scheme], mode_word("jacobi", arith), float(core), int(ring),
-            int(reinit_sweeps), float(h), int(check_every), ctypes.byref(done), ctypes.byref(cfl), trace.ctypes.data, cap, info.ctypes.data,
-            ctypes.byref(margin))
-    if dev:
-        rc = lib.lsf_evolve_band_device(p, *tail, _stream_and_device(phi))
+            int(reinit_sweeps), float(h), int(check_every))
+    tail = (trace.ctypes.data, cap, info.ctypes.data, ctypes.byref(margin)) + ((_stream_and_device(phi),) if dev else ())
+    if curv is None:
+        rc = (lib.lsf_evolve_band_device if dev else lib.lsf_evolve_band)(*head, ctypes.byref(done), ctypes.byref(cfl), *tail)
     else:
-        rc = lib.lsf_evolve_band(p, *tail)
+        rc = (lib.lsf_evolve_band_curv_device if dev else lib.lsf_evolve_band_curv)(*head, bcurv, clamp, ctypes.byref(done), ctypes.byref(cfl),
+                                                                                    ctypes.byref(diffusion), *tail)
     n = done.value
     told = rc == _lib.LSF_OK  # info and margin are written on LSF_OK only
-    rep = EvolveBandReport(n, float(cfl.value), [float(x) for x in trace[:n]], *((int(v) for v in info) if told else (None,) * 6),
-                           float(margin.value) if told else None)
+    rest = (*((int(v) for v in info) if told else (None,) * 6), float(margin.value) if told else None)
+    if curv is None:
+        rep = EvolveBandReport(n, float(cfl.value), [float(x) for x in trace[:n]], *rest)
+    else:
+        rep = EvolveBandCurvReport(n, float(cfl.value), float(diffusion.value), [float(x) for x in trace[:n]], *rest)
     try:
         _lib.check(rc)
     except LsfNaNError as e:
         e.report = rep  # the steps run, the NaN one included
         raise
     return rep
+
+
+class EvolveBandCurvReport(NamedTuple):
+    """What lsf_evolve_band_curv reports (include/lsf.h): EvolveBandReport's fields with `diffusion`, the number
+    curvature*dt/dx^2 of the explicit curvature term (reported, never judged), after `cfl`."""
+    steps: int
+    cfl: float
+    diffusion: float
+    change: List[float]
+    cells: Optional[int]
+    open_cells: Optional[int]
+    flips: Optional[int]
+    rebuilds: Optional[int]
+    entered: Optional[int]
+    near_wall: Optional[int]
+    margin: Optional[float]
+
+
+def evolveBandCurv(phi, mask, nx: int, ny: int, nz: int, dx: float, dt: float, steps: int, *, curvature: float, velocity=None, speed=None,
+                   clamp: float = 1.0, scheme: str = "rk3", arith: str = "strict", core: float = 3.0, ring: int = 3, reinit_sweeps: int = 2,
+                   h: Optional[float] = None, check_every: int = 1) -> EvolveBandCurvReport:
+    """The band time loop with a curvature term (include/lsf.h: lsf_evolve_band_curv): evolveBand for
+    phi_t + u.grad(phi) + F |grad(phi)| = curvature * kappa * |grad(phi)|, the term differenced centrally from each stage's own input
+    field -- the speed law F = a - b*kappa with b = `curvature`, run inside one call.
+
+    Everything is evolveBand's except: `curvature` (finite, >= 0) is b; `clamp` limits |kappa| to clamp/dx as in curvatureBand (0: no
+    clamp); velocity and speed may both be absent when curvature > 0 (motion by mean curvature: a sphere of radius R0 shrinks to
+    sqrt(R0^2 - 4 b t)); the report carries `diffusion` = b*dt/dx^2.  The term is explicit: keep `diffusion` small (the heat stencil's
+    bound for Euler is 1/6).  curvature=0 with a velocity or a speed is evolveBand bit for bit.
+    """
+    return _evolve_band(phi, mask, nx, ny, nz, dx, dt, steps, velocity, speed, scheme, arith, core, ring, reinit_sweeps, h, check_every,
+                        (curvature, clamp))
 
 
 class CurvatureReport(NamedTuple):
