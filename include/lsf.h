@@ -1039,8 +1039,17 @@ int lsf_multi_info(const lsf_multi *m, int *check_every, int *transport, int *rc
  * `float` with the layout of the fp64 entry points; dx, h, tol and the RMS trace stay double (the RMS is
  * accumulated in double from fp32 differences, and divided by the true product nx*ny*nz: the reference's
  * INTEGER*4 product, subs.f90:914, which the fp64 entry points reproduce, is negative for the 1536^3 grid of
- * configuration 5).  Checked against the fp64 path within the tolerance
- * stated in tests/test_gpu_f32.py. */
+ * configuration 5).  Checked against the fp64 oracle on the same fp32-rounded input: max and RMS of the
+ * difference over the whole array stay within 3 x the distance that the float32 statement of the same sweep
+ * (tests/reinit_f32_ref.py: the oracle's operations in numpy, every constant and intermediate in float32) has
+ * from that oracle; every kernel instance returns the same bits (tests/test_gpu_f32_statement.py).
+ * Value range, derived from the kernels and not measured: the smoothness terms are formed unscaled, as squares of
+ * second differences of phi, so the differences |dphi| between neighbouring points must stay below roughly 1e18 or
+ * the terms overflow; below roughly 2e-12 the 1e-30 floor takes over from the reference's relative epsilon
+ * (1e-6 * dphi^2 / 3 < 1e-30) and the weights drift towards the linear ones.  Tested with phi, dx and h scaled
+ * by 1e-8 and 1e8 (the accuracy rule above is asserted) and by 1e-13 and 1e15 (|dphi| ~ 8e-15 and 8e13: a finite
+ * field and RMS trace are asserted; at 1e-13 the field is measured 27 eps32 * max|phi| from the oracle after one
+ * sweep and 671 after nine, at 1e15 as close as inside the range). */
 int lsf_reinit_f32(float *phi, int nx, int ny, int nz, int iter, double dx, double h, double tol, int mode,
                    int *sweeps_done, double *rms_trace, int trace_cap);
 int lsf_reinit_f32_device(float *d_phi, const float *d_phiS, int nx, int ny, int nz, int iter, double dx,
