@@ -443,6 +443,43 @@ __device__ __forceinline__ double axis_godunov(double phic, double dm, double dp
     return m * m;
 }
 
+// The same term without the products by +-1, for dm and dp that the compiler can see to be results of an arithmetic
+// instruction (formed in the same branch: axis_term below).  sg x is x or -x, the sign bit flipped and nothing else, which is what
+// the negation (a source modifier of v_max_f64) gives, so each of the two inner maxima has the operands max(sg dm, -sg dp) has
+// for its sign of phic, in the same order, bit for bit -- -0 for +0 and a NaN's payload included (the product only quietens a
+// signalling NaN, which no arithmetic result is; the maximum returns its other operand for a NaN, and two NaNs end as 0 behind
+// the last maximum in both forms).  phic == +-0 and a NaN phic take the second case as `sg` does.  Compare, two maxima, select,
+// maximum, square: 7 instructions where the products take 10 (sg costs three v_mov, a compare and a select).  NOT for operands
+// merged out of two branches: the compiler then puts a canonicalising v_max x, x in front of every maximum, 12 instructions.
+template <bool STRICT>
+__device__ __forceinline__ double axis_godunov_sel(double phic, double dm, double dp)
+{
+#pragma clang fp contract(off)
+    const double mpos = STRICT ? smax(dm, -dp) : __builtin_fmax(dm, -dp);
+    const double mneg = STRICT ? smax(-dm, dp) : __builtin_fmax(-dm, dp);
+    const double mo = phic > 0. ? mpos : mneg;
+    const double m = STRICT ? smax(mo, 0.) : __builtin_fmax(mo, 0.);
+    return m * m;
+}
+
+// axis_pair and the Godunov term of one axis in one piece, the term formed INSIDE either branch (the three-lane march of
+// lsf_skew.hpp).  Formed behind the branch, from dm and dp merged out of the two, it cannot take the form above, and the compiler
+// lifts the two first-order differences of the fallback in front of the branch, where the WENO branch computes them a second
+// time: 12 instructions of every step where this takes 7.  The same doubles either way.
+template <bool STRICT>
+__device__ __forceinline__ double axis_term(const double q[7], bool weno_ok, bool yquirk, double dx, double floor2)
+{
+    double dm, dp;
+    if (weno_ok) {
+        axis_pair<STRICT>(q, true, yquirk, dx, floor2, dm, dp);
+        return axis_godunov_sel<STRICT>(q[3], dm, dp);
+    }
+    axis_pair<STRICT>(q, false, yquirk, dx, floor2, dm, dp);
+    double g = axis_godunov_sel<STRICT>(q[3], dm, dp);
+    asm volatile("" : "+v"(g)); // no instruction: left alone the compiler merges the two terms behind the branch again
+    return g;
+}
+
 // IEEE sqrt(x) by the sequence the compiler emits for it (v_rsq_f64, one coupled Newton step on root and half reciprocal
 // root, two residual corrections) WITHOUT its frame (scaling by 2^256 below 2^-767, pass-through of zeros and infinity):
 // the same instructions in the same order, hence the same bits, for every x in [1e-230, DBL_MAX] (profiles/micro/divcheck.hip

@@ -75,7 +75,7 @@ namespace lsf {
 //   [YD0, ZD0)    downstream y halo, r = YD0 + c * 3 + (b' - nj),   b' = nj..nj+2 entries 4..21
 //   [ZD0, NR)     downstream z halo, r = ZD0 + (c' - nk) * NYT + b, c' = nk..nk+2 entries 4..21
 // (z groups padded to whole load instructions).  phiS of the bundle cells is not staged: the lanes of a cell read
-// their 16 values straight into registers.
+// the 16 values of its row straight into registers (three lanes per cell: a third each).
 //
 // Two lane maps (BY = rows of one wavefront in y; a wavefront always holds 4 rows in z):
 //   BY = 5   three lanes per cell (x, y, z derivative), 5 cells + 1 idle lane per 16-lane row: 20 cells per wavefront and step
@@ -411,17 +411,23 @@ __device__ __forceinline__ bool skew_tile(SkShared<SkTile<TA, WY, WZ, BY>>& sm, 
     const int b = BY * (wave % WY) + bl, c = 4 * (wave / WY) + (lane >> 4);
     const bool row_ok = bl < BY && b < nj && c < nk;
     const int bc = row_ok ? b : 0, cc = row_ok ? c : 0;
-    // phiS of the 16 cells this lane's cell row holds (the x lane of a cell uses them): 8 registers, refilled for
-    // step t + 8 as soon as step t has used its value
+    // phiS of the TA cells this lane's cell row holds.  Three lanes per cell: only the x lane of a cell uses them, but its y and z
+    // lanes work on the same row (same bc, cc, e_ps), so each of the three holds a THIRD of the row -- the x lane steps
+    // 0 .. NPS - 1, the y lane NPS .. 2 NPS - 1, the z lane the rest -- all loaded up front, and the x lane fetches the other two
+    // thirds in the march by the row shifts that bring it gY and gZ.  (An 8-deep ring refilled by every lane in every step of the
+    // first half of the march cost 6 vector instructions and a load per refill and 16 registers instead of 12.)  Steps beyond the
+    // row's last, which the z lane's third runs into, clamp to the row like every other index here and are never fetched.
     // (one lane per cell: CU values, refilled CU steps ahead, CU = steps per iteration of the march loop)
     constexpr int CU = LSF_CELL_UNROLL;
     static_assert(CU == 4 || CU == 8 || CU == 16, "steps per iteration of the one-lane-per-cell march");
-    constexpr int NPS = BY == 5 ? TA / 2 : CU;
+    constexpr int NPS = BY == 5 ? (TA + 2) / 3 : CU;
     double ps[NPS];
     double colsum_prev = 0.0;
     const int2 e_ps = rowtab[cc * NYT + bc];
-    auto ps_load = [&](int t) {
-        return ps_t[(unsigned)(e_ps.x >> 2) + (unsigned)min(max(e_ps.y + (si > 0 ? t : -t), 0), nx)];
+    const int ps_t0 = BY == 5 ? NPS * axis : 0;               // first step of the lane's ps[]
+    const int ps_gi0 = e_ps.y + (si > 0 ? ps_t0 : -ps_t0);   // its global i
+    auto ps_load = [&](int t) { // ps[t]
+        return ps_t[(unsigned)(e_ps.x >> 2) + (unsigned)min(max(ps_gi0 + (si > 0 ? t : -t), 0), nx)];
     };
     // ---- per-lane constants ---------------------------------------------------------------------------------
     const int gj = j_lo + (sj > 0 ? bc : nj - 1 - bc), gk = k_lo + (sk > 0 ? cc : nk - 1 - cc);
@@ -640,12 +646,11 @@ __device__ __forceinline__ bool skew_tile(SkShared<SkTile<TA, WY, WZ, BY>>& sm, 
                 double q[7];
 #pragma unroll
                 for (int mm = 0; mm < 7; ++mm) q[mm] = lds[off[mm] + t];
-                const double pS = ps[t & (TA / 2 - 1)];
-                if (t + TA / 2 < TA) ps[t & (TA / 2 - 1)] = ps_load(t + TA / 2);
+                // phiS of step t at the x lane: its own third, or the y / z lane's (row_shl:1, row_shl:2 -- in front of the branch
+                // on `active`: a lane that is switched off cannot be a source)
+                const double pS = t < NPS ? ps[t] : (t < 2 * NPS ? dpp_mov<0x101>(ps[t - NPS]) : dpp_mov<0x102>(ps[t - 2 * NPS]));
                 const bool weno_ok = (bool)((weno_bits >> t) & 1u);
-                double dm, dp;
-                axis_pair<STRICT>(q, weno_ok, yquirk, dx, floor2, dm, dp);
-                const double gg = axis_godunov<STRICT>(q[3], dm, dp);
+                const double gg = axis_term<STRICT>(q, weno_ok, yquirk, dx, floor2);
                 const double gX = gg, gY = dpp_mov<0x101>(gg), gZ = dpp_mov<0x102>(gg); // row_shl:1, row_shl:2
                 if (active) { // only the x lane of a cell needs the tail (|grad|, sign, Euler step)
                     const double newv = finish_update<STRICT>(q[3], gX, gY, gZ, pS, dx, inv_dx, h);
@@ -1008,8 +1013,11 @@ __global__ __launch_bounds__(64 * WY * WZ) __attribute__((amdgpu_waves_per_eu(BY
 // is no deadlock whatever the dispatch order or the number of resident blocks; every spin is bounded (ctl[2] = 2 on
 // time-out).  A finished tile drains its write-through stores, raises its flag and counts itself into
 // plane_cnt[s][P]; the last tile of a hyperplane publishes planes_done[s] = P + 1.
+// (STRICT, three lanes per cell, 2 x 2 wavefronts: LSF_STRICT22_WAVES is the upper bound too.  With phiS in thirds the tile needs 95
+// registers instead of 101 and would run five to a CU; at four the compiler has 128 to schedule with, and 256^3 is 0.928-0.934 ms
+// per sweep against 0.943-0.946 at five -- profiles/gs_march_diet_ab.txt)
 template <int TA, int WY, int WZ, int BY, bool STRICT>
-__global__ __launch_bounds__(64 * WY * WZ) __attribute__((amdgpu_waves_per_eu(BY == 16 ? (WY * WZ == 1 ? 1 : LSF_WAVES16) : (WY == 2 && WZ == 2 ? (TA == 32 ? 2 : (STRICT ? LSF_STRICT22_WAVES : 5)) : 1)))) void k_reinit_gs_persist(GsArgs a)
+__global__ __launch_bounds__(64 * WY * WZ) __attribute__((amdgpu_waves_per_eu(BY == 16 ? (WY * WZ == 1 ? 1 : LSF_WAVES16) : (WY == 2 && WZ == 2 ? (TA == 32 ? 2 : (STRICT ? LSF_STRICT22_WAVES : 5)) : 1), (BY == 5 && WY == 2 && WZ == 2 && TA == 16 && STRICT) ? LSF_STRICT22_WAVES : 8))) void k_reinit_gs_persist(GsArgs a)
 {
     using T = SkTile<TA, WY, WZ, BY>;
     __shared__ SkShared<T> sm;
