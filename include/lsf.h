@@ -813,6 +813,87 @@ int lsf_extract_get(double *surfX, int32_t *surfElem);                          
 int lsf_extract_get_device(double *d_surfX, int32_t *d_surfElem, void *stream); /* device arrays */
 int lsf_stl_write(const char *path, const double *surfX, int nSurfNode, const int32_t *surfElem, int nSurfElem); /* host only */
 
+/* ---- surface and volume integrals of the level set phi = iso over the cells of a caller's mask ----------
+ * No reference counterpart.  How much surface there is and how much body it encloses, without a mesh: the area, the enclosed volume
+ * and its first moments (by the divergence theorem surface integrals too), the first moments of the surface and the integral of a
+ * field q over it, summed over the triangles lsf_extract_surface WOULD emit for the cells of the list.  Nothing is emitted and no
+ * node is numbered.  q, cell_area and info may be NULL; M is required.  xLo, M and info are host arrays on both seams.
+ *   LIST     the rule of lsf_reinit_band: the interior points (1..n-1 on each axis) with mask == 1.  Any other mask value means
+ *            "not in the list"; a 1 on a wall point is ignored.  The mask is read and never written.
+ *   MEASURED a cell of lsf_extract_surface (named by its lower corner c0) whose c0 is in LIST.  Its seven other corners are read
+ *            from the field whether they are list points or not, as the band stages read their stencils; c0 is interior, so
+ *            i + 1 <= nx, j + 1 <= ny, k + 1 <= nz always hold.
+ *   surface  f = phi - iso; INSIDE means f < 0, exactly as in lsf_extract_surface.  Each measured cell is cut into the same six Kuhn
+ *            tetrahedra; its crossed edges carry the same nodes, t = fa / (fa - fb) from the lower endpoint a, coordinate A
+ *            xLo[A] + ((double)i_A + t) * dx where the edge runs along A and xLo[A] + (double)i_A * dx where it does not; its
+ *            triangles have the same vertices in the same orientation and order (tetrahedron 0..5, triangle 0..1).
+ *   triangle vertices P0, P1, P2.  Evaluated exactly as written, left to right, without contraction; / and sqrt are the IEEE ones:
+ *              e1 = P1 - P0;  e2 = P2 - P0                                            (per component)
+ *              nx = e1y*e2z - e1z*e2y;  ny = e1z*e2x - e1x*e2z;  nz = e1x*e2y - e1y*e2x        n = e1 x e2 points outward
+ *              a  = 0.5 * sqrt((nx*nx + ny*ny) + nz*nz)
+ *              cx = P1y*P2z - P1z*P2y;  cy = P1z*P2x - P1x*P2z;  cz = P1x*P2y - P1y*P2x
+ *              v  = ((P0x*cx + P0y*cy) + P0z*cz) / 6.                                 the term of lsf_mesh_check's signed volume
+ *              m_A = (n_A * (((P0_A+P1_A)*(P0_A+P1_A) + (P1_A+P2_A)*(P1_A+P2_A)) + (P2_A+P0_A)*(P2_A+P0_A))) / 48.     A = x, y, z
+ *              s_A = a * (((P0_A + P1_A) + P2_A) / 3.)                                A = x, y, z
+ *              qa  = a * (((q0 + q1) + q2) / 3.)                                      with q only
+ *            q at a node is q(a) + t * (q(a+d) - q(a)): linear along the crossed edge with the node's own t.  The mean is divided
+ *            BEFORE it meets a, so that q == 1 gives qa == a bit for bit ((a*3.)/3. is not a for one double in seven).  Summed over
+ *            a closed surface m_A is the integral of x_A over the body (the edge-midpoint rule, exact for x_A^2 n_A / 2 on a flat
+ *            triangle) and s_A that of x_A over the surface.
+ *   cell     a cell's contribution to each quantity starts at 0.0 and adds its triangles in their order.
+ *   M        {area, volume, int x dV, int y dV, int z dV, int x dS, int y dS, int z dS, int q dS}; M[8] is 0.0 without q.  Each
+ *            total is the sum of the per-cell contributions over the measured cells, in an order that is a function of field and
+ *            mask alone: the brick-sorted list of lsf_reinit_band, one cell per lane, an xor butterfly over the 64 lanes of a
+ *            wave, the four waves of a block of 256 entries in wave order, the blocks in block order on the host.  The totals are
+ *            bit-identical from run to run, between the two seams and on any stream -- the promise the RMS of lsf_reinit_band
+ *            makes.  They are NOT bit-identical to a sequential sum: with N crossed measured cells a total differs from the exact
+ *            sum of the contributions by at most N * 2^-53 * sum|contribution|, the bound of any order of summation.
+ *            volume and the three volume moments mean what their names say for a closed surface wholly inside the list; info[3]
+ *            says when that fails.  They are taken about the origin of xLo's frame, as lsf_mesh_check's volume is: a body far
+ *            from that origin loses digits to cancellation, and a caller who cares passes a shifted xLo.  The centroid of the
+ *            body is M[2..4] / M[1], that of the surface M[5..7] / M[0].
+ *   cell_area  optional, phi's layout.  At EVERY list point the area of the surface inside the cell it names -- that cell's
+ *            contribution to `area`, 0.0 for an uncrossed cell; nothing is written anywhere else.  No order of summation enters
+ *            it: it is the serial statement's bit for bit, the discrete delta(phi) |grad(phi)| dx^3.  It must not share a byte
+ *            with phi, mask or q.
+ *   info     [0] list cells; [1] crossed measured cells; [2] triangles; [3] OPEN crossed cells: crossed measured cells with at
+ *            least one of the six face-neighbour cells (lower corners c0 +- e_A) not in LIST, a wall point included -- then the
+ *            surface may continue outside the list and M describes an open piece; [4] triangles with a == 0.0, the exact zeros of
+ *            phi - iso on grid points that lsf_extract_surface documents.  Written on LSF_OK only.  When every crossed cell of the
+ *            grid has an interior lower corner in LIST, info[1] and info[2] equal lsf_extract_surface's info[2] and info[1].
+ *   empty    an empty list, or no crossed measured cell: LSF_OK, M all 0.0, the counts as found, cell_area 0.0 at list points.
+ *   errors   LSF_ERR_INVALID, all detected before anything is written, with the count in lsf_last_error() where there is one: a
+ *            NULL phi, mask, xLo or M; the dimensions lsf_reinit_band refuses; dx not finite or <= 0; iso or a component of xLo
+ *            not finite; cell_area overlapping phi, mask or q; a crossed edge of a measured cell with a non-finite phi - iso on an
+ *            endpoint; with q, one with a non-finite q on an endpoint.  Both are counted once per measured cell that holds the
+ *            edge (the 19 edges of its six tetrahedra), phi first.  q is read at those endpoints only: a NaN anywhere else is
+ *            legal, so the kappa / gauss that lsf_curvature_band leaves NaN off its list plug straight in.  No device:
+ *            LSF_ERR_NO_DEVICE -- there is no CPU fallback, no mode word, one arithmetic.
+ *   result   cell_area and info equal the serial statement tests/measure_ref.py with ==, M within the bound above.
+ *   seams    lsf_measure_band takes phi through its twin under lsf_mirror as lsf_extract_surface does and the mask as
+ *            lsf_reinit_band does; q is staged as lsf_advect_field stages its inputs; cell_area has no twin: it is staged in a
+ *            slot of its own as lsf_curvature_band stages its outputs, copied in on every call and copied back on LSF_OK only.
+ *            lsf_measure_band_device returns after the stream is synchronised (the host finishes the per-block partials).
+ * Guidance: the corners of a crossed cell have |phi| <= sqrt(3) dx on a distance field, so any mask of |phi| < 2.1 dx or wider
+ * contains them; a closed surface needs every crossed cell's lower corner in the list (info[3] tells).  SECOND ORDER (serial
+ * statement, sphere of radius 0.6, every interior point listed): the area is 1.12 % low on 25^3 points and 0.28 % on 49^3, the
+ * volume 2.17 % and 0.54 % -- the polyhedron is inscribed.
+ * Work: the list build of lsf_reinit_band and two launches over the list (validation, then the sums); 8 gathered loads per list
+ * cell (16 with q) and the nodes of the crossed ones; the host reads 104 bytes per 256 list cells.  Workspace: that of the list;
+ * the host seam adds one field for q and one for cell_area.  Out of scope: fp32, multi-GPU, a per-step trace inside
+ * lsf_evolve_band, second moments, integrals over the interior cells instead of the divergence theorem.
+ * Timed once on one MI355X beside lsf_curvature_band (all three outputs) on the same sphere and mask |phi| < 8.1 dx and beside
+ * lsf_extract_surface + lsf_extract_get_device on the same field (profiles/measure_band_time.txt, from
+ * profiles/micro/measure_band_time.py; device seam, ms per call, list build included): 0.36 against 0.24 and 0.68 at 256^3 (34 070
+ * of 372 155 list cells crossed), 0.84 against 0.53 and 2.36 at 512^3.  No speed is claimed beyond that record. */
+#define LSF_MEASURE_LEN 9
+#define LSF_MEASURE_INFO_LEN 5
+int lsf_measure_band(const double *phi, const int32_t *mask, const double *q, double *cell_area, int nx, int ny, int nz, double dx,
+                     const double xLo[3], double iso, double M[LSF_MEASURE_LEN], int64_t info[LSF_MEASURE_INFO_LEN]);
+int lsf_measure_band_device(const double *d_phi, const int32_t *d_mask, const double *d_q, double *d_cell_area, int nx, int ny,
+                            int nz, double dx, const double xLo[3], double iso, double M[LSF_MEASURE_LEN],
+                            int64_t info[LSF_MEASURE_INFO_LEN], void *stream);
+
 /* ---- post-smoothing gradients + surface-node advection (the step after the hot path) ----------
  * Replaces set3d.f90:470-501: firstDeriv order 8 (subs.f90:309-347, with its
  * quirks) on the cells of phiSB, then every surface node is moved by x += phiSurf * gradPhiSurf with
@@ -864,7 +945,7 @@ int lsf_mirror_sync(void *host);
  * copied to the host.  What becomes of the twins it touched depends on how far the call came:
  *   - a call refused before it wrote anything keeps them as they were, an un-synced earlier result included, which a later
  *     lsf_mirror_sync still brings home: every LSF_ERR_INVALID of lsf_advect_field, lsf_advect_field_band, lsf_evolve_band,
- *     lsf_evolve_band_curv, lsf_curvature_band, lsf_extend_field, lsf_extend_field_band and lsf_extract_surface (argument checks and the checks of
+ *     lsf_evolve_band_curv, lsf_curvature_band, lsf_measure_band, lsf_extend_field, lsf_extend_field_band and lsf_extract_surface (argument checks and the checks of
  *     u, v, w, speed, q and the list alike: all are made before phi or the mask is written), and the argument checks of
  *     every other call, which come before the twins are looked at;
  *   - any other failure -- LSF_ERR_HIP anywhere, and an error that lsf_reinit, lsf_minmax, lsf_reinit_band or

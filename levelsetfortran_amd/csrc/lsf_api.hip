@@ -34,6 +34,7 @@
 #include "lsf_evolve_band_curv.hpp"
 #include "lsf_extend_band.hpp"
 #include "lsf_extract_surface.hpp"
+#include "lsf_measure_band.hpp"
 
 using namespace lsf;
 
@@ -190,7 +191,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -746,6 +747,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_extend_band.hpp"
 
 #include "lsf_host_extract_surface.hpp"
+
+#include "lsf_host_measure_band.hpp"
 
 int box_ok(const lsf_box* b, const int lo[3], const int hi[3])
 {
@@ -1791,6 +1794,54 @@ int lsf_extract_surface(const double* phi, int nx, int ny, int nz, double dx, co
     const size_t bytes = (size_t)(nx + 1) * (ny + 1) * (nz + 1) * sizeof(double);
     if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_narrowband
     return extract_core((const double*)c.slot[S_HPHI].p, nx, ny, nz, dx, xLo, iso, nSurfNode, nSurfElem, info, nullptr);
+}
+
+int lsf_measure_band_device(const double* d_phi, const int32_t* d_mask, const double* d_q, double* d_cell_area, int nx, int ny, int nz, double dx,
+                            const double xLo[3], double iso, double M[LSF_MEASURE_LEN], int64_t info[LSF_MEASURE_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_measure_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = measure_band_args_ok(d_phi, d_mask, d_q, d_cell_area, nx, ny, nz, dx, xLo, iso, M))) return rc;
+    return measure_band_core(d_phi, d_mask, d_q, d_cell_area, nx, ny, nz, dx, xLo, iso, M, info, (hipStream_t)stream);
+}
+
+int lsf_measure_band(const double* phi, const int32_t* mask, const double* q, double* cell_area, int nx, int ny, int nz, double dx,
+                     const double xLo[3], double iso, double M[LSF_MEASURE_LEN], int64_t info[LSF_MEASURE_INFO_LEN])
+{
+    Trace trace_("lsf_measure_band");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = measure_band_args_ok(phi, mask, q, cell_area, nx, ny, nz, dx, xLo, iso, M))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
+    // q is an input only and travels as lsf_advect_field's inputs do: into a slot of its own, from a current device twin under
+    // LSF_MIRROR_TRUST / LAZY, from the host otherwise.  cell_area has no twin: as lsf_curvature_band stages its outputs it is copied in on
+    // every call (what it holds off the list stays bit for bit) and comes home on LSF_OK only.  Both before phi's twin is touched.
+    const double* d_q = nullptr;
+    if (q) {
+        if ((rc = ws(c.slot[S_MS_Q], bytes))) return rc;
+        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, q, bytes) : nullptr;
+        HIPCHK(hipMemcpy(c.slot[S_MS_Q].p, twin ? twin : (const void*)q, bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        d_q = (const double*)c.slot[S_MS_Q].p;
+    }
+    double* d_cell = nullptr;
+    if (cell_area) {
+        if ((rc = ws(c.slot[S_MS_CELL], bytes))) return rc;
+        HIPCHK(hipMemcpy(c.slot[S_MS_CELL].p, cell_area, bytes, hipMemcpyHostToDevice));
+        d_cell = (double*)c.slot[S_MS_CELL].p;
+    }
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_extract_surface
+    // the mask travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
+    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+    const Slot sm = is_nb ? S_HNB : S_HSB;
+    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+    if ((rc = measure_band_core((const double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, d_q, d_cell, nx, ny, nz, dx, xLo, iso, M, info,
+                                nullptr)))
+        return rc;
+    if (cell_area) HIPCHK(hipMemcpy(cell_area, d_cell, bytes, hipMemcpyDeviceToHost));
+    return LSF_OK;
 }
 
 int lsf_extract_get(double* surfX, int32_t* surfElem) { return extract_get(surfX, surfElem, false, nullptr); }

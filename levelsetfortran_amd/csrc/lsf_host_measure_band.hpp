@@ -1,0 +1,107 @@
+// lsf_host_measure_band.hpp -- host side of lsf_measure_band (kernels and design: lsf_measure_band.hpp): validation, the list, the
+// two launches over it and the finish of the per-block partials in block order.  Included by lsf_api.hip inside its anonymous
+// namespace.
+#pragma once
+
+// what can be decided without the device (phi, mask, q and cell_area are the caller's, host or device: only compared; xLo and M are
+// host arrays on both seams); nothing is written anywhere before this has passed
+int measure_band_args_ok(const void* phi, const void* mask, const void* q, const void* cell_area, int nx, int ny, int nz, double dx,
+                         const double* xLo, double iso, const double* M)
+{
+    int rc;
+    if (!phi) return fail(LSF_ERR_INVALID, "lsf_measure_band: phi is NULL");
+    if (!mask) return fail(LSF_ERR_INVALID, "lsf_measure_band: mask is NULL");
+    if (!xLo) return fail(LSF_ERR_INVALID, "lsf_measure_band: xLo is NULL");
+    if (!M) return fail(LSF_ERR_INVALID, "lsf_measure_band: M is NULL");
+    if ((rc = check_dims(nx, ny, nz))) return rc;
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    if (n > (size_t)0x7fffffff)
+        return fail(LSF_ERR_INVALID, "lsf_measure_band: more than 2^31 - 1 points (list entries are 32-bit point indices)");
+    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "lsf_measure_band: dx must be finite and > 0");
+    if (!std::isfinite(iso)) return fail(LSF_ERR_INVALID, "lsf_measure_band: iso must be finite");
+    if (!std::isfinite(xLo[0]) || !std::isfinite(xLo[1]) || !std::isfinite(xLo[2]))
+        return fail(LSF_ERR_INVALID, "lsf_measure_band: xLo must hold three finite values");
+    // cell_area is written while phi, mask and q are still being read: it may share a byte with none of them
+    if (cell_area) {
+        const void* a[3] = {phi, mask, q};
+        const size_t bytes[3] = {n * sizeof(double), n * sizeof(int32_t), n * sizeof(double)};
+        const char* name[3] = {"phi", "mask", "q"};
+        const uintptr_t x = (uintptr_t)cell_area;
+        for (int i = 0; i < 3; ++i) {
+            if (!a[i]) continue;
+            const uintptr_t y = (uintptr_t)a[i];
+            if (x < y ? y - x < n * sizeof(double) : x - y < bytes[i])
+                return fail(LSF_ERR_INVALID, std::string("lsf_measure_band: cell_area overlaps ") + name[i]);
+        }
+    }
+    return LSF_OK;
+}
+
+// the arguments have passed measure_band_args_ok.  M and info are written on LSF_OK only.  Returns after the stream is synchronised.
+int measure_band_core(const double* d_phi, const int32_t* d_mask, const double* d_q, double* d_cell, int nx, int ny, int nz, double dx,
+                      const double xLo[3], double iso, double* M, int64_t* info, hipStream_t st)
+{
+    int rc;
+    Ctx& c = ctx();
+    BandList bl;
+    if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, dx, st))) return rc;
+    const int nL = bl.nL, nchunks = bl.nchunks;
+    if (nL <= 0) { // empty list: nothing to measure, nothing written
+        for (int m = 0; m < LSF_MEASURE_LEN; ++m) M[m] = 0.0;
+        if (info) info[0] = info[1] = info[2] = info[3] = info[4] = 0;
+        return LSF_OK;
+    }
+    // (a grid whose brick keys do not fit 32 bits keeps the memory order: the order of the sum is then that one, still a function of
+    // the mask alone)
+    if ((rc = band_list_sort(bl, bl.keys_fit(), st))) return rc;
+    if ((rc = ws(c.slot[S_PART], (size_t)nchunks * MS_NQ * sizeof(double)))) return rc;
+    if ((rc = ws(c.slot[S_PART2], (size_t)nchunks * MS_NCNT * sizeof(unsigned long long)))) return rc;
+    if ((rc = ws(c.slot[S_MS_CTL], MS_CTL_LEN * sizeof(unsigned long long)))) return rc;
+    double* part = (double*)c.slot[S_PART].p;
+    unsigned long long* cnt = (unsigned long long*)c.slot[S_PART2].p;
+    unsigned long long* ctl = (unsigned long long*)c.slot[S_MS_CTL].p;
+    HIPCHK(hipMemsetAsync(ctl, 0, MS_CTL_LEN * sizeof(unsigned long long), st));
+    const dim3 grid((unsigned)nchunks), blk(MB_CH);
+    // the validation pass comes first; the measuring pass leaves at once, before its one store, when it counted anything
+    if (d_q)
+        hipLaunchKernelGGL((k_measure_check<true>), grid, blk, 0, st, d_phi, d_q, (const int*)bl.L, nL, nx, ny, iso, ctl);
+    else
+        hipLaunchKernelGGL((k_measure_check<false>), grid, blk, 0, st, d_phi, d_q, (const int*)bl.L, nL, nx, ny, iso, ctl);
+#define LSF_MS_CALL(HQ, HC) \
+    hipLaunchKernelGGL((k_measure_band<HQ, HC>), grid, blk, 0, st, d_phi, d_mask, d_q, d_cell, (const int*)bl.L, nL, nx, ny, nz, dx, xLo[0], xLo[1], \
+                       xLo[2], iso, (const unsigned long long*)ctl, part, cnt)
+    switch ((d_q ? 2 : 0) | (d_cell ? 1 : 0)) {
+    case 0: LSF_MS_CALL(false, false); break;
+    case 1: LSF_MS_CALL(false, true); break;
+    case 2: LSF_MS_CALL(true, false); break;
+    default: LSF_MS_CALL(true, true); break;
+    }
+#undef LSF_MS_CALL
+    HIPCHK(hipGetLastError());
+    unsigned long long bad[MS_CTL_LEN];
+    std::vector<double> hp((size_t)nchunks * MS_NQ);
+    std::vector<unsigned long long> hc((size_t)nchunks * MS_NCNT);
+    HIPCHK(hipMemcpyAsync(bad, ctl, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hc.data(), cnt, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad[MS_BAD_F])
+        return fail(LSF_ERR_INVALID, "lsf_measure_band: " + std::to_string(bad[MS_BAD_F]) +
+                                         " crossed edge(s) of measured cells with a non-finite phi - iso on an endpoint");
+    if (bad[MS_BAD_Q])
+        return fail(LSF_ERR_INVALID,
+                    "lsf_measure_band: " + std::to_string(bad[MS_BAD_Q]) + " crossed edge(s) of measured cells with a non-finite q on an endpoint");
+    double tot[MS_NQ];
+    unsigned long long n[MS_NCNT] = {0, 0, 0, 0};
+    for (int m = 0; m < MS_NQ; ++m) tot[m] = 0.0;
+    for (int b = 0; b < nchunks; ++b) { // block order
+        for (int m = 0; m < MS_NQ; ++m) tot[m] = tot[m] + hp[(size_t)b * MS_NQ + m];
+        for (int m = 0; m < MS_NCNT; ++m) n[m] += hc[(size_t)b * MS_NCNT + m];
+    }
+    if (getenv("LSF_TRACE"))
+        fprintf(stderr, "[lsf] measures on the band: %d list cells (%.2f %% of the grid), %d chunks, %llu crossed, %llu triangles, %llu open\n", nL,
+                100.0 * nL / (double)bl.n, nchunks, n[0], n[1], n[2]);
+    for (int m = 0; m < MS_NQ; ++m) M[m] = tot[m];
+    if (info) info[0] = nL, info[1] = (int64_t)n[0], info[2] = (int64_t)n[1], info[3] = (int64_t)n[2], info[4] = (int64_t)n[3];
+    return LSF_OK;
+}

@@ -34,6 +34,9 @@
 !   curvatureBand(phi,mask,kappa,nx,ny,nz,dx,clamp)      the reference's own is commented out (subs.f90:426-448): the mean
 !                                                        curvature div(grad(phi)/|grad(phi)|) on the cells with mask == 1
 !                                                        only (include/lsf.h: lsf_curvature_band)
+!   measureBand(phi,mask,nx,ny,nz,dx,xLo,iso,M)          no reference counterpart: area, enclosed volume, their first moments
+!                                                        and the surface's, summed over the cells with mask == 1 only
+!                                                        (include/lsf.h: lsf_measure_band)
 !   extendFieldBand(q,phi,mask,nx,ny,nz,dx,band)         no reference counterpart: extendField on the cells with mask == 1
 !                                                        only, by Jacobi passes over the list: q carried off the list cells
 !                                                        with |phi| < band*dx (include/lsf.h: lsf_extend_field_band)
@@ -107,6 +110,7 @@ PUBLIC :: advectFieldBand
 PUBLIC :: evolveBand
 PUBLIC :: evolveBandCurv
 PUBLIC :: curvatureBand
+PUBLIC :: measureBand
 PUBLIC :: extendFieldBand
 PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
@@ -318,6 +322,20 @@ INTERFACE
       REAL(c_double), INTENT(OUT) :: kappa_max
       INTEGER(c_int) :: rc
    END FUNCTION lsf_curvature_band
+   ! int lsf_measure_band(const double*,const int32_t*,const double*,double*,int,int,int,double,const double[3],double,double[9],
+   !                      int64_t[5])
+   FUNCTION lsf_measure_band(phi,mask,q,cell_area,nx,ny,nz,dx,xLo,iso,M,info) &
+            BIND(C,NAME='lsf_measure_band') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(IN) :: phi(*),xLo(3)
+      INTEGER(c_int), INTENT(IN) :: mask(*)
+      TYPE(c_ptr), VALUE :: q,cell_area      ! NULL: no field to integrate, no per-cell areas wanted
+      INTEGER(c_int), VALUE :: nx,ny,nz
+      REAL(c_double), VALUE :: dx,iso
+      REAL(c_double), INTENT(OUT) :: M(9)
+      INTEGER(c_int64_t), INTENT(OUT) :: info(5)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_measure_band
    ! int lsf_extend_field_band(double*,const double*,const int32_t*,const int32_t*,int,int,int,double,double,int,int*,int64_t*,int,
    !                           int64_t[4])
    FUNCTION lsf_extend_field_band(q,phi,mask,known,nx,ny,nz,dx,band,max_passes,passes_done,changed_trace,trace_cap,info) &
@@ -1008,6 +1026,37 @@ PRINT*
 IF (rc == LSF_ERR_NAN) STOP
 
 END SUBROUTINE curvatureBand
+
+!*************************************************************************************!
+! How much surface there is and how much body it encloses, on the cells of a mask only
+! (include/lsf.h: lsf_measure_band; no reference counterpart): the level set phi = iso is
+! measured in the cells whose lower corner is an interior point with mask == 1 (e.g.
+! phiNB of narrowBand), triangle by triangle as extractSurface would emit them, and no
+! mesh is made.  M(1) area, M(2) enclosed volume, M(3:5) its first moments (the centroid
+! is M(3:5)/M(2)), M(6:8) the first moments of the surface, M(9) 0.  phi and mask are read
+! only.  Prints the area, the volume, the cells and the triangles, and says when the
+! surface leaves the list (volume and centroid then describe an open piece).
+!*************************************************************************************!
+SUBROUTINE measureBand(phi,mask,nx,ny,nz,dx,xLo,iso,M)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+REAL,INTENT(IN) :: dx,xLo(3),iso
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: mask
+REAL,INTENT(OUT) :: M(9)
+INTEGER(c_int64_t) :: info(5)
+INTEGER(c_int) :: rc
+
+M = 0.
+info = 0
+CALL lsf_set_mirror()
+rc = lsf_measure_band(phi,mask,c_null_ptr,c_null_ptr,nx,ny,nz,dx,xLo,iso,M,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_measure_band',rc)
+PRINT*, " Measures on the band: area ",M(1),", volume ",M(2),", crossed cells ",info(2)," of ",info(1),", triangles ",info(3)
+IF (info(4) > 0) PRINT*, " Measures on the band: ",info(4)," crossed cells at the edge of the list: an open piece"
+PRINT*
+
+END SUBROUTINE measureBand
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

@@ -30,6 +30,10 @@ and the mean and Gaussian curvature of the level sets on the cells of a mask (th
 
   curvatureBand(phi, mask, nx, ny, nz, dx, kappa, ...)          include/lsf.h: lsf_curvature_band
 
+and the area, the enclosed volume, the centroids and the integral of a field over the surface, summed on the cells of a mask:
+
+  measureBand(phi, mask, nx, ny, nz, dx, xLo, ...)              include/lsf.h: lsf_measure_band
+
 and a quantity known on that band carried to the rest of the grid constant along the normals (no reference counterpart):
 
   extendField(q, phi, nx, ny, nz, dx, band=... | mask=...)      include/lsf.h: lsf_extend_field
@@ -56,7 +60,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -901,6 +905,75 @@ def curvatureBand(phi, mask, nx: int, ny: int, nz: int, dx: float, kappa, *, gau
         rc = lib.lsf_curvature_band(*args)
     _lib.check(rc)
     return CurvatureReport(int(info[0]), int(info[1]), int(info[2]), float(kmax.value))
+
+
+class MeasureReport(NamedTuple):
+    """What lsf_measure_band reports (include/lsf.h): M as named fields -- `centroid` is the body's (volume moments / volume) and
+    `surface_centroid` the surface's (surface moments / area), NaN where the divisor is 0 -- and info[0..4].  `open` > 0: the surface
+    may continue outside the list, and volume and centroid then describe an open piece."""
+    area: float
+    volume: float
+    centroid: tuple
+    surface_centroid: tuple
+    q_integral: float
+    cells: int
+    crossed: int
+    triangles: int
+    open: int
+    degenerate: int
+
+
+def measureBand(phi, mask, nx: int, ny: int, nz: int, dx: float, xLo, iso: float = 0.0, q=None, cell_area=None) -> MeasureReport:
+    """Area, enclosed volume, centroids and the integral of `q` over the level set phi = iso, summed on the cells of `mask` only
+    (include/lsf.h: lsf_measure_band): the triangles extractSurface would emit for the cells whose lower corner is a list point,
+    measured where they are and never emitted.
+
+    mask: int32, phi's layout and kind; the interior points where it is 1 are the list (any mask of |phi| < 2.1 dx or wider holds the
+    crossed cells of a distance field).  q: a field of phi's layout and kind, read on the endpoints of crossed edges only -- NaN
+    anywhere else is fine, which is what curvatureBand leaves.  cell_area: a field of phi's layout and kind that receives, at every
+    list point, the area of the surface inside the cell the point names, and is left alone elsewhere.  phi, mask and q are read only.
+    The grid point (i,j,k) is xLo + (i,j,k)*dx; volume and centroid are taken about the origin of that frame.  The totals are
+    bit-identical from run to run and between the seams.  All arrays are numpy arrays (host seam) or all are torch CUDA tensors
+    (device seam, on the tensor's current stream).
+    """
+    if mask is None:
+        raise ValueError("mask (int32) must be a field of phi's shape")
+    lo = np.ascontiguousarray(xLo, dtype=np.float64)
+    if lo.shape != (3,) or not np.all(np.isfinite(lo)):
+        raise ValueError("xLo must hold 3 finite values")
+    dx, iso = float(dx), float(iso)
+    if not (np.isfinite(dx) and dx > 0.0):
+        raise ValueError("dx must be finite and > 0")
+    if not np.isfinite(iso):
+        raise ValueError("iso must be finite")
+    dev = _is_torch(phi)
+    opt = [(n, a) for n, a in (("q", q), ("cell_area", cell_area)) if a is not None]
+    if any(_is_torch(a) != dev for _, a in opt + [("mask", mask)]):
+        raise TypeError("phi, mask, q and cell_area must all be numpy arrays or all be CUDA tensors")
+    if dev:
+        import torch
+
+        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
+        if any(a.device != phi.device for _, a in opt + [("mask", mask)]):
+            raise ValueError("phi, mask, q and cell_area must live on one device")
+        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+    else:
+        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
+        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+    p = ptr(phi, "phi")
+    o = {n: ptr(a, n) for n, a in opt}
+    lib = _lib.load()
+    M = np.zeros(_lib.LSF_MEASURE_LEN, dtype=np.float64)
+    info = np.zeros(_lib.LSF_MEASURE_INFO_LEN, dtype=np.int64)
+    args = (p, m, o.get("q"), o.get("cell_area"), nx, ny, nz, dx, lo.ctypes.data, iso, M.ctypes.data, info.ctypes.data)
+    if dev:
+        rc = lib.lsf_measure_band_device(*args, _stream_and_device(phi))
+    else:
+        rc = lib.lsf_measure_band(*args)
+    _lib.check(rc)
+    M = [float(v) for v in M]
+    over = lambda num, den: tuple(v / den if den != 0.0 else float("nan") for v in num)
+    return MeasureReport(M[0], M[1], over(M[2:5], M[1]), over(M[5:8], M[0]), M[8], *(int(v) for v in info))
 
 
 class SurfaceInfo(NamedTuple):
