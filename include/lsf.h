@@ -894,6 +894,87 @@ int lsf_measure_band_device(const double *d_phi, const int32_t *d_mask, const do
                             int nz, double dx, const double xLo[3], double iso, double M[LSF_MEASURE_LEN],
                             int64_t info[LSF_MEASURE_INFO_LEN], void *stream);
 
+/* ---- the field at arbitrary points: value, gradient, a second field and the foot point on phi = iso ----------
+ * No reference counterpart (its setPhiSurf is private to lsf_advect_nodes, trilinear only, moves a node on the positive side only and
+ * clamps instead of refusing).  A caller that holds particles, the nodes of another mesh or the nodes lsf_extract_surface has just
+ * returned asks the grid a question: a pure gather, one lane per point, in the caller's order.  mask, q, grad, qval, foot, status and
+ * info may be NULL; qval requires q, foot requires iters >= 1; q without a mask is legal and is then read wherever the stencil goes.
+ * phi, mask, q and pts are inputs only.  xLo and info are host arrays on both seams.
+ *   arrays   pts, grad and foot are REAL a(npts,3) in Fortran order: point t has x at [t], y at [t + npts], z at [t + 2 npts] -- the
+ *            layout of surfX, so the output of lsf_extract_get / lsf_extract_get_device plugs in.  val, qval and status have npts
+ *            entries.  phi, mask and q are fields of (nx+1)(ny+1)(nz+1) points; the grid point (i,j,k) is xLo + (i,j,k) dx.
+ *   exact    every expression below is evaluated left to right as written, without contraction, with the IEEE / and sqrt: the numpy
+ *            transcription tests/sample_ref.py is the yardstick bit for bit.
+ *   locate   per axis A, n = nx, ny, nz:  s = (x - xLo[A]) / dx.  The point is INSIDE on that axis when s >= 0 && s <= n, compared
+ *            in double BEFORE any conversion to an integer: NaN, +-inf and 1e300 fail it and never reach an index.
+ *            i0 = min((int)floor(s), n - 1), so the upper wall belongs to the last cell with t = 1;  t = s - (double)i0.  A point
+ *            that is not INSIDE on all three axes gets status LSF_SAMPLE_OUTSIDE.
+ *   stencil  LSF_SAMPLE_CUBIC is used when 1 <= i0 <= n - 2 on ALL three axes (the joint rule, as for WENO in lsf_advect_field): the
+ *            4 x 4 x 4 points i0 - 1 .. i0 + 2.  Otherwise, and always for LSF_SAMPLE_LINEAR, the 2 x 2 x 2 corners of the cell.  A
+ *            cubic request served linearly is counted in info[3].
+ *   band     with a mask a stencil point is IN when it is an interior point (1..n-1 on each axis) with mask == 1, the LIST rule of
+ *            lsf_reinit_band.  A point whose used stencil holds a point that is not IN gets status LSF_SAMPLE_OFFBAND.  This is what
+ *            makes q = kappa of lsf_curvature_band, written at list cells only, safe to sample.
+ *   weights  cubic (Catmull-Rom):   w0 = 0.5*(((2.-t)*t-1.)*t)       w1 = 0.5*((3.*t-5.)*t*t+2.)
+ *                                   w2 = 0.5*(((4.-3.*t)*t+1.)*t)    w3 = 0.5*((t-1.)*t*t)
+ *            its derivative:        d0 = 0.5*((4.-3.*t)*t-1.)        d1 = 0.5*((9.*t-10.)*t)
+ *                                   d2 = 0.5*((8.-9.*t)*t+1.)        d3 = 0.5*((3.*t-2.)*t)
+ *            linear:                w0 = 1.-t, w1 = t;  d0 = -1., d1 = 1.
+ *   value    contract along x first: r = ((w0*a0 + w1*a1) + w2*a2) + w3*a3, or w0*a0 + w1*a1 for linear; then the row results along y
+ *            in the same form, then z.  val is that result for phi, qval the same for q.  grad[A] is the same contraction with d in
+ *            place of w on axis A, divided by dx at the end.  At t = 0 the linear value is the grid value with ==.
+ *   refused  for an OUTSIDE or OFFBAND point val, grad, qval and foot are NaN and nothing else of the point is computed.
+ *   foot     iters >= 1: the foot of the point on phi = iso, on both sides of the surface.  Start with y = x.  At most iters times:
+ *            sample v, g at y by the rules above; e = v - iso; if !(fabs(e) > tol*dx) converged; m = (g0*g0 + g1*g1) + g2*g2;
+ *            if m == 0 status LSF_SAMPLE_FLAT, stop; y_A = y_A - (e * g_A) / m.  After the last move y is sampled once more for the
+ *            convergence test; not converged: LSF_SAMPLE_NOT_CONVERGED.  A y that becomes OUTSIDE or OFFBAND ends the loop with that
+ *            status.  foot holds the last y in every case except OUTSIDE / OFFBAND of the original point.  val, grad and qval always
+ *            belong to the original point.  Precedence: the original point's OUTSIDE / OFFBAND first, then whatever ended the loop.
+ *            The foot follows the interpolant's gradient: it is the closest point where phi is a distance, a point of the level set
+ *            anywhere else.
+ *   info     [0] points with status OK; [1] OUTSIDE; [2] OFFBAND; [3] linear fallbacks of a cubic request, among the points whose own
+ *            sample was taken; [4] FLAT; [5] NOT_CONVERGED.  [0] + [1] + [2] + [4] + [5] == npts.  Integer counts: no order of
+ *            summation enters them.  Written on LSF_OK only.
+ *   errors   LSF_ERR_INVALID, all detected before any output is written: a NULL phi, pts, val or xLo; npts < 1; nx, ny or nz < 1 or
+ *            more than 2^31 - 1 points; dx or xLo not finite, dx <= 0; iso not finite; an unknown order; iters < 0; iters >= 1 with
+ *            tol not finite or < 0; qval without q; foot with iters == 0; any output sharing a byte with another output or with an
+ *            input.  A non-finite phi or q VALUE is not an error: it flows into the outputs as NaN / inf, like any interpolation.
+ *            No device: LSF_ERR_NO_DEVICE -- there is no CPU fallback, no mode word, one arithmetic.
+ *   seams    lsf_sample_points takes phi through its twin under lsf_mirror as lsf_extract_surface does and the mask as
+ *            lsf_curvature_band does; q is staged in a slot of its own (from its device twin where a current one exists under
+ *            LSF_MIRROR_TRUST / LAZY) and never copied back; pts and the outputs are staged per call and the outputs come home on
+ *            LSF_OK only.  lsf_sample_points_device returns after the stream is synchronised (the host finishes the block counts).
+ *   flat     m == 0 is exact: on a constant field the linear gradient -a + a is 0.0 and the point is FLAT; the cubic d weights sum
+ *            to 0 only to rounding, so a cubic request there may see a gradient of 1e-17, take a wild step and end OUTSIDE.
+ * Accuracy (the statement, cubic, on phi = |x| - 0.25 over [-0.5, 0.5]^3 at points within 1.5 dx of the surface; 13^3 / 25^3 / 49^3
+ * grid points): largest value error 2.0e-2 / 2.7e-3 / 4.3e-4 dx, largest gradient error 8.3e-2 / 8.8e-3 / 1.7e-3, largest foot
+ * error (iters = 5, tol = 1e-9) 8.5e-2 / 1.1e-2 / 2.5e-3 dx.
+ * Work: one launch; 8 or 64 gathered loads per sample and field (the mask as many), 1 + (moves made) samples per point.  Workspace:
+ * 48 bytes per 256 points; the host seam adds one field for q and 92 bytes per point.  Out of scope: fp32, multi-GPU, binning or
+ * sorting the points by brick, several q in one call, q sampled at the foot (project first, then sample), exact closest points
+ * where the field is no distance, higher-order or monotone interpolants, the mesh -> grid scatter.
+ * Timed once on one MI355X at the nodes of lsf_extract_surface on a sphere, in cell order and under a fixed random permutation,
+ * beside lsf_curvature_band (kappa only) on the mask |phi| < 8.1 dx of the same field (profiles/sample_points_time.txt, from
+ * profiles/micro/sample_points_time.py; device seam, ms per call): at 256^3 (101 898 nodes) linear 0.059 / shuffled 0.059, cubic
+ * 0.055 / 0.061, cubic with iters = 3 0.061 / 0.078, cubic with q = kappa and the mask 0.077 / 0.112 against 0.257 for the curvature
+ * call; at 512^3 (408 902 nodes) linear 0.064 / 0.073, cubic 0.072 / 0.130, cubic with iters = 3 0.085 / 0.197, cubic with q and the
+ * mask 0.119 / 0.372 against 0.517.  No speed is claimed beyond that record. */
+#define LSF_SAMPLE_LINEAR 0 /* order */
+#define LSF_SAMPLE_CUBIC 1
+#define LSF_SAMPLE_INFO_LEN 6
+#define LSF_SAMPLE_OK 0 /* status[t] */
+#define LSF_SAMPLE_OUTSIDE 1
+#define LSF_SAMPLE_OFFBAND 2
+#define LSF_SAMPLE_FLAT 3
+#define LSF_SAMPLE_NOT_CONVERGED 4
+int lsf_sample_points(const double *phi, const int32_t *mask, const double *q, int nx, int ny, int nz, double dx, const double xLo[3],
+                      const double *pts, int npts, int order, double iso, int iters, double tol, double *val, double *grad,
+                      double *qval, double *foot, int32_t *status, int64_t info[LSF_SAMPLE_INFO_LEN]);
+int lsf_sample_points_device(const double *d_phi, const int32_t *d_mask, const double *d_q, int nx, int ny, int nz, double dx,
+                             const double xLo[3], const double *d_pts, int npts, int order, double iso, int iters, double tol,
+                             double *d_val, double *d_grad, double *d_qval, double *d_foot, int32_t *d_status,
+                             int64_t info[LSF_SAMPLE_INFO_LEN], void *stream);
+
 /* ---- post-smoothing gradients + surface-node advection (the step after the hot path) ----------
  * Replaces set3d.f90:470-501: firstDeriv order 8 (subs.f90:309-347, with its
  * quirks) on the cells of phiSB, then every surface node is moved by x += phiSurf * gradPhiSurf with
@@ -945,7 +1026,7 @@ int lsf_mirror_sync(void *host);
  * copied to the host.  What becomes of the twins it touched depends on how far the call came:
  *   - a call refused before it wrote anything keeps them as they were, an un-synced earlier result included, which a later
  *     lsf_mirror_sync still brings home: every LSF_ERR_INVALID of lsf_advect_field, lsf_advect_field_band, lsf_evolve_band,
- *     lsf_evolve_band_curv, lsf_curvature_band, lsf_measure_band, lsf_extend_field, lsf_extend_field_band and lsf_extract_surface (argument checks and the checks of
+ *     lsf_evolve_band_curv, lsf_curvature_band, lsf_measure_band, lsf_sample_points, lsf_extend_field, lsf_extend_field_band and lsf_extract_surface (argument checks and the checks of
  *     u, v, w, speed, q and the list alike: all are made before phi or the mask is written), and the argument checks of
  *     every other call, which come before the twins are looked at;
  *   - any other failure -- LSF_ERR_HIP anywhere, and an error that lsf_reinit, lsf_minmax, lsf_reinit_band or

@@ -35,6 +35,7 @@
 #include "lsf_extend_band.hpp"
 #include "lsf_extract_surface.hpp"
 #include "lsf_measure_band.hpp"
+#include "lsf_sample_points.hpp"
 
 using namespace lsf;
 
@@ -191,7 +192,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -749,6 +750,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_extract_surface.hpp"
 
 #include "lsf_host_measure_band.hpp"
+
+#include "lsf_host_sample_points.hpp"
 
 int box_ok(const lsf_box* b, const int lo[3], const int hi[3])
 {
@@ -1841,6 +1844,67 @@ int lsf_measure_band(const double* phi, const int32_t* mask, const double* q, do
                                 nullptr)))
         return rc;
     if (cell_area) HIPCHK(hipMemcpy(cell_area, d_cell, bytes, hipMemcpyDeviceToHost));
+    return LSF_OK;
+}
+
+int lsf_sample_points_device(const double* d_phi, const int32_t* d_mask, const double* d_q, int nx, int ny, int nz, double dx, const double xLo[3],
+                             const double* d_pts, int npts, int order, double iso, int iters, double tol, double* d_val, double* d_grad,
+                             double* d_qval, double* d_foot, int32_t* d_status, int64_t info[LSF_SAMPLE_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_sample_points_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = sample_points_args_ok(d_phi, d_mask, d_q, nx, ny, nz, dx, xLo, d_pts, npts, order, iso, iters, tol, d_val, d_grad, d_qval, d_foot,
+                                    d_status)))
+        return rc;
+    return sample_points_core(d_phi, d_mask, d_q, nx, ny, nz, dx, xLo, d_pts, npts, order, iso, iters, tol, d_val, d_grad, d_qval, d_foot, d_status,
+                              info, (hipStream_t)stream);
+}
+
+int lsf_sample_points(const double* phi, const int32_t* mask, const double* q, int nx, int ny, int nz, double dx, const double xLo[3],
+                      const double* pts, int npts, int order, double iso, int iters, double tol, double* val, double* grad, double* qval,
+                      double* foot, int32_t* status, int64_t info[LSF_SAMPLE_INFO_LEN])
+{
+    Trace trace_("lsf_sample_points");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = sample_points_args_ok(phi, mask, q, nx, ny, nz, dx, xLo, pts, npts, order, iso, iters, tol, val, grad, qval, foot, status))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double), np = (size_t)npts;
+    // q is an input only: into a slot of its own as lsf_extend_field stages q (from a current device twin under LSF_MIRROR_TRUST / LAZY,
+    // as lsf_measure_band does) and never copied back.  Staged before phi's twin is touched.
+    const double* d_q = nullptr;
+    if (q) {
+        if ((rc = ws(c.slot[S_SP_Q], bytes))) return rc;
+        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, q, bytes) : nullptr;
+        HIPCHK(hipMemcpy(c.slot[S_SP_Q].p, twin ? twin : (const void*)q, bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        d_q = (const double*)c.slot[S_SP_Q].p;
+    }
+    // pts and the outputs are staged per call in one slot: pts(3), val(1), grad(3), qval(1), foot(3) doubles per point, then status.
+    // The kernel writes every entry of every output, so nothing is copied in but pts; the outputs come home on LSF_OK only.
+    if ((rc = ws(c.slot[S_SP_IO], np * (11 * sizeof(double) + sizeof(int32_t))))) return rc;
+    double* io = (double*)c.slot[S_SP_IO].p;
+    double *d_pts = io, *d_val = io + 3 * np, *d_grad = grad ? io + 4 * np : nullptr, *d_qval = qval ? io + 7 * np : nullptr,
+           *d_foot = foot ? io + 8 * np : nullptr;
+    int32_t* d_status = status ? (int32_t*)(io + 11 * np) : nullptr;
+    HIPCHK(hipMemcpy(d_pts, pts, 3 * np * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_extract_surface
+    const int32_t* d_mask = nullptr;
+    if (mask) { // as in lsf_curvature_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
+        const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+        Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+        const Slot sm = is_nb ? S_HNB : S_HSB;
+        if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+        d_mask = (const int32_t*)c.slot[sm].p;
+    }
+    if ((rc = sample_points_core((const double*)c.slot[S_HPHI].p, d_mask, d_q, nx, ny, nz, dx, xLo, d_pts, npts, order, iso, iters, tol, d_val,
+                                 d_grad, d_qval, d_foot, d_status, info, nullptr)))
+        return rc;
+    HIPCHK(hipMemcpy(val, d_val, np * sizeof(double), hipMemcpyDeviceToHost));
+    if (grad) HIPCHK(hipMemcpy(grad, d_grad, 3 * np * sizeof(double), hipMemcpyDeviceToHost));
+    if (qval) HIPCHK(hipMemcpy(qval, d_qval, np * sizeof(double), hipMemcpyDeviceToHost));
+    if (foot) HIPCHK(hipMemcpy(foot, d_foot, 3 * np * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, d_status, np * sizeof(int32_t), hipMemcpyDeviceToHost));
     return LSF_OK;
 }
 

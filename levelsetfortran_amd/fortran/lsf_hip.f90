@@ -37,6 +37,9 @@
 !   measureBand(phi,mask,nx,ny,nz,dx,xLo,iso,M)          no reference counterpart: area, enclosed volume, their first moments
 !                                                        and the surface's, summed over the cells with mask == 1 only
 !                                                        (include/lsf.h: lsf_measure_band)
+!   samplePoints(phi,nx,ny,nz,dx,xLo,pts,npts,order,     no reference counterpart: phi, its gradient and the foot point on
+!                iso,iters,tol,val,grad,foot,status      phi = iso at arbitrary points, trilinear or Catmull-Rom; optionally a
+!                [,mask,q,qval])                         second field q and a band mask (include/lsf.h: lsf_sample_points)
 !   extendFieldBand(q,phi,mask,nx,ny,nz,dx,band)         no reference counterpart: extendField on the cells with mask == 1
 !                                                        only, by Jacobi passes over the list: q carried off the list cells
 !                                                        with |phi| < band*dx (include/lsf.h: lsf_extend_field_band)
@@ -111,6 +114,7 @@ PUBLIC :: evolveBand
 PUBLIC :: evolveBandCurv
 PUBLIC :: curvatureBand
 PUBLIC :: measureBand
+PUBLIC :: samplePoints
 PUBLIC :: extendFieldBand
 PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
@@ -336,6 +340,21 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: info(5)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_measure_band
+   ! int lsf_sample_points(const double*,const int32_t*,const double*,int,int,int,double,const double[3],const double*,int,int,
+   !                       double,int,double,double*,double*,double*,double*,int32_t*,int64_t[6])
+   FUNCTION lsf_sample_points(phi,mask,q,nx,ny,nz,dx,xLo,pts,npts,order,iso,iters,tol,val,grad,qval,foot,status,info) &
+            BIND(C,NAME='lsf_sample_points') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(IN) :: phi(*),xLo(3),pts(*)
+      TYPE(c_ptr), VALUE :: mask,q           ! NULL: no band, no second field
+      INTEGER(c_int), VALUE :: nx,ny,nz,npts,order,iters
+      REAL(c_double), VALUE :: dx,iso,tol
+      REAL(c_double), INTENT(OUT) :: val(*),grad(*)
+      TYPE(c_ptr), VALUE :: qval,foot        ! NULL: not wanted (qval needs q, foot needs iters >= 1)
+      INTEGER(c_int), INTENT(OUT) :: status(*)
+      INTEGER(c_int64_t), INTENT(OUT) :: info(6)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_sample_points
    ! int lsf_extend_field_band(double*,const double*,const int32_t*,const int32_t*,int,int,int,double,double,int,int*,int64_t*,int,
    !                           int64_t[4])
    FUNCTION lsf_extend_field_band(q,phi,mask,known,nx,ny,nz,dx,band,max_passes,passes_done,changed_trace,trace_cap,info) &
@@ -1057,6 +1076,54 @@ IF (info(4) > 0) PRINT*, " Measures on the band: ",info(4)," crossed cells at th
 PRINT*
 
 END SUBROUTINE measureBand
+
+!*************************************************************************************!
+! The field at arbitrary points (include/lsf.h: lsf_sample_points; no reference
+! counterpart): val = phi and grad = its gradient at the npts points pts(npts,3) -- the
+! layout of surfX, so the nodes of extractSurface plug in -- interpolated trilinearly
+! (order = 0) or by Catmull-Rom cubics (order = 1, linear in the cells next to the walls).
+! iters >= 1: foot(npts,3) receives the foot of each point on phi = iso (both sides), by
+! at most iters steps along the interpolant's gradient, converged when
+! |phi - iso| <= tol*dx; iters = 0 leaves foot alone.  status(t): 0 OK, 1 outside the
+! grid, 2 off the band, 3 flat, 4 not converged; a refused point holds NaN.  mask: only
+! stencils of interior points with mask == 1 are sampled.  q, qval: a second field and
+! its values at the points.  phi, mask, q and pts are read only.  Prints the counts.
+!*************************************************************************************!
+SUBROUTINE samplePoints(phi,nx,ny,nz,dx,xLo,pts,npts,order,iso,iters,tol,val,grad,foot,status,mask,q,qval)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,order,iters
+INTEGER*4,INTENT(IN) :: npts
+REAL,INTENT(IN) :: dx,xLo(3),iso,tol
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+REAL,INTENT(IN) :: pts(npts,3)
+REAL,INTENT(OUT) :: val(npts),grad(npts,3)
+REAL,INTENT(INOUT),TARGET :: foot(npts,3)
+INTEGER*4,INTENT(OUT) :: status(npts)
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN),OPTIONAL,TARGET :: mask
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN),OPTIONAL,TARGET :: q
+REAL,INTENT(OUT),OPTIONAL,TARGET :: qval(npts)
+TYPE(c_ptr) :: pm,pq,pqv,pf
+INTEGER(c_int64_t) :: info(6)
+INTEGER(c_int) :: rc
+
+pm = c_null_ptr
+pq = c_null_ptr
+pqv = c_null_ptr
+pf = c_null_ptr
+IF (PRESENT(mask)) pm = C_LOC(mask)
+IF (PRESENT(q)) pq = C_LOC(q)
+IF (PRESENT(qval)) pqv = C_LOC(qval)
+IF (iters >= 1) pf = C_LOC(foot)
+info = 0
+CALL lsf_set_mirror()
+rc = lsf_sample_points(phi,pm,pq,nx,ny,nz,dx,xLo,pts,npts,order,iso,iters,tol,val,grad,pqv,pf,status,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_sample_points',rc)
+PRINT*, " Samples: points ",npts,", ok ",info(1),", outside ",info(2)
+PRINT*, " Samples: off the band ",info(3),", linear fallbacks ",info(4)
+IF (iters >= 1) PRINT*, " Samples: flat ",info(5),", not converged ",info(6)
+PRINT*
+
+END SUBROUTINE samplePoints
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

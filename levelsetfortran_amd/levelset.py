@@ -34,6 +34,10 @@ and the area, the enclosed volume, the centroids and the integral of a field ove
 
   measureBand(phi, mask, nx, ny, nz, dx, xLo, ...)              include/lsf.h: lsf_measure_band
 
+and the field, its gradient, a second field and the foot point on the surface at arbitrary points (particles, nodes of another mesh):
+
+  samplePoints(phi, nx, ny, nz, dx, xLo, pts, ...)              include/lsf.h: lsf_sample_points
+
 and a quantity known on that band carried to the rest of the grid constant along the normals (no reference counterpart):
 
   extendField(q, phi, nx, ny, nz, dx, band=... | mask=...)      include/lsf.h: lsf_extend_field
@@ -60,7 +64,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -974,6 +978,97 @@ def measureBand(phi, mask, nx: int, ny: int, nz: int, dx: float, xLo, iso: float
     M = [float(v) for v in M]
     over = lambda num, den: tuple(v / den if den != 0.0 else float("nan") for v in num)
     return MeasureReport(M[0], M[1], over(M[2:5], M[1]), over(M[5:8], M[0]), M[8], *(int(v) for v in info))
+
+
+class SampleReport(NamedTuple):
+    """What lsf_sample_points returns (include/lsf.h): `val` (npts), `grad` (npts, 3; None with want_grad=False), `qval` (npts; None
+    without q), `foot` (npts, 3; None with iters == 0), `status` (npts, int32: 0 OK, 1 OUTSIDE, 2 OFFBAND, 3 FLAT, 4 NOT_CONVERGED)
+    and `info`, the six counts [OK, OUTSIDE, OFFBAND, linear fallbacks of a cubic request, FLAT, NOT_CONVERGED].  The (npts, 3)
+    arrays are Fortran-ordered, the layout of surfX."""
+    val: object
+    grad: object
+    qval: object
+    foot: object
+    status: object
+    info: tuple
+
+
+_SAMPLE_ORDERS = {"linear": _lib.LSF_SAMPLE_LINEAR, "cubic": _lib.LSF_SAMPLE_CUBIC}
+
+
+def samplePoints(phi, nx: int, ny: int, nz: int, dx: float, xLo, pts, *, order: str = "cubic", mask=None, q=None, iso: float = 0.0,
+                 iters: int = 0, tol: float = 1e-6, want_grad: bool = True) -> SampleReport:
+    """The field at arbitrary points (include/lsf.h: lsf_sample_points): phi, its gradient, a second field q and, with iters >= 1, the
+    foot of each point on the level set phi = iso, interpolated trilinearly (order="linear") or by Catmull-Rom cubics ("cubic",
+    linear in the cells next to the walls).
+
+    pts: (npts, 3) float64 in Fortran order -- what extractSurface returns as surfX plugs in; it is never written.  mask: int32 field;
+    a point whose stencil leaves the interior points with mask == 1 is refused with status OFFBAND, which makes a q that exists on
+    a list only (kappa of curvatureBand) safe to sample.  A point outside the grid, NaN and inf included, gets status OUTSIDE.
+    Refused points hold NaN in every output.  phi, mask, q and pts are read only.  The grid point (i,j,k) is xLo + (i,j,k)*dx.
+    Numpy in gives numpy out (host seam); CUDA tensors in give CUDA tensors out (device seam, on the tensor's current stream).
+    """
+    lo = np.ascontiguousarray(xLo, dtype=np.float64)
+    if lo.shape != (3,) or not np.all(np.isfinite(lo)):
+        raise ValueError("xLo must hold 3 finite values")
+    dx, iso, tol, iters = float(dx), float(iso), float(tol), int(iters)
+    if not (np.isfinite(dx) and dx > 0.0):
+        raise ValueError("dx must be finite and > 0")
+    if not np.isfinite(iso):
+        raise ValueError("iso must be finite")
+    if order not in _SAMPLE_ORDERS:
+        raise ValueError("order must be 'linear' or 'cubic'")
+    if iters < 0:
+        raise ValueError("iters must be >= 0")
+    if iters >= 1 and not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError("tol must be finite and >= 0")
+    if min(int(nx), int(ny), int(nz)) < 1:
+        raise ValueError("nx, ny, nz must be >= 1")
+    dev = _is_torch(phi)
+    opt = [(n, a) for n, a in (("mask", mask), ("q", q)) if a is not None]
+    if any(_is_torch(a) != dev for _, a in opt + [("pts", pts)]):
+        raise TypeError("phi, mask, q and pts must all be numpy arrays or all be CUDA tensors")
+    if len(pts.shape) != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError("pts must have shape (npts, 3) with npts >= 1")
+    npts = int(pts.shape[0])
+    lib = _lib.load()
+    info = np.zeros(_lib.LSF_SAMPLE_INFO_LEN, dtype=np.int64)
+    if dev:
+        import torch
+
+        if any(a.device != phi.device for _, a in opt + [("pts", pts)]):
+            raise ValueError("phi, mask, q and pts must live on one device")
+        if not pts.is_cuda or pts.dtype != torch.float64 or not pts.t().is_contiguous():
+            raise TypeError("pts must be a float64 CUDA tensor of shape (npts, 3) in Fortran order (the transpose of a contiguous (3, npts))")
+        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        m = None if mask is None else _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+        qq = None if q is None else _dev_ptr(q, torch.float64, nx, ny, nz, "q")
+        vec = lambda: torch.empty((3, npts), dtype=torch.float64, device=phi.device).t()
+        val = torch.empty(npts, dtype=torch.float64, device=phi.device)
+        status = torch.empty(npts, dtype=torch.int32, device=phi.device)
+        grad = vec() if want_grad else None
+        qval = torch.empty(npts, dtype=torch.float64, device=phi.device) if q is not None else None
+        foot = vec() if iters >= 1 else None
+        ptr = lambda a: None if a is None else a.data_ptr()
+        rc = lib.lsf_sample_points_device(p, m, qq, nx, ny, nz, dx, lo.ctypes.data, pts.data_ptr(), npts, _SAMPLE_ORDERS[order], iso, iters, tol,
+                                          ptr(val), ptr(grad), ptr(qval), ptr(foot), ptr(status), info.ctypes.data, _stream_and_device(phi))
+    else:
+        if not isinstance(pts, np.ndarray) or pts.dtype != np.float64 or not pts.flags.f_contiguous:
+            raise TypeError("pts must be a Fortran-ordered float64 numpy array of shape (npts, 3)")
+        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
+        m = None if mask is None else _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+        qq = None if q is None else _host_ptr(q, np.float64, nx, ny, nz, "q")
+        vec = lambda: np.zeros((npts, 3), dtype=np.float64, order="F")
+        val = np.zeros(npts, dtype=np.float64)
+        status = np.zeros(npts, dtype=np.int32)
+        grad = vec() if want_grad else None
+        qval = np.zeros(npts, dtype=np.float64) if q is not None else None
+        foot = vec() if iters >= 1 else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = lib.lsf_sample_points(p, m, qq, nx, ny, nz, dx, lo.ctypes.data, pts.ctypes.data, npts, _SAMPLE_ORDERS[order], iso, iters, tol,
+                                   ptr(val), ptr(grad), ptr(qval), ptr(foot), ptr(status), info.ctypes.data)
+    _lib.check(rc)
+    return SampleReport(val, grad, qval, foot, status, tuple(int(v) for v in info))
 
 
 class SurfaceInfo(NamedTuple):
