@@ -975,6 +975,78 @@ int lsf_sample_points_device(const double *d_phi, const int32_t *d_mask, const d
                              double *d_val, double *d_grad, double *d_qval, double *d_foot, int32_t *d_status,
                              int64_t info[LSF_SAMPLE_INFO_LEN], void *stream);
 
+/* ---- connected components of the level set on the cells of a caller's mask ----------
+ * No reference counterpart.  How many bodies there are, which cell belongs to which, and whether two have merged or one has pinched
+ * off: the 6-connected components of the list cells on either side of phi = iso, a pure graph problem on the cell list every band
+ * call builds, with an exact integer answer that no order of execution reaches.  comp, ncomp and info may be NULL; phi and mask
+ * are inputs only.  comp, ncomp and info are host arrays on both seams.
+ *   LIST     the rule of lsf_reinit_band: the interior points (1..n-1 on each axis) with mask == 1.  Any other mask value means
+ *            "not in the list"; a 1 on a wall point is ignored.  The mask is read and never written.  Fewer than 2^31 points; a
+ *            grid whose brick keys do not fit 32 bits keeps the list in memory order.
+ *   CLASS    d = phi - iso, evaluated once per cell.  INSIDE is d < 0; OUTSIDE is everything else that is finite, d == 0 and -0.0
+ *            included.  A list cell with a non-finite d gives LSF_ERR_INVALID with the number of such cells in lsf_last_error(),
+ *            before anything is written.  phi off the list may hold anything, NaN included: it is read at list cells only.
+ *   side     LSF_LABEL_INSIDE labels the INSIDE cells only, LSF_LABEL_OUTSIDE the OUTSIDE cells only, LSF_LABEL_BOTH both classes;
+ *            a component never holds cells of both.
+ *   COMPONENT  two labelled list cells are LINKED when they are face neighbours (+-1 on one axis), both list cells, and of the same
+ *            class.  The components are the classes of the transitive closure.  18- and 26-connectivity are out of scope.
+ *   label    int32, phi's layout.  Written AT LIST CELLS and nowhere else: every other point keeps its bits, as kappa of
+ *            lsf_curvature_band does.  A labelled cell receives the 0-based point index i + (nx+1)*(j + (ny+1)*k) of the smallest
+ *            point index in its component; a list cell of a class that `side` leaves out receives -1.  label must not share a byte
+ *            with phi or mask.
+ *   comp     ncomp receives the number of components, always, even beyond comp_cap.  comp may be NULL with comp_cap == 0;
+ *            otherwise it receives min(ncomp, comp_cap) rows of LSF_LABEL_COMP_LEN int64 values, in ascending order of root index:
+ *              [0] root index   [1] cells   [2] -1 for INSIDE, +1 for OUTSIDE
+ *              [3..8] imin, imax, jmin, jmax, kmin, kmax over the component's cells (0-based point coordinates)
+ *              [9] EDGE cells: the component's cells with at least one of the six face neighbours not a list cell -- an interior
+ *                  point off the list or a wall point.
+ *            [9] == 0: the component is closed inside the list.  Anything else: it may continue beyond the list, and two
+ *            components reported here may be one in truth.  Rows beyond min(ncomp, comp_cap) are not written.
+ *   info     [0] list cells; [1] labelled cells; [2] INSIDE components; [3] OUTSIDE components; [4] passes run; [5] links still
+ *            found by the last pass -- 0 means the labels are CERTIFIED final; [6] list cells left at -1; [7] 0, reserved.  info and
+ *            ncomp are written on LSF_OK only.
+ *   max_passes  >= 1.  When the passes run out with info[5] > 0 the call still returns LSF_OK, and the labels are a REFINEMENT of
+ *            the truth: every label is the index of a cell of the same true component, and cells with one label are truly
+ *            connected.  ncomp, comp, info[2] and info[3] then count that refinement: a caller must look at info[5].
+ *   empty    LIST empty: LSF_OK, nothing written, info all 0, ncomp = 0.
+ *   errors   LSF_ERR_INVALID, all detected before anything is written: a NULL phi, mask or label; comp == NULL with comp_cap > 0;
+ *            comp_cap < 0; an unknown side; a non-finite iso; max_passes < 1; the dimensions lsf_reinit_band refuses (nx, ny or
+ *            nz < 2, a k-plane above 2 GB, more than 2^31 - 1 points); label overlapping phi or mask; a non-finite d at a list
+ *            cell.  No device: LSF_ERR_NO_DEVICE -- there is no CPU fallback.  LSF_ERR_HIP with a message if a chase of the forest
+ *            meets a word that cannot be one (label written by someone else during the call).
+ *   result   once certified, label, ncomp, the comp rows and info[0..3], info[5] and info[6] are a function of phi, mask, iso and
+ *            side alone: they equal the serial statement tests/label_ref.py with ==, on both seams, on any stream, from run to
+ *            run.  info[4], the passes, is reported and not part of that equality.
+ *   seams    lsf_label_band takes phi, an input only, through its twin under lsf_mirror as lsf_curvature_band takes it, and the
+ *            mask as lsf_reinit_band takes its mask.  label has NO twin: it is staged like kappa, in an int32 slot of its own,
+ *            copied in on every call and copied back on LSF_OK only.  lsf_label_band_device returns after the stream is
+ *            synchronised.
+ * Guidance: compact ids 0 .. ncomp-1 are a binary search of a label in the root column comp[.][0] (ncomp <= comp_cap).  Merging
+ * and pinching show as a change of info[2] between two calls on the in/out mask of lsf_evolve_band; per-component area and volume
+ * are label combined with cell_area of lsf_measure_band.
+ * Work: the list build of lsf_reinit_band; a check and an init launch; per pass a link launch (3 gathered neighbours, two chases
+ * of the forest per same-class neighbour, one 32-bit atomicMin per edge between two trees) and a flatten launch, CHECK_EVERY passes
+ * enqueued at a time; for the table a count, a collect, a sort of the roots and one launch with 64-bit integer atomics, one set per
+ * wave and component.  The forest lives in label itself; workspace beyond the list: 2 ncomp ints, the sort's temporary storage
+ * and comp_cap rows; the host seam adds one int32 field.  Out of scope: 18- and 26-connectivity, compact ids written by the call,
+ * per-component area / volume, a per-step trace inside lsf_evolve_band, fp32, multi-GPU.
+ * Timed once on one MI355X beside lsf_curvature_band (kappa only) on the same sphere and mask |phi| < 8.1 dx
+ * (profiles/label_band_time.txt, from profiles/micro/label_band_time.py; device seam, side = both, ms per call, list build
+ * included): 1.08 against 0.245 at 256^3 (0.68 without the table; 2 passes) and 3.84 against 0.511 at 512^3 (2.31; 3 passes); on
+ * min of two sphere distances with every interior point of 256^3 listed 23.6 (5.70 without the table; 3 passes) -- the table's
+ * atomics of a 16 M-cell component all meet on one row.  No test case and no timed field needed more than 3 passes.  No speed is
+ * claimed beyond that record. */
+#define LSF_LABEL_INSIDE 0 /* side */
+#define LSF_LABEL_OUTSIDE 1
+#define LSF_LABEL_BOTH 2
+#define LSF_LABEL_COMP_LEN 10
+#define LSF_LABEL_INFO_LEN 8
+int lsf_label_band(const double *phi, const int32_t *mask, int32_t *label, int nx, int ny, int nz, double iso, int side,
+                   int max_passes, int64_t *comp, int comp_cap, int64_t *ncomp, int64_t info[LSF_LABEL_INFO_LEN]);
+int lsf_label_band_device(const double *d_phi, const int32_t *d_mask, int32_t *d_label, int nx, int ny, int nz, double iso, int side,
+                          int max_passes, int64_t *comp, int comp_cap, int64_t *ncomp, int64_t info[LSF_LABEL_INFO_LEN],
+                          void *stream);
+
 /* ---- post-smoothing gradients + surface-node advection (the step after the hot path) ----------
  * Replaces set3d.f90:470-501: firstDeriv order 8 (subs.f90:309-347, with its
  * quirks) on the cells of phiSB, then every surface node is moved by x += phiSurf * gradPhiSurf with

@@ -36,6 +36,7 @@
 #include "lsf_extract_surface.hpp"
 #include "lsf_measure_band.hpp"
 #include "lsf_sample_points.hpp"
+#include "lsf_label_band.hpp"
 
 using namespace lsf;
 
@@ -192,7 +193,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -752,6 +753,8 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_measure_band.hpp"
 
 #include "lsf_host_sample_points.hpp"
+
+#include "lsf_host_label_band.hpp"
 
 int box_ok(const lsf_box* b, const int lo[3], const int hi[3])
 {
@@ -1905,6 +1908,42 @@ int lsf_sample_points(const double* phi, const int32_t* mask, const double* q, i
     if (qval) HIPCHK(hipMemcpy(qval, d_qval, np * sizeof(double), hipMemcpyDeviceToHost));
     if (foot) HIPCHK(hipMemcpy(foot, d_foot, 3 * np * sizeof(double), hipMemcpyDeviceToHost));
     if (status) HIPCHK(hipMemcpy(status, d_status, np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return LSF_OK;
+}
+
+int lsf_label_band_device(const double* d_phi, const int32_t* d_mask, int32_t* d_label, int nx, int ny, int nz, double iso, int side, int max_passes,
+                          int64_t* comp, int comp_cap, int64_t* ncomp, int64_t info[LSF_LABEL_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_label_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = label_band_args_ok(d_phi, d_mask, d_label, nx, ny, nz, iso, side, max_passes, comp, comp_cap))) return rc;
+    return label_band_core(d_phi, d_mask, d_label, nx, ny, nz, iso, side, max_passes, comp, comp_cap, ncomp, info, (hipStream_t)stream);
+}
+
+int lsf_label_band(const double* phi, const int32_t* mask, int32_t* label, int nx, int ny, int nz, double iso, int side, int max_passes, int64_t* comp,
+                   int comp_cap, int64_t* ncomp, int64_t info[LSF_LABEL_INFO_LEN])
+{
+    Trace trace_("lsf_label_band");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = label_band_args_ok(phi, mask, label, nx, ny, nz, iso, side, max_passes, comp, comp_cap))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    // label has no twin: as lsf_curvature_band stages kappa it is staged in an int32 slot of its own from the host on every call (what it
+    // holds outside the list stays bit for bit) and comes home on LSF_OK only.  Staged before phi's twin is touched.
+    if ((rc = ws(c.slot[S_LB_LABEL], n * sizeof(int32_t)))) return rc;
+    HIPCHK(hipMemcpy(c.slot[S_LB_LABEL].p, label, n * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // phi is an input only, as in lsf_curvature_band
+    // the mask travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
+    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+    const Slot sm = is_nb ? S_HNB : S_HSB;
+    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+    if ((rc = label_band_core((const double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, (int32_t*)c.slot[S_LB_LABEL].p, nx, ny, nz, iso, side,
+                              max_passes, comp, comp_cap, ncomp, info, nullptr)))
+        return rc;
+    HIPCHK(hipMemcpy(label, c.slot[S_LB_LABEL].p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return LSF_OK;
 }
 

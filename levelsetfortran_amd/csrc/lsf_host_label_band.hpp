@@ -1,0 +1,143 @@
+// lsf_host_label_band.hpp -- host side of lsf_label_band (kernels and design: lsf_label_band.hpp): validation, the list, the check
+// launch with its error counts, the link / flatten passes enqueued CHECK_EVERY at a time, and the table of components.  Included by
+// lsf_api.hip inside its anonymous namespace.
+#pragma once
+
+// what can be decided without the device (the pointers are the caller's, host or device: only compared); nothing is written anywhere
+// before this and the check launch have passed
+int label_band_args_ok(const void* phi, const void* mask, const void* label, int nx, int ny, int nz, double iso, int side, int max_passes,
+                       const void* comp, int comp_cap)
+{
+    int rc;
+    if (!phi) return fail(LSF_ERR_INVALID, "lsf_label_band: phi is NULL");
+    if (!mask) return fail(LSF_ERR_INVALID, "lsf_label_band: mask is NULL");
+    if (!label) return fail(LSF_ERR_INVALID, "lsf_label_band: label is NULL");
+    if ((rc = check_dims(nx, ny, nz))) return rc;
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    if (n > (size_t)0x7fffffff)
+        return fail(LSF_ERR_INVALID, "lsf_label_band: more than 2^31 - 1 points (list entries and labels are 32-bit point indices)");
+    if (!std::isfinite(iso)) return fail(LSF_ERR_INVALID, "lsf_label_band: iso must be finite");
+    if (side != LSF_LABEL_INSIDE && side != LSF_LABEL_OUTSIDE && side != LSF_LABEL_BOTH)
+        return fail(LSF_ERR_INVALID, "lsf_label_band: side must be LSF_LABEL_INSIDE, LSF_LABEL_OUTSIDE or LSF_LABEL_BOTH");
+    if (max_passes < 1) return fail(LSF_ERR_INVALID, "lsf_label_band: max_passes must be >= 1");
+    if (comp_cap < 0) return fail(LSF_ERR_INVALID, "lsf_label_band: comp_cap must be >= 0");
+    if (!comp && comp_cap > 0) return fail(LSF_ERR_INVALID, "lsf_label_band: comp is NULL with comp_cap > 0");
+    // label is written while phi and the mask are still being read
+    const uintptr_t l0 = (uintptr_t)label, l1 = l0 + n * sizeof(int32_t);
+    const uintptr_t p0 = (uintptr_t)phi, m0 = (uintptr_t)mask;
+    if (l0 < p0 + n * sizeof(double) && p0 < l1) return fail(LSF_ERR_INVALID, "lsf_label_band: label overlaps phi");
+    if (l0 < m0 + n * sizeof(int32_t) && m0 < l1) return fail(LSF_ERR_INVALID, "lsf_label_band: label overlaps mask");
+    return LSF_OK;
+}
+
+// the arguments have passed label_band_args_ok.  comp, ncomp and info are host arrays and are written on LSF_OK only, d_label after every
+// error has been decided.  Returns after the stream is synchronised.
+int label_band_core(const double* d_phi, const int32_t* d_mask, int32_t* d_label, int nx, int ny, int nz, double iso, int side, int max_passes,
+                    int64_t* comp, int comp_cap, int64_t* ncomp, int64_t* info, hipStream_t st)
+{
+    int rc;
+    Ctx& c = ctx();
+    BandList bl;
+    if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, 1.0, st))) return rc;
+    const int nL = bl.nL, nchunks = bl.nchunks;
+    if (nL <= 0) { // empty list: nothing to do, nothing written
+        if (info)
+            for (int q = 0; q < LSF_LABEL_INFO_LEN; ++q) info[q] = 0;
+        if (ncomp) *ncomp = 0;
+        return LSF_OK;
+    }
+    // (a grid whose brick keys do not fit 32 bits keeps the memory order: only the locality of a chunk depends on the order)
+    if ((rc = band_list_sort(bl, bl.keys_fit(), st))) return rc;
+    const int* L = bl.L;
+    int* label = (int*)d_label;
+    constexpr int NPART = LB_NCHECK > LB_NROOTS ? LB_NCHECK : LB_NROOTS;
+    if ((rc = ws(c.slot[S_PART], (size_t)nchunks * NPART * sizeof(unsigned long long)))) return rc;
+    if ((rc = ws(c.slot[S_LB_CNT], (CHECK_EVERY + 2) * sizeof(unsigned long long)))) return rc;
+    unsigned long long* part = (unsigned long long*)c.slot[S_PART].p;
+    unsigned long long* d_cnt = (unsigned long long*)c.slot[S_LB_CNT].p; // one count per pass of a batch | the chase flag | the head of the roots
+    int* d_flag = (int*)(d_cnt + CHECK_EVERY);
+    unsigned* d_head = (unsigned*)(d_cnt + CHECK_EVERY + 1);
+    const dim3 grid((unsigned)nchunks), blk(MB_CH);
+
+    // the check: read-only on the caller's arrays; its counts decide the errors
+    hipLaunchKernelGGL(k_label_check, grid, blk, 0, st, d_phi, L, nL, iso, part);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned long long> h((size_t)nchunks * NPART);
+    HIPCHK(hipMemcpyAsync(h.data(), part, (size_t)nchunks * LB_NCHECK * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    unsigned long long nbad = 0, nin = 0, nout = 0;
+    for (int b = 0; b < nchunks; ++b) // integer counts: no order in the result
+        nbad += h[(size_t)b * LB_NCHECK], nin += h[(size_t)b * LB_NCHECK + 1], nout += h[(size_t)b * LB_NCHECK + 2];
+    if (nbad) return fail(LSF_ERR_INVALID, "lsf_label_band: " + std::to_string(nbad) + " list cell(s) hold a non-finite phi - iso");
+    const unsigned long long nlabelled = side == LSF_LABEL_BOTH ? nin + nout : side == LSF_LABEL_INSIDE ? nin : nout;
+
+    HIPCHK(hipMemsetAsync(d_cnt + CHECK_EVERY, 0, 2 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_label_init, grid, blk, 0, st, d_phi, L, nL, iso, side, label);
+    // the passes, a batch enqueued ahead of the device; the kernels behind a pass that linked nothing return at once, and the host
+    // reads the counts of the batch and the chase flag once
+    int passes = 0;
+    unsigned long long last = 0, hc[CHECK_EVERY + 1];
+    bool stopped = false;
+    while (!stopped && passes < max_passes) {
+        const int batch = std::min(CHECK_EVERY, max_passes - passes);
+        HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)batch * sizeof(unsigned long long), st));
+        for (int p = 0; p < batch; ++p) {
+            hipLaunchKernelGGL(k_label_link, grid, blk, 0, st, d_phi, d_mask, L, nL, nx, ny, nz, iso, label, d_cnt, p, d_flag);
+            hipLaunchKernelGGL(k_label_flatten, grid, blk, 0, st, L, nL, label, (const unsigned long long*)d_cnt, p, d_flag);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hc, d_cnt, (CHECK_EVERY + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if ((int)hc[CHECK_EVERY] != 0)
+            return fail(LSF_ERR_HIP, "lsf_label_band: a chase met a word that is no forest word, or ran beyond the number of list cells "
+                                     "(label was written by someone else during the call?)");
+        for (int p = 0; p < batch && !stopped; ++p) {
+            ++passes, last = hc[p];
+            stopped = hc[p] == 0; // that pass is counted
+        }
+    }
+
+    // the roots of each class
+    hipLaunchKernelGGL(k_label_roots, grid, blk, 0, st, d_phi, L, nL, iso, (const int*)label, part);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h.data(), part, (size_t)nchunks * LB_NROOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    unsigned long long rin = 0, rout = 0;
+    for (int b = 0; b < nchunks; ++b) rin += h[(size_t)b * LB_NROOTS], rout += h[(size_t)b * LB_NROOTS + 1];
+    const size_t nc = (size_t)(rin + rout);
+    const int rows = (int)std::min(nc, (size_t)comp_cap);
+    std::vector<int64_t> table((size_t)rows * LB_ROW);
+    if (rows > 0) {
+        // the roots, sorted ascending; the first `rows` get a slot number at their point of the staging buffer of the list build
+        // (free since band_list_sort, written and read at root points only) and a row
+        size_t tmp_bytes = 0;
+        HIPCHK(rocprim::radix_sort_keys(nullptr, tmp_bytes, (unsigned*)nullptr, (unsigned*)nullptr, nc, 0, 32, st));
+        const size_t keys_bytes = (nc * sizeof(int) + 255) & ~(size_t)255;
+        if ((rc = ws(c.slot[S_LB_ROOTS], 2 * keys_bytes + tmp_bytes))) return rc;
+        if ((rc = ws(c.slot[S_LB_ROWS], (size_t)rows * LB_ROW * sizeof(long long)))) return rc;
+        int* roots = (int*)c.slot[S_LB_ROOTS].p;
+        int* sorted = (int*)((char*)c.slot[S_LB_ROOTS].p + keys_bytes);
+        void* tmp = (char*)c.slot[S_LB_ROOTS].p + 2 * keys_bytes;
+        long long* d_rows = (long long*)c.slot[S_LB_ROWS].p;
+        hipLaunchKernelGGL(k_label_collect, grid, blk, 0, st, L, nL, (const int*)label, roots, d_head);
+        HIPCHK(rocprim::radix_sort_keys(tmp, tmp_bytes, (unsigned*)roots, (unsigned*)sorted, nc, 0, 32, st));
+        hipLaunchKernelGGL(k_label_slots, dim3((unsigned)((nc + MB_CH - 1) / MB_CH)), blk, 0, st, (const int*)sorted, (int)nc, rows, d_phi, iso,
+                           bl.staging, d_rows);
+        hipLaunchKernelGGL(k_label_table, grid, blk, 0, st, d_mask, L, nL, nx, ny, nz, (const int*)label, (const int*)bl.staging, rows, d_rows);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(table.data(), d_rows, table.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if (getenv("LSF_TRACE"))
+        fprintf(stderr, "[lsf] components on the band: %d list cells (%.2f %% of the grid), %d chunks, %llu labelled, %llu + %llu components, "
+                        "%d pass(es), last count %llu\n",
+                nL, 100.0 * nL / (double)bl.n, nchunks, nlabelled, rin, rout, passes, last);
+    if (comp)
+        for (size_t q = 0; q < table.size(); ++q) comp[q] = table[q];
+    if (ncomp) *ncomp = (int64_t)nc;
+    if (info) {
+        info[0] = nL, info[1] = (int64_t)nlabelled, info[2] = (int64_t)rin, info[3] = (int64_t)rout, info[4] = passes, info[5] = (int64_t)last;
+        info[6] = (int64_t)((unsigned long long)nL - nlabelled), info[7] = 0;
+    }
+    return LSF_OK;
+}

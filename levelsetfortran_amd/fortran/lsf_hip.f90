@@ -40,6 +40,8 @@
 !   samplePoints(phi,nx,ny,nz,dx,xLo,pts,npts,order,     no reference counterpart: phi, its gradient and the foot point on
 !                iso,iters,tol,val,grad,foot,status      phi = iso at arbitrary points, trilinear or Catmull-Rom; optionally a
 !                [,mask,q,qval])                         second field q and a band mask (include/lsf.h: lsf_sample_points)
+!   labelBand(phi,mask,label,nx,ny,nz,iso,side,ncomp)    no reference counterpart: the connected components of the cells with
+!                                                        mask == 1 on either side of phi = iso (include/lsf.h: lsf_label_band)
 !   extendFieldBand(q,phi,mask,nx,ny,nz,dx,band)         no reference counterpart: extendField on the cells with mask == 1
 !                                                        only, by Jacobi passes over the list: q carried off the list cells
 !                                                        with |phi| < band*dx (include/lsf.h: lsf_extend_field_band)
@@ -115,6 +117,7 @@ PUBLIC :: evolveBandCurv
 PUBLIC :: curvatureBand
 PUBLIC :: measureBand
 PUBLIC :: samplePoints
+PUBLIC :: labelBand
 PUBLIC :: extendFieldBand
 PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
@@ -340,6 +343,20 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: info(5)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_measure_band
+   ! int lsf_label_band(const double*,const int32_t*,int32_t*,int,int,int,double,int,int,int64_t*,int,int64_t*,int64_t[8])
+   FUNCTION lsf_label_band(phi,mask,label,nx,ny,nz,iso,side,max_passes,comp,comp_cap,ncomp,info) &
+            BIND(C,NAME='lsf_label_band') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(IN) :: phi(*)
+      INTEGER(c_int), INTENT(IN) :: mask(*)
+      INTEGER(c_int), INTENT(INOUT) :: label(*)
+      INTEGER(c_int), VALUE :: nx,ny,nz,side,max_passes,comp_cap
+      REAL(c_double), VALUE :: iso
+      TYPE(c_ptr), VALUE :: comp             ! NULL with comp_cap = 0: no table wanted
+      INTEGER(c_int64_t), INTENT(OUT) :: ncomp
+      INTEGER(c_int64_t), INTENT(OUT) :: info(8)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_label_band
    ! int lsf_sample_points(const double*,const int32_t*,const double*,int,int,int,double,const double[3],const double*,int,int,
    !                       double,int,double,double*,double*,double*,double*,int32_t*,int64_t[6])
    FUNCTION lsf_sample_points(phi,mask,q,nx,ny,nz,dx,xLo,pts,npts,order,iso,iters,tol,val,grad,qval,foot,status,info) &
@@ -1076,6 +1093,43 @@ IF (info(4) > 0) PRINT*, " Measures on the band: ",info(4)," crossed cells at th
 PRINT*
 
 END SUBROUTINE measureBand
+
+!*************************************************************************************!
+! How many bodies there are and which cell belongs to which, on the cells of a mask only
+! (include/lsf.h: lsf_label_band; no reference counterpart): the 6-connected components of
+! the interior points with mask == 1 (e.g. phiSB of narrowBand, or the mask evolveBand
+! returns) on one side of phi = iso.  side = 0: the cells with phi - iso < 0, 1: all other
+! cells (phi == iso included), 2: both classes, never mixed in one component.  label
+! (INTEGER, phi's shape) receives at every such cell the 0-based point index
+! i + (nx+1)*(j + (ny+1)*k) of the smallest point of its component, -1 at a list cell of
+! the class left out; every other point keeps what it held.  phi and mask are read only.
+! ncomp receives the number of components.  Prints the list cells, the labelled cells,
+! the components of each class and the passes, and says when the passes ran out before
+! the labels were certified (they are then a refinement of the components).
+!*************************************************************************************!
+SUBROUTINE labelBand(phi,mask,label,nx,ny,nz,iso,side,ncomp)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,side
+REAL,INTENT(IN) :: iso
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: mask
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: label
+INTEGER,INTENT(OUT) :: ncomp
+INTEGER(c_int64_t) :: info(8),nc
+INTEGER(c_int) :: rc
+
+info = 0
+nc = 0
+CALL lsf_set_mirror()
+rc = lsf_label_band(phi,mask,label,nx,ny,nz,iso,side,64,c_null_ptr,0,nc,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_label_band',rc)
+ncomp = INT(nc)
+PRINT*, " Components on the band: list cells ",info(1),", labelled ",info(2),", inside ",info(3),", outside ",info(4), &
+        ", passes ",info(5)
+IF (info(6) > 0) PRINT*, " Components on the band: ",info(6)," links were still found by the last pass: a refinement"
+PRINT*
+
+END SUBROUTINE labelBand
 
 !*************************************************************************************!
 ! The field at arbitrary points (include/lsf.h: lsf_sample_points; no reference

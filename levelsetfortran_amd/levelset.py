@@ -38,6 +38,10 @@ and the field, its gradient, a second field and the foot point on the surface at
 
   samplePoints(phi, nx, ny, nz, dx, xLo, pts, ...)              include/lsf.h: lsf_sample_points
 
+and how many bodies there are and which cell belongs to which, the connected components on the cells of a mask:
+
+  labelBand(phi, mask, nx, ny, nz, label, ...)                  include/lsf.h: lsf_label_band
+
 and a quantity known on that band carried to the rest of the grid constant along the normals (no reference counterpart):
 
   extendField(q, phi, nx, ny, nz, dx, band=... | mask=...)      include/lsf.h: lsf_extend_field
@@ -978,6 +982,80 @@ def measureBand(phi, mask, nx: int, ny: int, nz: int, dx: float, xLo, iso: float
     M = [float(v) for v in M]
     over = lambda num, den: tuple(v / den if den != 0.0 else float("nan") for v in num)
     return MeasureReport(M[0], M[1], over(M[2:5], M[1]), over(M[5:8], M[0]), M[8], *(int(v) for v in info))
+
+
+class LabelReport(NamedTuple):
+    """What lsf_label_band reports (include/lsf.h): the number of components, the first min(ncomp, comp_cap) rows of the table (int64,
+    shape (rows, 10): root index, cells, -1 INSIDE / +1 OUTSIDE, imin, imax, jmin, jmax, kmin, kmax, edge cells; ascending root index),
+    the passes run, whether the last pass found no link any more (`certified`: the labels are final) and the raw info[0..7]."""
+    ncomp: int
+    components: np.ndarray
+    passes: int
+    certified: bool
+    info: tuple
+
+
+_LABEL_SIDES = {"inside": _lib.LSF_LABEL_INSIDE, "outside": _lib.LSF_LABEL_OUTSIDE, "both": _lib.LSF_LABEL_BOTH}
+
+
+def labelBand(phi, mask, nx: int, ny: int, nz: int, label, *, iso: float = 0.0, side: str = "inside", max_passes: int = 64,
+              comp_cap=None) -> LabelReport:
+    """The 6-connected components of the cells of `mask` on either side of phi = iso (include/lsf.h: lsf_label_band): how many bodies
+    there are and which cell belongs to which.
+
+    mask: int32, phi's layout and kind; the interior points where it is 1 are the list.  label: int32, phi's layout and kind, written
+    at the list cells and nowhere else: a labelled cell receives the point index i + (nx+1)*(j + (ny+1)*k) of the smallest point of its
+    component, a list cell of the class `side` leaves out receives -1.  side: "inside" (phi - iso < 0), "outside" (everything else,
+    phi == iso included) or "both"; a component never holds cells of both classes.  Two cells are linked when they are face
+    neighbours, both in the list and of one class.  phi and mask are read only; phi is read at list cells only.  comp_cap: the rows of
+    the table to return at most (None: 1024); `ncomp` counts every component.  A row's last entry counts the component's cells at the
+    edge of the list: 0 means it is closed inside the list.  `certified` False (max_passes ran out): the labels are a refinement of
+    the truth.  All arrays are numpy arrays (host seam) or all are torch CUDA tensors (device seam, on the tensor's current stream).
+
+    Compact ids 0 .. ncomp-1 (ncomp <= comp_cap), at the labelled cells:
+        rep = labelBand(phi, mask, nx, ny, nz, label)
+        ids = np.searchsorted(rep.components[:, 0], label[label >= 0])
+    """
+    if mask is None or label is None:
+        raise ValueError("mask and label (int32) must be fields of phi's shape")
+    if side not in _LABEL_SIDES:
+        raise ValueError('side must be "inside", "outside" or "both"')
+    iso, max_passes = float(iso), int(max_passes)
+    if not np.isfinite(iso):
+        raise ValueError("iso must be finite")
+    if max_passes < 1:
+        raise ValueError("max_passes must be >= 1")
+    cap = 1024 if comp_cap is None else int(comp_cap)
+    if cap < 0:
+        raise ValueError("comp_cap must be >= 0")
+    dev = _is_torch(phi)
+    if _is_torch(mask) != dev or _is_torch(label) != dev:
+        raise TypeError("phi, mask and label must all be numpy arrays or all be CUDA tensors")
+    if dev:
+        import torch
+
+        if mask.device != phi.device or label.device != phi.device:
+            raise ValueError("phi, mask and label must live on one device")
+        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+        lab = _dev_ptr(label, torch.int32, nx, ny, nz, "label")
+    else:
+        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
+        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+        lab = _host_ptr(label, np.int32, nx, ny, nz, "label")
+    lib = _lib.load()
+    comp = np.zeros((cap, _lib.LSF_LABEL_COMP_LEN), dtype=np.int64)
+    info = np.zeros(_lib.LSF_LABEL_INFO_LEN, dtype=np.int64)
+    ncomp = ctypes.c_int64(0)
+    args = (p, m, lab, nx, ny, nz, iso, _LABEL_SIDES[side], max_passes, comp.ctypes.data if cap else None, cap, ctypes.byref(ncomp),
+            info.ctypes.data)
+    if dev:
+        rc = lib.lsf_label_band_device(*args, _stream_and_device(phi))
+    else:
+        rc = lib.lsf_label_band(*args)
+    _lib.check(rc)
+    n = int(ncomp.value)
+    return LabelReport(n, comp[:min(n, cap)].copy(), int(info[4]), int(info[5]) == 0, tuple(int(v) for v in info))
 
 
 class SampleReport(NamedTuple):

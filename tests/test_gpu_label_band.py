@@ -1,0 +1,320 @@
+"""lsf_label_band on the GPU against tests/label_ref.py, the serial statement of the contract in include/lsf.h: label -- the whole array,
+the bits off the list included --, ncomp, the comp rows and info[0..3], info[5], info[6] are compared with `==`, on both seams, for
+every side.  info[4], the passes, is printed and checked against max_passes only.
+
+The cases are those of tests/label_cases.py (its docstring says what each is for; tests/test_label_band_cpu.py asserts it on the CPU).
+Besides them: max_passes = 1 on the snakes (LSF_OK, info[5] > 0, a refinement), comp_cap = 16 on the checkerboard (16 rows, the rest of
+comp untouched), the refusals, the merge of two growing spheres through evolveBand, two streams, and the Fortran wrapper through
+tests/fortran/host_label.f90."""
+import ctypes
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import label_cases as C
+import label_ref as L
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+SEAMS = ["host", "device"]
+SIDE_WORD = {"inside": 0, "outside": 1, "both": 2}
+
+
+@pytest.fixture(scope="module")
+def lsf():
+    import torch
+
+    assert torch.cuda.is_available()
+    import levelsetfortran_amd
+
+    return levelsetfortran_amd
+
+
+@functools.lru_cache(maxsize=None)
+def _want(case, side):
+    phi, mask, npts, iso = C.geometry(case)
+    r = L.label_band(phi, mask, C.prefill(npts), iso, side)
+    r.label.setflags(write=False), r.comp.setflags(write=False)
+    return r
+
+
+def _dev(a):
+    import torch
+
+    return torch.from_numpy(np.array(a.ravel(order="F"))).cuda()  # (a copy: the shared inputs are read-only)
+
+
+def _host(t, shape):
+    return t.cpu().numpy().reshape(shape, order="F")
+
+
+def _bits(a, b):
+    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+
+
+def _run(lsf, seam, phi, mask, npts, iso, side, stream=None, **kw):
+    """labelBand on fresh copies through one seam; returns (label, report); asserts that phi and mask are unchanged"""
+    import torch
+
+    n = tuple(v - 1 for v in npts)
+    mk = _dev if seam == "device" else (lambda a: a.copy(order="F"))
+    p, m, lab = mk(phi), mk(mask), mk(C.prefill(npts))
+    back = lambda a: a if seam == "host" else _host(a, npts)
+    try:
+        if stream is not None:
+            torch.cuda.synchronize()
+            with torch.cuda.stream(stream):
+                rep = lsf.labelBand(p, m, *n, lab, iso=iso, side=side, **kw)
+            torch.cuda.synchronize()
+        else:
+            rep = lsf.labelBand(p, m, *n, lab, iso=iso, side=side, **kw)
+    finally:
+        assert _bits(back(p), phi) and np.array_equal(back(m), mask)  # read, never written
+    return back(lab), rep
+
+
+def _assert_equal(label, rep, want, cap=1024):
+    assert label.dtype == np.int32 and np.array_equal(label, want.label), int(np.count_nonzero(label != want.label))
+    assert rep.ncomp == want.ncomp and rep.components.dtype == np.int64
+    assert np.array_equal(rep.components, want.comp[:cap])
+    assert rep.certified and rep.info[:4] == want.info[:4] and rep.info[5:] == want.info[5:]
+
+
+# ---------------------------------------------------------------------------------- 1: == the statement
+@pytest.mark.parametrize("seam", SEAMS)
+@pytest.mark.parametrize("side", L.SIDES)
+@pytest.mark.parametrize("case", C.CASES)
+def test_equal_to_the_statement(lsf, case, side, seam):
+    phi, mask, npts, iso = C.geometry(case)
+    want = _want(case, side)
+    label, rep = _run(lsf, seam, phi, mask, npts, iso, side)
+    print(f"{case} {side} {seam}: ncomp {rep.ncomp} (want {want.ncomp}), passes {rep.passes}, info {rep.info}; label differs at "
+          f"{int(np.count_nonzero(label != want.label))} points")
+    _assert_equal(label, rep, want)
+    assert 1 <= rep.passes <= 64  # certified within the default max_passes
+    lst = L.list_of(mask)
+    assert np.array_equal(label[~lst], C.prefill(npts)[~lst])  # the list cells, and nothing else
+
+
+# ---------------------------------------------------------------------------------- 2: the passes run out
+@pytest.mark.parametrize("seam", SEAMS)
+@pytest.mark.parametrize("case", ["snake_end", "snake_mid"])
+def test_one_pass_gives_a_refinement(lsf, case, seam):
+    phi, mask, npts, iso = C.geometry(case)
+    want = _want(case, "inside")
+    label, rep = _run(lsf, seam, phi, mask, npts, iso, "inside", max_passes=1)
+    print(f"{case} {seam}: max_passes 1: ncomp {rep.ncomp}, links found by the pass {rep.info[5]}")
+    assert rep.passes == 1 and not rep.certified and rep.info[5] > 0  # LSF_OK all the same
+    lst = L.list_of(mask)
+    assert np.array_equal(label[~lst], C.prefill(npts)[~lst])
+    got, truth = label.ravel(order="F"), want.label.ravel(order="F")
+    cells = np.flatnonzero(lst.ravel(order="F"))
+    assert np.array_equal(got[cells] == -1, truth[cells] == -1)
+    cells = cells[got[cells] >= 0]
+    # every label is the index of a labelled cell with the same statement label -- so equal labels imply equal statement labels --
+    # and never larger than the cell's own index; a root carries its own index
+    assert (truth[got[cells]] == truth[cells]).all() and (got[cells] <= cells).all() and (got[got[cells]] == got[cells]).all()
+    roots = np.unique(got[cells])
+    assert rep.ncomp == len(roots) == rep.info[2] >= want.ncomp and rep.info[3] == 0
+    assert np.array_equal(rep.components[:, 0], roots[:1024])
+    assert all(row[1] == np.count_nonzero(got[cells] == row[0]) for row in rep.components)
+
+
+# ---------------------------------------------------------------------------------- 3: more components than rows
+def _raw(lib, seam, phi, mask, label, n, iso, side, max_passes, comp, cap, stream=None):
+    info = np.full(8, -7, np.int64)
+    ncomp = ctypes.c_int64(-7)
+    ptr = (lambda a: None if a is None else a.data_ptr()) if seam == "device" else (lambda a: None if a is None else a.ctypes.data)
+    args = (ptr(phi), ptr(mask), ptr(label), n[0], n[1], n[2], iso, side, max_passes, None if comp is None else comp.ctypes.data, cap,
+            ctypes.byref(ncomp), info.ctypes.data)
+    rc = lib.lsf_label_band_device(*args, stream) if seam == "device" else lib.lsf_label_band(*args)
+    return rc, list(info), ncomp.value, (lib.lsf_last_error() or b"").decode()
+
+
+@pytest.mark.parametrize("seam", SEAMS)
+def test_comp_cap_below_ncomp(lsf, seam):
+    from levelsetfortran_amd import _lib
+
+    lib = _lib.load()
+    phi, mask, npts, iso = C.geometry("checker")
+    n = tuple(v - 1 for v in npts)
+    want = _want("checker", "both")
+    assert want.ncomp == want.info[1] == 720 > 16
+    mk = _dev if seam == "device" else (lambda a: a.copy(order="F"))
+    comp = np.full((20, 10), -99, np.int64)
+    lab = mk(C.prefill(npts))
+    rc, info, ncomp, msg = _raw(lib, seam, mk(phi), mk(mask), lab, n, iso, 2, 64, comp, 16)
+    assert rc == 0, msg
+    assert ncomp == 720 and info[:4] == list(want.info[:4]) and info[5] == 0
+    assert np.array_equal(comp[:16], want.comp[:16]) and (comp[16:] == -99).all()  # the 16 smallest roots; the rows beyond stay
+    assert np.array_equal(lab if seam == "host" else _host(lab, npts), want.label)
+    label, rep = _run(lsf, seam, phi, mask, npts, iso, "both", comp_cap=16)
+    _assert_equal(label, rep, want, cap=16)
+    label, rep = _run(lsf, seam, phi, mask, npts, iso, "both", comp_cap=0)  # ncomp alone: comp is NULL
+    assert rep.ncomp == 720 and rep.components.shape == (0, 10) and np.array_equal(label, want.label)
+
+
+# ---------------------------------------------------------------------------------- 4: refusals
+@pytest.mark.parametrize("seam", SEAMS)
+def test_refusals_leave_everything_untouched(lsf, seam):
+    from levelsetfortran_amd import _lib
+
+    lib = _lib.load()
+    phi0, mask0, npts, iso = C.geometry("small")
+    n = tuple(v - 1 for v in npts)
+    lst = L.list_of(mask0)
+    mk = _dev if seam == "device" else (lambda a: a.copy(order="F"))
+    back = (lambda t: _host(t, npts)) if seam == "device" else (lambda t: t)
+    nan_on = phi0.copy(order="F")
+    for c in np.argwhere(lst)[[3, 100, 200]]:
+        nan_on[tuple(c)] = np.nan
+    nan_on[tuple(np.argwhere(lst)[50])] = np.inf
+    phi, mask, lab, bad = mk(phi0), mk(mask0), mk(C.prefill(npts)), mk(nan_on)
+    comp = np.full((4, 10), -99, np.int64)
+    ok = dict(phi=phi, mask=mask, label=lab, n=n, iso=0.0, side=2, max_passes=64, comp=comp, cap=4)
+    # (a double array seen as int32 words, for "label is phi": the check compares addresses only)
+    cases = {
+        "NULL phi": dict(phi=None),
+        "NULL mask": dict(mask=None),
+        "NULL label": dict(label=None),
+        "label is phi": dict(label=phi),
+        "label is mask": dict(label=mask),
+        "comp NULL with a cap": dict(comp=None, cap=4),
+        "cap < 0": dict(cap=-1),
+        "side 3": dict(side=3),
+        "side -1": dict(side=-1),
+        "iso NaN": dict(iso=float("nan")),
+        "iso inf": dict(iso=float("inf")),
+        "max_passes 0": dict(max_passes=0),
+        "nx < 2": dict(n=(1, n[1], n[2])),
+        "nz < 2": dict(n=(n[0], n[1], 0)),
+        "non-finite phi on the list": dict(phi=bad),
+    }
+    for name, change in cases.items():
+        rc, info, ncomp, msg = _raw(lib, seam, **dict(ok, **change))
+        assert rc == _lib.LSF_ERR_INVALID, (name, rc, msg)
+        assert msg and info == [-7] * 8 and ncomp == -7 and (comp == -99).all(), name  # nothing reported
+        assert np.array_equal(back(lab), C.prefill(npts)), name  # nothing written
+        assert _bits(back(phi), phi0) and np.array_equal(back(mask), mask0), name
+        if name == "non-finite phi on the list":
+            assert msg.startswith("lsf_label_band: 4 list cell"), msg
+        if name.startswith("label is"):
+            assert "overlaps" in msg
+    # a NaN off the list is accepted, and the library is in working order
+    nan_off = phi0.copy(order="F")
+    nan_off[~lst] = np.nan
+    want = _want("small", "both")
+    rc, info, ncomp, msg = _raw(lib, seam, **dict(ok, phi=mk(nan_off)))
+    assert rc == 0 and ncomp == 2 and info[:4] == list(want.info[:4]) and info[5:] == [0, 0, 0], (rc, msg)
+    assert np.array_equal(back(lab), want.label) and np.array_equal(comp[:2], want.comp) and (comp[2:] == -99).all()
+    # the Python layer raises the same errors
+    with pytest.raises(lsf.LsfError) as e:
+        lsf.labelBand(bad, mask, *n, lab)
+    assert e.value.code == _lib.LSF_ERR_INVALID and "4 list cell" in str(e.value)
+    with pytest.raises(ValueError):
+        lsf.labelBand(phi, mask, *n, lab, side="all")
+
+
+@pytest.mark.parametrize("seam", SEAMS)
+def test_empty_list_writes_nothing(lsf, seam):
+    phi, _, npts, iso = C.geometry("two")
+    walls = np.zeros(npts, np.int32, order="F")
+    walls[0, :, :], walls[:, -1, :] = 1, 1  # 1s on wall points only
+    walls[5, 5, 5] = 2
+    label, rep = _run(lsf, seam, phi, walls, npts, iso, "both")
+    assert rep.ncomp == 0 and rep.info == (0,) * 8 and rep.components.shape == (0, 10)
+    assert np.array_equal(label, C.prefill(npts))
+
+
+# ---------------------------------------------------------------------------------- 5: two spheres grow into each other
+@pytest.mark.parametrize("seam", SEAMS)
+def test_two_spheres_merge_under_evolve_band(lsf, seam):
+    import evolve_band_ref as V
+
+    phi0, mask0, speed, dx, dt, steps = C.two_sphere_chain()
+    npts = phi0.shape
+    n = tuple(v - 1 for v in npts)
+    mk = _dev if seam == "device" else (lambda a: a.copy(order="F"))
+    back = (lambda t: _host(t, npts)) if seam == "device" else (lambda t: t)
+    p, m, f, lab = mk(phi0), mk(mask0), mk(speed), mk(C.prefill(npts))
+    before = lsf.labelBand(p, m, *n, lab, side="inside")
+    want0 = L.label_band(phi0, mask0, C.prefill(npts), 0.0, "inside")
+    assert before.ncomp == want0.ncomp == 2 and np.array_equal(back(lab), want0.label) and np.array_equal(before.components, want0.comp)
+    rep = lsf.evolveBand(p, m, *n, dx, dt, steps, speed=f)
+    e = V.evolve_band(phi0, mask0, None, speed, dx, dt, steps)
+    assert rep.steps == e.steps == steps and np.array_equal(back(p), e.field) and np.array_equal(back(m), e.mask)
+    lab = mk(C.prefill(npts))
+    after = lsf.labelBand(p, m, *n, lab, side="inside")  # on the call's own in/out mask
+    want1 = L.label_band(e.field, e.mask, C.prefill(npts), 0.0, "inside")
+    print(f"{seam}: {before.ncomp} -> {after.ncomp} components, passes {before.passes} and {after.passes}")
+    assert after.ncomp == want1.ncomp == 1 and after.certified
+    assert np.array_equal(back(lab), want1.label) and np.array_equal(after.components, want1.comp) and after.components[0, 9] == 0
+    assert after.info[:4] == want1.info[:4] and after.info[5:] == want1.info[5:]
+
+
+# ---------------------------------------------------------------------------------- 6: streams, run to run
+def test_two_streams_give_identical_bits(lsf):
+    import torch
+
+    for case in ("two", "snake_mid"):
+        phi, mask, npts, iso = C.geometry(case)
+        want = _want(case, "both")
+        got = [_run(lsf, "device", phi, mask, npts, iso, "both", stream=torch.cuda.Stream()) for _ in range(2)]
+        for label, rep in got:
+            _assert_equal(label, rep, want)
+        assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1].components, got[1][1].components)
+
+
+# ---------------------------------------------------------------------------------- 7: the Fortran wrapper
+EXE = os.path.join(ROOT, "build", "dropin", "host_label.exec")
+
+
+@pytest.fixture(scope="module")
+def host_label_exe():
+    import shutil
+
+    path = os.environ.get("PATH", "") + ":/opt/rocm/bin"
+    if not os.path.exists(EXE):
+        fc = shutil.which("amdflang", path=path)
+        if fc is None:
+            pytest.skip("no amdflang: tests/fortran/host_label.f90 cannot be built")
+        p = subprocess.run(["make", "-C", os.path.join(ROOT, "levelsetfortran_amd", "fortran"), "label", f"FC={fc}"],
+                           env=dict(os.environ, PATH=path), text=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+        assert p.returncode == 0 and os.path.exists(EXE), p.stdout[-3000:]
+    return EXE
+
+
+@pytest.mark.parametrize("resident", ["0", "2"])
+@pytest.mark.parametrize("case,side", [("two", "both"), ("hollow_band", "outside"), ("iso", "inside")])
+def test_label_band_through_the_fortran_wrapper(lsf, host_label_exe, tmp_path, case, side, resident):
+    """tests/fortran/host_label.f90: labelBand of lsf_hip.f90 on a case of the statement, after a narrowBand on other arrays has taken
+    the device twins: label, ncomp and the printed counts are the statement's, phi and the mask come back as they went in.
+    resident = 2 (TRUST | LAZY) is the shim's default."""
+    import re
+
+    phi, mask, npts, iso = C.geometry(case)
+    want = _want(case, side)
+    with open(tmp_path / "label_in.bin", "wb") as f:
+        f.write(np.array([*(v - 1 for v in npts), SIDE_WORD[side]], np.int32).tobytes())
+        f.write(np.array([iso], np.float64).tobytes())
+        for a in (phi, mask, C.prefill(npts)):
+            f.write(a.tobytes(order="F"))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("LSF_")}
+    env.update(LSF_RESIDENT=resident)
+    p = subprocess.run(f"ulimit -s unlimited; cd {tmp_path}; {host_label_exe}", shell=True, env=env, text=True, stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, timeout=120)
+    assert p.returncode == 0, p.stdout[-3000:]
+    print(p.stdout)
+    label = np.fromfile(tmp_path / "label.bin", np.int32).reshape(npts, order="F")
+    assert np.array_equal(label, want.label)
+    assert int(np.fromfile(tmp_path / "ncomp.bin", np.int32)[0]) == want.ncomp
+    assert _bits(np.fromfile(tmp_path / "phi.bin", np.float64).reshape(npts, order="F"), phi)
+    assert np.array_equal(np.fromfile(tmp_path / "mask.bin", np.int32).reshape(npts, order="F"), mask)
+    line = [q for q in (" ".join(t.split()) for t in re.split(r"\n[ \t]*\n", p.stdout)) if q.startswith("Components on the band: list cells")]
+    assert len(line) == 1, p.stdout[-3000:]
+    got = [int(t) for t in re.findall(r"-?\d+", line[0])]
+    assert got[:4] == list(want.info[:4]) and 1 <= got[4] <= 64 and len(got) == 5, (got, want.info)  # certified: no second line
