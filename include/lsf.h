@@ -975,6 +975,100 @@ int lsf_sample_points_device(const double *d_phi, const int32_t *d_mask, const d
                              double *d_val, double *d_grad, double *d_qval, double *d_foot, int32_t *d_status,
                              int64_t info[LSF_SAMPLE_INFO_LEN], void *stream);
 
+/* ---- the first hit of a ray with the level set: what the surface looks like from over there ----------
+ * No reference counterpart.  Line-of-sight speed laws and shadowing, wall thickness (cast from a node of lsf_extract_surface against
+ * its normal), depth images of the moved geometry without a mesh, probes: one lane per ray, in the caller's order, marching by
+ * the field's own value between samples of lsf_sample_points' interpolant and skipping what a band list does not hold.  mask, q,
+ * hit, grad, qval, status and info may be NULL; qval requires q.  phi, mask, q, org and dir are inputs only.  xLo and info are host
+ * arrays on both seams.
+ *   arrays   org, dir, hit and grad are REAL a(nrays,3) in Fortran order, the layout of surfX and of pts of lsf_sample_points; thit,
+ *            qval and status have nrays entries.  phi, mask and q are fields of (nx+1)(ny+1)(nz+1) points.
+ *   exact    every expression below is evaluated left to right as written, without contraction, with the IEEE / and sqrt: the numpy
+ *            transcription tests/cast_ref.py is the yardstick bit for bit.  fmax(a, b) and fmin(a, b) are defined HERE: b where a
+ *            is NaN; else a where b is NaN or a >= b (fmin: a <= b); else b.  That is C's fmax / fmin with the one thing C leaves
+ *            open decided: on a tie, +0 against -0 included, the FIRST argument is returned.
+ *   ray      o = org, d = dir of the ray.  A component of o or d that is not finite: status LSF_CAST_BAD.  L = sqrt((d0*d0 + d1*d1)
+ *            + d2*d2); !(L > 0) or L not finite (a zero direction, 1e300): BAD.  u_A = d_A / L; every t below is a length.
+ *   clip     slabs.  t0 = tmin, t1 = tmax; per axis A, n = nx, ny, nz:  lo = xLo[A], hi = xLo[A] + (double)n*dx.  u_A == 0: when
+ *            !(o_A >= lo && o_A <= hi) status LSF_CAST_NOGRID.  Otherwise a = (lo - o_A)/u_A, b = (hi - o_A)/u_A,
+ *            t0 = fmax(t0, fmin(a, b)), t1 = fmin(t1, fmax(a, b)).  After the three axes !(t0 <= t1): NOGRID.
+ *   sample   at t the point is p_A = o_A + t*u_A.  Per axis s = (p_A - xLo[A]) / dx; the sample is refused as OUTSIDE when
+ *            !(s >= -1e-6 && s <= (double)n + 1e-6), compared in double BEFORE any conversion to an integer -- the only guard
+ *            between a wild ray and a load; the tolerance takes in the rounding of a point that the clip has put on a wall.  Then
+ *            s = fmin(fmax(s, 0.), (double)n), i0 = min((int)floor(s), n - 1), t = s - (double)i0.  From here on the sample is
+ *            lsf_sample_points': its stencil (the joint rule), its band rule (with a mask every stencil point an interior point
+ *            with mask == 1, else the sample is OFF THE LIST and nothing of phi is read), its weights and its contraction.  At a
+ *            point with 0 <= s <= n on every axis a ray sample equals lsf_sample_points at that point with ==.
+ *   march    state: the reference (tr, er), the last on-list sample with e = v - iso; a flag gap, false at the start; a step
+ *            count.  The first sample is at t = t0; after each sample that does not end the ray the next one is at
+ *            tn = t + step, and if !(tn < t1) then tn = t1 and that sample is the LAST.  A sample, in this order:
+ *              OUTSIDE                         status LSF_CAST_MISS, thit = t.
+ *              off the list (mask only)        gap = true; step = skip*dx.
+ *              on the list, no reference yet   it becomes the reference, gap = false; e == 0: a hit at t (bracket [t, t], no
+ *                                              bisection, on to the full sample).
+ *              on the list, with a reference   a CROSSING when e == 0 || (e > 0) != (er > 0); NaN counts as not > 0.  A crossing
+ *                                              with gap set: status LSF_CAST_LOST -- the surface was crossed where the list has no
+ *                                              cells, the ray's version of info[3] of lsf_measure_band.  A crossing without:
+ *                                              the bracket is [ta, tb] = [tr, t], ea = er, eb = e, on to the refinement.  No
+ *                                              crossing: the sample becomes the reference, gap = false.
+ *              step (on the list)              step = fmin(fmax(safety*fabs(er), smin*dx), smax*dx), er the reference just set.
+ *              it was the LAST sample          status MISS, thit = t.
+ *              max_steps steps made already    status LSF_CAST_STEPS.  Otherwise one more step is counted.
+ *            So a ray takes the first sample and at most max_steps further ones.
+ *   refine   `refine` times: tm = 0.5*(ta + tb), sample there; refused (OUTSIDE or off the list): LOST; em = v - iso; when
+ *            em == 0 || (em > 0) != (ea > 0) then tb = tm, eb = em, else ta = tm, ea = em.  Then quo = (ea*(tb - ta))/(eb - ea);
+ *            th = ta - quo when eb != ea and quo is finite, else th = ta; th = fmin(fmax(th, ta), tb).  One full sample at th,
+ *            with q where given: refused: LOST; else status LSF_CAST_HIT, thit = th, hit = o + th*u as sampled, grad and qval
+ *            that sample's.
+ *   outputs  a ray that is not HIT holds NaN in hit, grad and qval; thit is NaN for BAD, NOGRID, LOST and STEPS and the end of the
+ *            march for MISS.  Every entry of every output given is written.
+ *   info     [0..5] rays with status HIT, MISS, NOGRID, BAD, LOST, STEPS -- they add up to nrays; [6] samples of phi taken (every
+ *            on-list sample of the march and the refinement and the full sample of a HIT); [7] off-list strides (off-list samples
+ *            of the march); [8] rays that began on the inner side (e < 0 at their first reference).  Integer counts: no order of
+ *            summation enters them.  Written on LSF_OK only.
+ *   errors   LSF_ERR_INVALID, all detected before any output is written: a NULL phi, org, dir, thit or xLo; nrays < 1; nx, ny or
+ *            nz < 1 or more than 2^31 - 1 points; dx or xLo not finite, dx <= 0; iso not finite; an unknown order; tmin not finite
+ *            or < 0; tmax not finite or <= tmin; safety outside (0, 1]; smin not finite or <= 0; smax not finite or < smin; skip
+ *            not finite or <= 0 (looked at with or without a mask); refine < 0; max_steps < 1; qval without q; any output sharing
+ *            a byte with another output or with an input.  A non-finite phi or q VALUE is not an error: NaN is "not > 0".
+ *            No device: LSF_ERR_NO_DEVICE -- there is no CPU fallback, no mode word, one arithmetic.
+ *   seams    lsf_sample_points' own: phi through its twin under lsf_mirror, the mask as lsf_curvature_band takes it, q in a slot
+ *            of its own and never copied back; org, dir and the outputs are staged per call and the outputs come home on LSF_OK
+ *            only.  lsf_cast_rays_device returns after the stream is synchronised (the host finishes the block counts).
+ * Guidance: where phi is a distance, safety <= 1 cannot step over the surface and smin bounds the work next to a grazing ray;
+ * smax = 1 keeps a step inside the cells the last sample saw where phi is no distance.  skip <= the band's half width in cells
+ * cannot jump a band.  A ray that starts inside the body (info[8]) hits the surface from within: thit is then the way OUT.
+ * Accuracy (the statement on phi = |x| - 0.25 over [-0.5, 0.5]^3, 400 rays from outside the box aimed into the body, safety 0.9,
+ * smin 0.05, smax 1, refine 30; 13^3 / 25^3 / 49^3 grid points; largest |thit - analytic| / dx, measured):
+ * linear 1.39e-1 / 6.28e-2 / 3.29e-2, cubic 7.89e-3 / 1.58e-3 / 5.05e-4; as a length the linear error falls 4.4 x and 3.8 x per halving.
+ * Work: one launch; 8 or 64 gathered loads per sample (the mask as many, 8 for most off-list strides); a wave runs as long as its longest ray.  Workspace:
+ * 72 bytes per 256 rays; the host seam adds one field for q and 116 bytes per ray.  Out of scope: fp32, multi-GPU, secondary rays
+ * and flux integrals over a hemisphere (a caller loops over directions), exact cell-by-cell traversal with the root of the cubic
+ * along the ray, sorting rays for coherence, all hits of a ray instead of the first.
+ * Timed once on one MI355X on a 512 x 512 pinhole image of two spheres (exact distance; 40 % of the rays hit), without a mask with
+ * smax = 1 / smax = 8 / with the mask |phi| < 8.1 dx and skip = 4, beside lsf_sample_points with iters = 3 on as many points
+ * (profiles/cast_rays_time.txt, from profiles/micro/cast_rays_time.py; device seam, ms per call, samples of phi per ray in
+ * brackets): at 256^3 linear 0.857 [203] / 0.444 [39] / 0.542 [21 and 46 strides] against 0.066, cubic 1.866 / 0.996 / 1.440
+ * against 0.081; at 512^3 linear 1.611 [393] / 0.662 [63] / 0.865 [20 and 94 strides] against 0.069, cubic 3.883 / 1.753 / 2.150
+ * against 0.088.  The band rule is read with its loads side by side, not with lsf_sample_points' early exit.
+ * No speed is claimed beyond that record. */
+#define LSF_CAST_INFO_LEN 9
+#define LSF_CAST_HIT 0 /* status[r] */
+#define LSF_CAST_MISS 1
+#define LSF_CAST_NOGRID 2
+#define LSF_CAST_BAD 3
+#define LSF_CAST_LOST 4
+#define LSF_CAST_STEPS 5
+int lsf_cast_rays(const double *phi, const int32_t *mask, const double *q, int nx, int ny, int nz, double dx, const double xLo[3],
+                  const double *org, const double *dir, int nrays, int order, double iso, double tmin, double tmax, double safety,
+                  double smin, double smax, double skip, int refine, int max_steps, double *thit, double *hit, double *grad,
+                  double *qval, int32_t *status, int64_t info[LSF_CAST_INFO_LEN]);
+int lsf_cast_rays_device(const double *d_phi, const int32_t *d_mask, const double *d_q, int nx, int ny, int nz, double dx,
+                         const double xLo[3], const double *d_org, const double *d_dir, int nrays, int order, double iso, double tmin,
+                         double tmax, double safety, double smin, double smax, double skip, int refine, int max_steps,
+                         double *d_thit, double *d_hit, double *d_grad, double *d_qval, int32_t *d_status,
+                         int64_t info[LSF_CAST_INFO_LEN], void *stream);
+
 /* ---- connected components of the level set on the cells of a caller's mask ----------
  * No reference counterpart.  How many bodies there are, which cell belongs to which, and whether two have merged or one has pinched
  * off: the 6-connected components of the list cells on either side of phi = iso, a pure graph problem on the cell list every band

@@ -29,6 +29,8 @@ LSF_SURF_INFO_LEN = 4  # include/lsf.h: lsf_extract_surface
 LSF_MEASURE_LEN, LSF_MEASURE_INFO_LEN = 9, 5  # include/lsf.h: lsf_measure_band
 LSF_SAMPLE_LINEAR, LSF_SAMPLE_CUBIC, LSF_SAMPLE_INFO_LEN = 0, 1, 6  # include/lsf.h: lsf_sample_points
 LSF_SAMPLE_OK, LSF_SAMPLE_OUTSIDE, LSF_SAMPLE_OFFBAND, LSF_SAMPLE_FLAT, LSF_SAMPLE_NOT_CONVERGED = 0, 1, 2, 3, 4  # ... its status[t]
+LSF_CAST_INFO_LEN = 9  # include/lsf.h: lsf_cast_rays
+LSF_CAST_HIT, LSF_CAST_MISS, LSF_CAST_NOGRID, LSF_CAST_BAD, LSF_CAST_LOST, LSF_CAST_STEPS = 0, 1, 2, 3, 4, 5  # ... its status[r]
 LSF_LABEL_INSIDE, LSF_LABEL_OUTSIDE, LSF_LABEL_BOTH = 0, 1, 2  # include/lsf.h: lsf_label_band
 LSF_LABEL_COMP_LEN, LSF_LABEL_INFO_LEN = 10, 8
 LSF_EXTEND_INFO_LEN = 3  # include/lsf.h: lsf_extend_field
@@ -122,6 +124,12 @@ SIGNATURES = {
                                   c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsf_sample_points_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int, c_double,
                                          c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsf_cast_rays": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                              c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p]),
+    "lsf_cast_rays_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                     c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsf_label_band": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int,
                                POINTER(ctypes.c_int64), c_void_p]),
     "lsf_label_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int,

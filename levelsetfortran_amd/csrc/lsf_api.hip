@@ -36,6 +36,7 @@
 #include "lsf_extract_surface.hpp"
 #include "lsf_measure_band.hpp"
 #include "lsf_sample_points.hpp"
+#include "lsf_cast_rays.hpp"
 #include "lsf_label_band.hpp"
 
 using namespace lsf;
@@ -193,7 +194,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_CR_Q, S_CR_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -753,6 +754,7 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_measure_band.hpp"
 
 #include "lsf_host_sample_points.hpp"
+#include "lsf_host_cast_rays.hpp"
 
 #include "lsf_host_label_band.hpp"
 
@@ -1908,6 +1910,71 @@ int lsf_sample_points(const double* phi, const int32_t* mask, const double* q, i
     if (qval) HIPCHK(hipMemcpy(qval, d_qval, np * sizeof(double), hipMemcpyDeviceToHost));
     if (foot) HIPCHK(hipMemcpy(foot, d_foot, 3 * np * sizeof(double), hipMemcpyDeviceToHost));
     if (status) HIPCHK(hipMemcpy(status, d_status, np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return LSF_OK;
+}
+
+int lsf_cast_rays_device(const double* d_phi, const int32_t* d_mask, const double* d_q, int nx, int ny, int nz, double dx, const double xLo[3],
+                         const double* d_org, const double* d_dir, int nrays, int order, double iso, double tmin, double tmax, double safety, double smin,
+                         double smax, double skip, int refine, int max_steps, double* d_thit, double* d_hit, double* d_grad, double* d_qval,
+                         int32_t* d_status, int64_t info[LSF_CAST_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_cast_rays_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = cast_rays_args_ok(d_phi, d_mask, d_q, nx, ny, nz, dx, xLo, d_org, d_dir, nrays, order, iso, tmin, tmax, safety, smin, smax, skip, refine,
+                                max_steps, d_thit, d_hit, d_grad, d_qval, d_status)))
+        return rc;
+    return cast_rays_core(d_phi, d_mask, d_q, nx, ny, nz, dx, xLo, d_org, d_dir, nrays, order, iso, tmin, tmax, safety, smin, smax, skip, refine,
+                          max_steps, d_thit, d_hit, d_grad, d_qval, d_status, info, (hipStream_t)stream);
+}
+
+int lsf_cast_rays(const double* phi, const int32_t* mask, const double* q, int nx, int ny, int nz, double dx, const double xLo[3], const double* org,
+                  const double* dir, int nrays, int order, double iso, double tmin, double tmax, double safety, double smin, double smax, double skip,
+                  int refine, int max_steps, double* thit, double* hit, double* grad, double* qval, int32_t* status, int64_t info[LSF_CAST_INFO_LEN])
+{
+    Trace trace_("lsf_cast_rays");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = cast_rays_args_ok(phi, mask, q, nx, ny, nz, dx, xLo, org, dir, nrays, order, iso, tmin, tmax, safety, smin, smax, skip, refine, max_steps,
+                                thit, hit, grad, qval, status)))
+        return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double), nr = (size_t)nrays;
+    // q is an input only: into a slot of its own, as lsf_sample_points stages its q, and never copied back.  Staged before phi's twin is
+    // touched.
+    const double* d_q = nullptr;
+    if (q) {
+        if ((rc = ws(c.slot[S_CR_Q], bytes))) return rc;
+        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, q, bytes) : nullptr;
+        HIPCHK(hipMemcpy(c.slot[S_CR_Q].p, twin ? twin : (const void*)q, bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        d_q = (const double*)c.slot[S_CR_Q].p;
+    }
+    // org, dir and the outputs are staged per call in one slot: org(3), dir(3), thit(1), hit(3), grad(3), qval(1) doubles per ray, then
+    // status.  The kernel writes every entry of every output, so nothing is copied in but org and dir; the outputs come home on LSF_OK only.
+    if ((rc = ws(c.slot[S_CR_IO], nr * (14 * sizeof(double) + sizeof(int32_t))))) return rc;
+    double* io = (double*)c.slot[S_CR_IO].p;
+    double *d_org = io, *d_dir = io + 3 * nr, *d_thit = io + 6 * nr, *d_hit = hit ? io + 7 * nr : nullptr, *d_grad = grad ? io + 10 * nr : nullptr,
+           *d_qval = qval ? io + 13 * nr : nullptr;
+    int32_t* d_status = status ? (int32_t*)(io + 14 * nr) : nullptr;
+    HIPCHK(hipMemcpy(d_org, org, 3 * nr * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_dir, dir, 3 * nr * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_sample_points
+    const int32_t* d_mask = nullptr;
+    if (mask) { // as in lsf_curvature_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
+        const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+        Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+        const Slot sm = is_nb ? S_HNB : S_HSB;
+        if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
+        d_mask = (const int32_t*)c.slot[sm].p;
+    }
+    if ((rc = cast_rays_core((const double*)c.slot[S_HPHI].p, d_mask, d_q, nx, ny, nz, dx, xLo, d_org, d_dir, nrays, order, iso, tmin, tmax, safety, smin,
+                             smax, skip, refine, max_steps, d_thit, d_hit, d_grad, d_qval, d_status, info, nullptr)))
+        return rc;
+    HIPCHK(hipMemcpy(thit, d_thit, nr * sizeof(double), hipMemcpyDeviceToHost));
+    if (hit) HIPCHK(hipMemcpy(hit, d_hit, 3 * nr * sizeof(double), hipMemcpyDeviceToHost));
+    if (grad) HIPCHK(hipMemcpy(grad, d_grad, 3 * nr * sizeof(double), hipMemcpyDeviceToHost));
+    if (qval) HIPCHK(hipMemcpy(qval, d_qval, nr * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, d_status, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
     return LSF_OK;
 }
 

@@ -40,6 +40,10 @@
 !   samplePoints(phi,nx,ny,nz,dx,xLo,pts,npts,order,     no reference counterpart: phi, its gradient and the foot point on
 !                iso,iters,tol,val,grad,foot,status      phi = iso at arbitrary points, trilinear or Catmull-Rom; optionally a
 !                [,mask,q,qval])                         second field q and a band mask (include/lsf.h: lsf_sample_points)
+!   castRays(phi,nx,ny,nz,dx,xLo,org,dir,nrays,order,    no reference counterpart: the first hit of each ray with phi = iso,
+!            iso,tmin,tmax,safety,smin,smax,skip,        marching by the field's own value and skipping what a band mask does
+!            refine,max_steps,thit,hit,grad,status       not hold; optionally a second field q sampled at the hit
+!            [,mask,q,qval])                             (include/lsf.h: lsf_cast_rays)
 !   labelBand(phi,mask,label,nx,ny,nz,iso,side,ncomp)    no reference counterpart: the connected components of the cells with
 !                                                        mask == 1 on either side of phi = iso (include/lsf.h: lsf_label_band)
 !   extendFieldBand(q,phi,mask,nx,ny,nz,dx,band)         no reference counterpart: extendField on the cells with mask == 1
@@ -117,6 +121,7 @@ PUBLIC :: evolveBandCurv
 PUBLIC :: curvatureBand
 PUBLIC :: measureBand
 PUBLIC :: samplePoints
+PUBLIC :: castRays
 PUBLIC :: labelBand
 PUBLIC :: extendFieldBand
 PUBLIC :: extractSurface, stlWrite
@@ -372,6 +377,21 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: info(6)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_sample_points
+   ! int lsf_cast_rays(const double*,const int32_t*,const double*,int,int,int,double,const double[3],const double*,const double*,int,int,
+   !                   double,double,double,double,double,double,double,int,int,double*,double*,double*,double*,int32_t*,int64_t[9])
+   FUNCTION lsf_cast_rays(phi,mask,q,nx,ny,nz,dx,xLo,org,dir,nrays,order,iso,tmin,tmax,safety,smin,smax,skip,refine,max_steps, &
+                          thit,hit,grad,qval,status,info) BIND(C,NAME='lsf_cast_rays') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(IN) :: phi(*),xLo(3),org(*),dir(*)
+      TYPE(c_ptr), VALUE :: mask,q           ! NULL: no band, no second field
+      INTEGER(c_int), VALUE :: nx,ny,nz,nrays,order,refine,max_steps
+      REAL(c_double), VALUE :: dx,iso,tmin,tmax,safety,smin,smax,skip
+      REAL(c_double), INTENT(OUT) :: thit(*),hit(*),grad(*)
+      TYPE(c_ptr), VALUE :: qval             ! NULL: not wanted (qval needs q)
+      INTEGER(c_int), INTENT(OUT) :: status(*)
+      INTEGER(c_int64_t), INTENT(OUT) :: info(9)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_cast_rays
    ! int lsf_extend_field_band(double*,const double*,const int32_t*,const int32_t*,int,int,int,double,double,int,int*,int64_t*,int,
    !                           int64_t[4])
    FUNCTION lsf_extend_field_band(q,phi,mask,known,nx,ny,nz,dx,band,max_passes,passes_done,changed_trace,trace_cap,info) &
@@ -1178,6 +1198,55 @@ IF (iters >= 1) PRINT*, " Samples: flat ",info(5),", not converged ",info(6)
 PRINT*
 
 END SUBROUTINE samplePoints
+
+!*************************************************************************************!
+! The first hit of a ray with the level set (include/lsf.h: lsf_cast_rays; no reference
+! counterpart): ray r starts at org(r,:) and runs along dir(r,:), any length -- the
+! layout of surfX, so the nodes of extractSurface and grad of samplePoints plug in.  It
+! is followed from the length tmin to tmax in steps of safety*|phi - iso|, kept between
+! smin and smax cells, over the interpolant of samplePoints (order = 0 trilinear, 1
+! Catmull-Rom); the first sign change is bisected refine times.  thit(r): the length to
+! the hit; hit(r,:), grad(r,:): the point and the gradient there.  status(r): 0 hit,
+! 1 miss, 2 the ray does not meet the grid, 3 not a ray, 4 lost (the surface was crossed
+! where the list has no cells), 5 more than max_steps steps; a ray that is not hit holds
+! NaN.  mask: only stencils of interior points with mask == 1 are sampled, the rest is
+! crossed in strides of skip cells.  q, qval: a second field and its values at the hits.
+! phi, mask, q, org and dir are read only.  Prints the counts.
+!*************************************************************************************!
+SUBROUTINE castRays(phi,nx,ny,nz,dx,xLo,org,dir,nrays,order,iso,tmin,tmax,safety,smin,smax,skip,refine,max_steps, &
+                    thit,hit,grad,status,mask,q,qval)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,order,refine,max_steps
+INTEGER*4,INTENT(IN) :: nrays
+REAL,INTENT(IN) :: dx,xLo(3),iso,tmin,tmax,safety,smin,smax,skip
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+REAL,INTENT(IN) :: org(nrays,3),dir(nrays,3)
+REAL,INTENT(OUT) :: thit(nrays),hit(nrays,3),grad(nrays,3)
+INTEGER*4,INTENT(OUT) :: status(nrays)
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN),OPTIONAL,TARGET :: mask
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN),OPTIONAL,TARGET :: q
+REAL,INTENT(OUT),OPTIONAL,TARGET :: qval(nrays)
+TYPE(c_ptr) :: pm,pq,pqv
+INTEGER(c_int64_t) :: info(9)
+INTEGER(c_int) :: rc
+
+pm = c_null_ptr
+pq = c_null_ptr
+pqv = c_null_ptr
+IF (PRESENT(mask)) pm = C_LOC(mask)
+IF (PRESENT(q)) pq = C_LOC(q)
+IF (PRESENT(qval)) pqv = C_LOC(qval)
+info = 0
+CALL lsf_set_mirror()
+rc = lsf_cast_rays(phi,pm,pq,nx,ny,nz,dx,xLo,org,dir,nrays,order,iso,tmin,tmax,safety,smin,smax,skip,refine,max_steps, &
+                   thit,hit,grad,pqv,status,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_cast_rays',rc)
+PRINT*, " Rays: rays ",nrays,", hit ",info(1),", miss ",info(2),", no grid ",info(3)
+PRINT*, " Rays: bad ",info(4),", lost ",info(5),", out of steps ",info(6)
+PRINT*, " Rays: samples ",info(7),", strides ",info(8),", began inside ",info(9)
+PRINT*
+
+END SUBROUTINE castRays
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

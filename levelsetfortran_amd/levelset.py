@@ -38,6 +38,10 @@ and the field, its gradient, a second field and the foot point on the surface at
 
   samplePoints(phi, nx, ny, nz, dx, xLo, pts, ...)              include/lsf.h: lsf_sample_points
 
+and the first hit of a ray with the surface, marching by the field's own value and skipping what a band mask does not hold:
+
+  castRays(phi, nx, ny, nz, dx, xLo, org, dir, ...)             include/lsf.h: lsf_cast_rays
+
 and how many bodies there are and which cell belongs to which, the connected components on the cells of a mask:
 
   labelBand(phi, mask, nx, ny, nz, label, ...)                  include/lsf.h: lsf_label_band
@@ -68,7 +72,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "castRays", "CastReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -1147,6 +1151,107 @@ def samplePoints(phi, nx: int, ny: int, nz: int, dx: float, xLo, pts, *, order: 
                                    ptr(val), ptr(grad), ptr(qval), ptr(foot), ptr(status), info.ctypes.data)
     _lib.check(rc)
     return SampleReport(val, grad, qval, foot, status, tuple(int(v) for v in info))
+
+
+class CastReport(NamedTuple):
+    """What lsf_cast_rays returns (include/lsf.h): `thit` (nrays; the length along the ray to the hit, the end of the march for a MISS,
+    NaN otherwise), `hit` (nrays, 3; None with want_hit=False), `grad` (nrays, 3; None with want_grad=False), `qval` (nrays; None
+    without q), `status` (nrays, int32: 0 HIT, 1 MISS, 2 NOGRID, 3 BAD, 4 LOST, 5 STEPS) and `info`, the nine counts [HIT, MISS, NOGRID,
+    BAD, LOST, STEPS, samples of phi taken, off-list strides, rays that began on the inner side].  The (nrays, 3) arrays are
+    Fortran-ordered, the layout of surfX."""
+    thit: object
+    hit: object
+    grad: object
+    qval: object
+    status: object
+    info: tuple
+
+
+def castRays(phi, nx: int, ny: int, nz: int, dx: float, xLo, org, dir, *, order: str = "cubic", mask=None, q=None, iso: float = 0.0,
+             tmin: float = 0.0, tmax: float = 1e30, safety: float = 0.9, smin: float = 0.05, smax: float = 1.0, skip: float = 1.0,
+             refine: int = 24, max_steps: int = 4096, want_hit: bool = True, want_grad: bool = True) -> CastReport:
+    """The first hit of each ray org + t * dir / |dir|, tmin <= t <= tmax, with the level set phi = iso (include/lsf.h: lsf_cast_rays):
+    a march in steps of safety * |phi - iso|, kept between smin and smax cells, over the interpolant of samplePoints (order="linear"
+    or "cubic"), `refine` bisections of the first sign change and one secant step.
+
+    org, dir: (nrays, 3) float64 in Fortran order -- what extractSurface returns as surfX and samplePoints as grad plug in; they are
+    never written.  mask: int32 field; where a sample's stencil leaves the interior points with mask == 1 the ray strides on by
+    `skip` cells without reading phi, and a sign change found across such a gap is reported as LOST, never as a hit.  q: a second
+    field, sampled at the hit.  A ray that is not HIT holds NaN in hit, grad and qval.  More than max_steps steps: status STEPS.
+    Numpy in gives numpy out (host seam); CUDA tensors in give CUDA tensors out (device seam, on the tensor's current stream).
+    """
+    lo = np.ascontiguousarray(xLo, dtype=np.float64)
+    if lo.shape != (3,) or not np.all(np.isfinite(lo)):
+        raise ValueError("xLo must hold 3 finite values")
+    dx, iso, tmin, tmax, safety, smin, smax, skip = (float(v) for v in (dx, iso, tmin, tmax, safety, smin, smax, skip))
+    refine, max_steps = int(refine), int(max_steps)
+    if not (np.isfinite(dx) and dx > 0.0):
+        raise ValueError("dx must be finite and > 0")
+    if not np.isfinite(iso):
+        raise ValueError("iso must be finite")
+    if order not in _SAMPLE_ORDERS:
+        raise ValueError("order must be 'linear' or 'cubic'")
+    if not (np.isfinite(tmin) and tmin >= 0.0 and np.isfinite(tmax) and tmax > tmin):
+        raise ValueError("tmin must be finite and >= 0, tmax finite and > tmin")
+    if not (0.0 < safety <= 1.0):
+        raise ValueError("safety must lie in (0, 1]")
+    if not (np.isfinite(smin) and smin > 0.0 and np.isfinite(smax) and smax >= smin):
+        raise ValueError("smin must be finite and > 0, smax finite and >= smin")
+    if not (np.isfinite(skip) and skip > 0.0):
+        raise ValueError("skip must be finite and > 0")
+    if refine < 0 or max_steps < 1:
+        raise ValueError("refine must be >= 0 and max_steps >= 1")
+    if min(int(nx), int(ny), int(nz)) < 1:
+        raise ValueError("nx, ny, nz must be >= 1")
+    dev = _is_torch(phi)
+    opt = [(n, a) for n, a in (("mask", mask), ("q", q)) if a is not None]
+    rays = [("org", org), ("dir", dir)]
+    if any(_is_torch(a) != dev for _, a in opt + rays):
+        raise TypeError("phi, mask, q, org and dir must all be numpy arrays or all be CUDA tensors")
+    if len(org.shape) != 2 or org.shape[1] != 3 or org.shape[0] < 1 or tuple(dir.shape) != tuple(org.shape):
+        raise ValueError("org and dir must have one shape (nrays, 3) with nrays >= 1")
+    nrays = int(org.shape[0])
+    lib = _lib.load()
+    info = np.zeros(_lib.LSF_CAST_INFO_LEN, dtype=np.int64)
+    par = (nrays, _SAMPLE_ORDERS[order], iso, tmin, tmax, safety, smin, smax, skip, refine, max_steps)
+    if dev:
+        import torch
+
+        if any(a.device != phi.device for _, a in opt + rays):
+            raise ValueError("phi, mask, q, org and dir must live on one device")
+        for name, a in rays:
+            if not a.is_cuda or a.dtype != torch.float64 or not a.t().is_contiguous():
+                raise TypeError(f"{name} must be a float64 CUDA tensor of shape (nrays, 3) in Fortran order (the transpose of a contiguous (3, nrays))")
+        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        m = None if mask is None else _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+        qq = None if q is None else _dev_ptr(q, torch.float64, nx, ny, nz, "q")
+        vec = lambda: torch.empty((3, nrays), dtype=torch.float64, device=phi.device).t()
+        thit = torch.empty(nrays, dtype=torch.float64, device=phi.device)
+        status = torch.empty(nrays, dtype=torch.int32, device=phi.device)
+        hit = vec() if want_hit else None
+        grad = vec() if want_grad else None
+        qval = torch.empty(nrays, dtype=torch.float64, device=phi.device) if q is not None else None
+        ptr = lambda a: None if a is None else a.data_ptr()
+        rc = lib.lsf_cast_rays_device(p, m, qq, nx, ny, nz, dx, lo.ctypes.data, org.data_ptr(), dir.data_ptr(), *par, ptr(thit), ptr(hit),
+                                      ptr(grad), ptr(qval), ptr(status), info.ctypes.data, _stream_and_device(phi))
+    else:
+        for name, a in rays:
+            if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.f_contiguous:
+                raise TypeError(f"{name} must be a Fortran-ordered float64 numpy array of shape (nrays, 3)")
+        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
+        m = None if mask is None else _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+        qq = None if q is None else _host_ptr(q, np.float64, nx, ny, nz, "q")
+        vec = lambda: np.zeros((nrays, 3), dtype=np.float64, order="F")
+        thit = np.zeros(nrays, dtype=np.float64)
+        status = np.zeros(nrays, dtype=np.int32)
+        hit = vec() if want_hit else None
+        grad = vec() if want_grad else None
+        qval = np.zeros(nrays, dtype=np.float64) if q is not None else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = lib.lsf_cast_rays(p, m, qq, nx, ny, nz, dx, lo.ctypes.data, org.ctypes.data, dir.ctypes.data, *par, ptr(thit), ptr(hit), ptr(grad),
+                               ptr(qval), ptr(status), info.ctypes.data)
+    _lib.check(rc)
+    return CastReport(thit, hit, grad, qval, status, tuple(int(v) for v in info))
 
 
 class SurfaceInfo(NamedTuple):
