@@ -461,14 +461,8 @@ BcWhole bc_whole(int nx, int ny, int nz)
     return w;
 }
 
-int check_dims(int nx, int ny, int nz)
-{
-    if (nx < 2 || ny < 2 || nz < 2) return fail(LSF_ERR_INVALID, "nx, ny, nz must be >= 2");
-    if ((double)(nx + 1) * (ny + 1) * (nz + 1) > 9.0e9) return fail(LSF_ERR_INVALID, "field too large");
-    // the Jacobi kernels address one k-plane through a buffer descriptor with 32-bit byte offsets
-    if ((double)(nx + 1) * (ny + 1) * 8.0 > 2.0e9) return fail(LSF_ERR_INVALID, "a k-plane of the field exceeds 2 GB");
-    return LSF_OK;
-}
+// check_dims and the *_args_ok of every call: pure host code, run on the CPU by tests/test_host_args_cpu.py
+#include "lsf_host_args.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // One fp64 Jacobi sweep over the cells [lo, hi) of a box: picks the kernel and its launch geometry.
@@ -995,6 +989,83 @@ const void* twin_of(Ctx& c, const void* host, size_t bytes, Twin** which = nullp
     return nullptr;
 }
 
+// ---- the seam routines: what a host seam does with each kind of array, each rule stated once --------------
+// A seam calls them in this order: input-only fields and twin-less arrays first (an input may be the very array a twin stands for,
+// phi's included, and taking a twinned slot may send another array's un-synced result home), then phi, then the mask.
+
+// The mask of a band call is an input and is never copied back: it goes through the twin of phiNB when it IS the array that twin stands
+// for, with that size (the narrow band as the update mask), through the twin of phiSB otherwise (the stencil band, or any other array).
+// A NULL (optional) mask gives a NULL device pointer and touches nothing.  `which` / `slot`: for the one caller that writes its mask.
+int mask_in(Ctx& c, const int32_t* mask, size_t n, const int32_t** d_mask, Twin** which = nullptr, Slot* slot = nullptr)
+{
+    *d_mask = nullptr;
+    if (!mask) return LSF_OK;
+    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
+    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
+    const Slot sm = is_nb ? S_HNB : S_HSB;
+    const int rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t));
+    if (rc) return rc;
+    *d_mask = (const int32_t*)c.slot[sm].p;
+    if (which) *which = &tm;
+    if (slot) *slot = sm;
+    return LSF_OK;
+}
+// An input-only field (a velocity, a speed, a quantity q) goes into a slot of its own and is never copied back.  Its source is the
+// device twin where the caller lets twins be trusted (lsf_mirror TRUST / LAZY: under LAZY the host copy may be the older one) and the
+// array has a current one, the host otherwise -- without lsf_mirror the host copy is the truth: an address may have been a twin's in
+// an earlier call and hold other values now.  A NULL field gives a NULL device pointer.
+int input_in(Ctx& c, Slot slot, const double* host, size_t bytes, const double** d)
+{
+    *d = nullptr;
+    if (!host) return LSF_OK;
+    const int rc = ws(c.slot[slot], bytes);
+    if (rc) return rc;
+    const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, host, bytes) : nullptr;
+    HIPCHK(hipMemcpy(c.slot[slot].p, twin ? twin : (const void*)host, bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    *d = (const double*)c.slot[slot].p;
+    return LSF_OK;
+}
+// ... the velocity and the speed of the transport calls: d_in = {u, v, w, speed}
+int velocity_in(Ctx& c, const double* u, const double* v, const double* w, const double* speed, size_t bytes, const double* d_in[4])
+{
+    const double* h_in[4] = {u, v, w, speed};
+    const Slot s_in[4] = {S_AF_U, S_AF_V, S_AF_W, S_AF_F};
+    for (int q = 0; q < 4; ++q) {
+        const int rc = input_in(c, s_in[q], h_in[q], bytes, &d_in[q]);
+        if (rc) return rc;
+    }
+    return LSF_OK;
+}
+// An array without a twin (an output that keeps what it held off the list, or an int32 input) is copied from the host into a slot of
+// its own on every call, lsf_mirror or not.  Its way home is a hipMemcpy at the call site, on the return codes that call brings it
+// home on.  A NULL array gives a NULL device pointer.
+template <typename T>
+int stage_in(Ctx& c, Slot slot, const T* host, size_t bytes, T** d)
+{
+    *d = nullptr;
+    if (!host) return LSF_OK;
+    const int rc = ws(c.slot[slot], bytes);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(c.slot[slot].p, host, bytes, hipMemcpyHostToDevice));
+    *d = (T*)c.slot[slot].p;
+    return LSF_OK;
+}
+// The way home of phi after a call that wrote it in its slot and returned rc.  LSF_OK and LSF_ERR_NAN: the slot holds a result, which
+// comes home (or stays as an un-synced twin, LSF_MIRROR_LAZY) with the call's own message kept.  Anything else: the slot is undefined
+// and the twin is dropped -- except, with `invalid_keeps`, on LSF_ERR_INVALID of a call that finds every invalid input before it writes:
+// the twin stays what it was.  Returns rc, or the error of the copy.
+int phi_home(Ctx& c, double* phi, size_t bytes, int rc, bool invalid_keeps)
+{
+    if (rc == LSF_OK || rc == LSF_ERR_NAN) {
+        const std::string keep = g_err;
+        const int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
+        if (rc2) return rc2;
+        g_err = keep;
+    } else if (!(invalid_keeps && rc == LSF_ERR_INVALID))
+        twin_drop(c.twin_phi);
+    return rc;
+}
+
 __global__ __launch_bounds__(256) void k_sumsq_diff(const double* __restrict__ a, const double* __restrict__ b, long n,
                                                     double* __restrict__ partials)
 {
@@ -1172,14 +1243,7 @@ int lsf_reinit(double* phi, int nx, int ny, int nz, int iter, double dx, double 
     if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc;
     double* d = (double*)c.slot[S_HPHI].p;
     rc = reinit_core(d, nullptr, nx, ny, nz, iter, dx, h, tol, mode, 0, sweeps_done, rms_trace, trace_cap, nullptr);
-    if (rc == LSF_OK || rc == LSF_ERR_NAN) {
-        const std::string keep = g_err;
-        const int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
-        if (rc2) return rc2;
-        g_err = keep;
-    } else
-        twin_drop(c.twin_phi);
-    return rc;
+    return phi_home(c, phi, bytes, rc, false);
 }
 
 int lsf_minmax_device(double* d_phi, int32_t* d_phiNB, int32_t* d_phiSB, int nx, int ny, int nz, int iter,
@@ -1243,23 +1307,12 @@ int lsf_reinit_band(double* phi, const int32_t* mask, int nx, int ny, int nz, in
     if (!mask) return fail(LSF_ERR_INVALID, "mask is NULL");
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    const int32_t* d_mask;
     if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc;
-    // the mask is an input only: it travels through the twin of phiNB when it IS the array that twin stands for (the narrow band
-    // as the update mask), through the twin of phiSB otherwise (the stencil band, or any other array); never copied back
-    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-    const Slot sm = is_nb ? S_HNB : S_HSB;
-    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-    rc = reinit_band_core((double*)c.slot[S_HPHI].p, nullptr, (const int32_t*)c.slot[sm].p, nx, ny, nz, iter, dx, h, tol, mode, sweeps_done,
-                          rms_trace, trace_cap, nullptr);
-    if (rc == LSF_OK || rc == LSF_ERR_NAN) {
-        const std::string keep = g_err;
-        const int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, n * sizeof(double));
-        if (rc2) return rc2;
-        g_err = keep;
-    } else
-        twin_drop(c.twin_phi);
-    return rc;
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    rc = reinit_band_core((double*)c.slot[S_HPHI].p, nullptr, d_mask, nx, ny, nz, iter, dx, h, tol, mode, sweeps_done, rms_trace, trace_cap,
+                          nullptr);
+    return phi_home(c, phi, n * sizeof(double), rc, false);
 }
 
 int lsf_narrowband_device(const double* d_phi, int32_t* d_phiNB, int32_t* d_phiSB, int nx, int ny, int nz,
@@ -1430,20 +1483,12 @@ int lsf_distance_fill(double* phi, const int32_t* mask, int nx, int ny, int nz, 
     if ((rc = distance_fill_args_ok(phi, mask, nx, ny, nz, dx, band, max_rounds))) return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    const int32_t* d_mask;
     if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc;
-    // the mask is an input only and travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin
-    // of phiSB otherwise; never copied back
-    const int32_t* d_mask = nullptr;
-    if (mask) {
-        const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-        Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-        const Slot sm = is_nb ? S_HNB : S_HSB;
-        if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-        d_mask = (const int32_t*)c.slot[sm].p;
-    }
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
     rc = distance_fill_core((double*)c.slot[S_HPHI].p, d_mask, nx, ny, nz, dx, band, max_rounds, rounds_done, changed_trace, trace_cap,
                             frozen_points, nullptr);
-    if (rc == LSF_OK) return twin_out(c, c.twin_phi, S_HPHI, phi, n * sizeof(double));
+    if (rc == LSF_OK) return twin_out(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)); // (not phi_home: phi comes home on LSF_OK alone)
     twin_drop(c.twin_phi);
     return rc;
 }
@@ -1469,23 +1514,15 @@ int lsf_extend_field(double* q, const double* phi, const int32_t* mask, int nx, 
     if ((rc = extend_field_args_ok(q, phi, mask, nx, ny, nz, dx, band, max_rounds))) return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-    // q has no twin: it is staged in a slot of its own from the host on every call and comes home on LSF_OK, lsf_mirror or not.
-    // Staged before phi's twin is touched, as lsf_advect_field stages its inputs.
-    if ((rc = ws(c.slot[S_EXT_Q], n * sizeof(double)))) return rc;
-    HIPCHK(hipMemcpy(c.slot[S_EXT_Q].p, q, n * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // phi is an input only, as in lsf_extract_surface
-    const int32_t* d_mask = nullptr;
-    if (mask) { // as in lsf_distance_fill
-        const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-        Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-        const Slot sm = is_nb ? S_HNB : S_HSB;
-        if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-        d_mask = (const int32_t*)c.slot[sm].p;
-    }
-    if ((rc = extend_field_core((double*)c.slot[S_EXT_Q].p, (const double*)c.slot[S_HPHI].p, d_mask, nx, ny, nz, dx, band, max_rounds,
-                                rounds_done, changed_trace, trace_cap, info, nullptr)))
+    double* d_q;
+    const int32_t* d_mask;
+    if ((rc = stage_in(c, S_EXT_Q, q, n * sizeof(double), &d_q))) return rc;        // q has no twin; home on LSF_OK
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // phi is an input only
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    if ((rc = extend_field_core(d_q, (const double*)c.slot[S_HPHI].p, d_mask, nx, ny, nz, dx, band, max_rounds, rounds_done, changed_trace,
+                                trace_cap, info, nullptr)))
         return rc;
-    HIPCHK(hipMemcpy(q, c.slot[S_EXT_Q].p, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(q, d_q, n * sizeof(double), hipMemcpyDeviceToHost));
     return LSF_OK;
 }
 
@@ -1513,35 +1550,15 @@ int lsf_advect_field(double* phi, const double* u, const double* v, const double
     if ((rc = advect_field_args_ok(phi, u, v, w, speed, nx, ny, nz, dx, dt, steps, scheme, mode))) return rc;
     Ctx& c = ctx();
     const size_t bytes = (size_t)(nx + 1) * (ny + 1) * (nz + 1) * sizeof(double);
-    // u, v, w, speed are inputs only and travel like the mask of lsf_reinit_band, never copied back: each into a slot of its own,
-    // from the device twin where the caller lets twins be trusted (lsf_mirror TRUST / LAZY: under LAZY the host copy may be the older
-    // one) and the array has a current one, from the host otherwise -- without lsf_mirror the host copy is the truth: an address may
-    // have been a twin's in an earlier call and hold other values now.  Staged before phi's twin is touched: an input may be the very
-    // array a twin stands for, phi's included.
-    const double* h_in[4] = {u, v, w, speed};
-    const Slot s_in[4] = {S_AF_U, S_AF_V, S_AF_W, S_AF_F};
-    const double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int q = 0; q < 4; ++q) {
-        if (!h_in[q]) continue;
-        if ((rc = ws(c.slot[s_in[q]], bytes))) return rc;
-        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, h_in[q], bytes) : nullptr;
-        HIPCHK(hipMemcpy(c.slot[s_in[q]].p, twin ? twin : (const void*)h_in[q], bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-        d_in[q] = (const double*)c.slot[s_in[q]].p;
-    }
+    const double* d_in[4];
+    if ((rc = velocity_in(c, u, v, w, speed, bytes, d_in))) return rc;
     if ((rc = advect_field_scan(d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, cfl, nullptr))) return rc;
     if (steps_done) *steps_done = 0;
-    if (steps == 0) return LSF_OK;
+    if (steps == 0) return LSF_OK; // (phi's twin is not touched)
     if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc;
     rc = advect_field_steps((double*)c.slot[S_HPHI].p, d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, steps, scheme, mode, steps_done,
                             change_trace, trace_cap, nullptr);
-    if (rc == LSF_OK || rc == LSF_ERR_NAN) {
-        const std::string keep = g_err;
-        const int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
-        if (rc2) return rc2;
-        g_err = keep;
-    } else
-        twin_drop(c.twin_phi);
-    return rc;
+    return phi_home(c, phi, bytes, rc, false);
 }
 
 int lsf_advect_field_band_device(double* d_phi, const int32_t* d_mask, const double* d_u, const double* d_v, const double* d_w,
@@ -1567,35 +1584,14 @@ int lsf_advect_field_band(double* phi, const int32_t* mask, const double* u, con
     if (!mask) return fail(LSF_ERR_INVALID, "lsf_advect_field_band: mask is NULL");
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
-    // u, v, w, speed travel as in lsf_advect_field: each into a slot of its own, from a current device twin under LSF_MIRROR_TRUST / LAZY,
-    // from the host otherwise; staged before phi's twin is touched
-    const double* h_in[4] = {u, v, w, speed};
-    const Slot s_in[4] = {S_AF_U, S_AF_V, S_AF_W, S_AF_F};
-    const double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int q = 0; q < 4; ++q) {
-        if (!h_in[q]) continue;
-        if ((rc = ws(c.slot[s_in[q]], bytes))) return rc;
-        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, h_in[q], bytes) : nullptr;
-        HIPCHK(hipMemcpy(c.slot[s_in[q]].p, twin ? twin : (const void*)h_in[q], bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-        d_in[q] = (const double*)c.slot[s_in[q]].p;
-    }
-    // phi and the mask travel as in lsf_reinit_band: the mask through the twin of phiNB when it IS that array, through the twin of phiSB
-    // otherwise; never copied back
+    const double* d_in[4];
+    const int32_t* d_mask;
+    if ((rc = velocity_in(c, u, v, w, speed, bytes, d_in))) return rc;
     if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc;
-    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-    const Slot sm = is_nb ? S_HNB : S_HSB;
-    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-    rc = advect_band_core((double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, steps,
-                          scheme, mode, steps_done, cfl, change_trace, trace_cap, info, margin, nullptr);
-    if (rc == LSF_OK || rc == LSF_ERR_NAN) {
-        const std::string keep = g_err;
-        const int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
-        if (rc2) return rc2;
-        g_err = keep;
-    } else if (rc != LSF_ERR_INVALID) // (an invalid call is found before the twin is written: it stays what it was)
-        twin_drop(c.twin_phi);
-    return rc;
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    rc = advect_band_core((double*)c.slot[S_HPHI].p, d_mask, d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, steps, scheme, mode,
+                          steps_done, cfl, change_trace, trace_cap, info, margin, nullptr);
+    return phi_home(c, phi, bytes, rc, true); // (the core finds an invalid input before it writes phi)
 }
 
 // the host seam of lsf_evolve_band and lsf_evolve_band_curv: the staging of the inputs, the twins of phi and the mask, the call, the way home
@@ -1611,36 +1607,25 @@ static int evolve_band_host(double* phi, int32_t* mask, const double* u, const d
         return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
-    // u, v, w, speed travel as in lsf_advect_field: each into a slot of its own, from a current device twin under LSF_MIRROR_TRUST / LAZY,
-    // from the host otherwise; staged before phi's twin is touched
-    const double* h_in[4] = {u, v, w, speed};
-    const Slot s_in[4] = {S_AF_U, S_AF_V, S_AF_W, S_AF_F};
-    const double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int q = 0; q < 4; ++q) {
-        if (!h_in[q]) continue;
-        if ((rc = ws(c.slot[s_in[q]], bytes))) return rc;
-        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, h_in[q], bytes) : nullptr;
-        HIPCHK(hipMemcpy(c.slot[s_in[q]].p, twin ? twin : (const void*)h_in[q], bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-        d_in[q] = (const double*)c.slot[s_in[q]].p;
-    }
-    // phi and the mask are both in/out and travel as phi does in lsf_reinit_band: the mask through the twin of phiNB when it IS that
-    // array, through the twin of phiSB otherwise
+    const double* d_in[4];
+    const int32_t* d_mask;
+    Twin* tm; // the mask is in/out here: its twin and slot come back from mask_in for the way home
+    Slot sm;
+    if ((rc = velocity_in(c, u, v, w, speed, bytes, d_in))) return rc;
     if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc;
-    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-    const Slot sm = is_nb ? S_HNB : S_HSB;
-    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-    rc = evolve_band_core((double*)c.slot[S_HPHI].p, (int32_t*)c.slot[sm].p, d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, steps, scheme,
+    if ((rc = mask_in(c, mask, n, &d_mask, &tm, &sm))) return rc;
+    rc = evolve_band_core((double*)c.slot[S_HPHI].p, const_cast<int32_t*>(d_mask), d_in[0], d_in[1], d_in[2], d_in[3], nx, ny, nz, dx, dt, steps, scheme,
                           mode, core, ring, reinit_sweeps, h, check_every, bcurv, clamp, steps_done, cfl, diffusion, change_trace, trace_cap, info,
                           margin, nullptr);
+    // (not phi_home: phi AND the mask come home, or both twins are dropped)
     if (rc == LSF_OK || rc == LSF_ERR_NAN) {
         const std::string keep = g_err;
         int rc2 = twin_out(c, c.twin_phi, S_HPHI, phi, bytes);
-        if (!rc2) rc2 = twin_out(c, tm, sm, mask, n * sizeof(int32_t));
+        if (!rc2) rc2 = twin_out(c, *tm, sm, mask, n * sizeof(int32_t));
         if (rc2) return rc2;
         g_err = keep;
     } else if (rc != LSF_ERR_INVALID) // (an invalid call is found before the twins are written: they stay what they were)
-        twin_drop(c.twin_phi), twin_drop(tm);
+        twin_drop(c.twin_phi), twin_drop(*tm);
     return rc;
 }
 
@@ -1707,26 +1692,16 @@ int lsf_curvature_band(const double* phi, const int32_t* mask, double* kappa, do
     if ((rc = curvature_band_args_ok(phi, mask, kappa, gauss, gmag, nx, ny, nz, dx, clamp))) return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
-    // The outputs have no twin: as lsf_extend_field stages q, each one given is staged in a slot of its own from the host on every call
-    // (what it holds outside the list stays bit for bit) and comes home on LSF_OK and on LSF_ERR_NAN, lsf_mirror or not.  Staged before
-    // phi's twin is touched.
+    // the outputs have no twin (what they hold off the list stays bit for bit); they come home on LSF_OK and on LSF_ERR_NAN
     double* h_out[3] = {kappa, gauss, gmag};
     const Slot s_out[3] = {S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG};
-    double* d_out[3] = {nullptr, nullptr, nullptr};
-    for (int q = 0; q < 3; ++q) {
-        if (!h_out[q]) continue;
-        if ((rc = ws(c.slot[s_out[q]], bytes))) return rc;
-        HIPCHK(hipMemcpy(c.slot[s_out[q]].p, h_out[q], bytes, hipMemcpyHostToDevice));
-        d_out[q] = (double*)c.slot[s_out[q]].p;
-    }
-    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_extract_surface
-    // the mask travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
-    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-    const Slot sm = is_nb ? S_HNB : S_HSB;
-    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-    rc = curvature_band_core((const double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, d_out[0], d_out[1], d_out[2], nx, ny, nz, dx, clamp, info,
-                             kappa_max, nullptr);
+    double* d_out[3];
+    const int32_t* d_mask;
+    for (int q = 0; q < 3; ++q)
+        if ((rc = stage_in(c, s_out[q], h_out[q], bytes, &d_out[q]))) return rc;
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    rc = curvature_band_core((const double*)c.slot[S_HPHI].p, d_mask, d_out[0], d_out[1], d_out[2], nx, ny, nz, dx, clamp, info, kappa_max, nullptr);
     if (rc != LSF_OK && rc != LSF_ERR_NAN) return rc;
     const std::string keep = g_err;
     for (int q = 0; q < 3; ++q)
@@ -1756,26 +1731,17 @@ int lsf_extend_field_band(double* q, const double* phi, const int32_t* mask, con
     if ((rc = extend_band_args_ok(q, phi, mask, known, nx, ny, nz, dx, band, max_passes, trace_cap))) return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-    // q is staged as lsf_extend_field stages it: no twin, copied in from the host on every call (what it holds off the list stays bit
-    // for bit) and copied back on LSF_OK only.  known is an input only and has a slot of its own.  Both before phi's twin is touched.
-    if ((rc = ws(c.slot[S_EXT_Q], n * sizeof(double)))) return rc;
-    HIPCHK(hipMemcpy(c.slot[S_EXT_Q].p, q, n * sizeof(double), hipMemcpyHostToDevice));
-    const int32_t* d_known = nullptr;
-    if (known) {
-        if ((rc = ws(c.slot[S_XB_KNOWN], n * sizeof(int32_t)))) return rc;
-        HIPCHK(hipMemcpy(c.slot[S_XB_KNOWN].p, known, n * sizeof(int32_t), hipMemcpyHostToDevice));
-        d_known = (const int32_t*)c.slot[S_XB_KNOWN].p;
-    }
-    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // phi is an input only, as in lsf_extend_field
-    // the mask travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
-    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-    const Slot sm = is_nb ? S_HNB : S_HSB;
-    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-    if ((rc = extend_band_core((double*)c.slot[S_EXT_Q].p, (const double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, d_known, nx, ny, nz, dx, band,
-                               max_passes, passes_done, changed_trace, trace_cap, info, nullptr)))
+    double* d_q;
+    int32_t* d_known;
+    const int32_t* d_mask;
+    if ((rc = stage_in(c, S_EXT_Q, q, n * sizeof(double), &d_q))) return rc; // q has no twin (off the list it stays bit for bit); home on LSF_OK
+    if ((rc = stage_in(c, S_XB_KNOWN, known, n * sizeof(int32_t), &d_known))) return rc; // an int32 input with a slot of its own
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc;       // phi is an input only
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    if ((rc = extend_band_core(d_q, (const double*)c.slot[S_HPHI].p, d_mask, d_known, nx, ny, nz, dx, band, max_passes, passes_done, changed_trace,
+                               trace_cap, info, nullptr)))
         return rc;
-    HIPCHK(hipMemcpy(q, c.slot[S_EXT_Q].p, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(q, d_q, n * sizeof(double), hipMemcpyDeviceToHost));
     return LSF_OK;
 }
 
@@ -1823,31 +1789,14 @@ int lsf_measure_band(const double* phi, const int32_t* mask, const double* q, do
     if ((rc = measure_band_args_ok(phi, mask, q, cell_area, nx, ny, nz, dx, xLo, iso, M))) return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
-    // q is an input only and travels as lsf_advect_field's inputs do: into a slot of its own, from a current device twin under
-    // LSF_MIRROR_TRUST / LAZY, from the host otherwise.  cell_area has no twin: as lsf_curvature_band stages its outputs it is copied in on
-    // every call (what it holds off the list stays bit for bit) and comes home on LSF_OK only.  Both before phi's twin is touched.
-    const double* d_q = nullptr;
-    if (q) {
-        if ((rc = ws(c.slot[S_MS_Q], bytes))) return rc;
-        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, q, bytes) : nullptr;
-        HIPCHK(hipMemcpy(c.slot[S_MS_Q].p, twin ? twin : (const void*)q, bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-        d_q = (const double*)c.slot[S_MS_Q].p;
-    }
-    double* d_cell = nullptr;
-    if (cell_area) {
-        if ((rc = ws(c.slot[S_MS_CELL], bytes))) return rc;
-        HIPCHK(hipMemcpy(c.slot[S_MS_CELL].p, cell_area, bytes, hipMemcpyHostToDevice));
-        d_cell = (double*)c.slot[S_MS_CELL].p;
-    }
-    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_extract_surface
-    // the mask travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
-    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-    const Slot sm = is_nb ? S_HNB : S_HSB;
-    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-    if ((rc = measure_band_core((const double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, d_q, d_cell, nx, ny, nz, dx, xLo, iso, M, info,
-                                nullptr)))
-        return rc;
+    const double* d_q;
+    double* d_cell;
+    const int32_t* d_mask;
+    if ((rc = input_in(c, S_MS_Q, q, bytes, &d_q))) return rc;
+    if ((rc = stage_in(c, S_MS_CELL, cell_area, bytes, &d_cell))) return rc; // no twin (off the list it stays bit for bit); home on LSF_OK
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc;        // phi is an input only
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    if ((rc = measure_band_core((const double*)c.slot[S_HPHI].p, d_mask, d_q, d_cell, nx, ny, nz, dx, xLo, iso, M, info, nullptr))) return rc;
     if (cell_area) HIPCHK(hipMemcpy(cell_area, d_cell, bytes, hipMemcpyDeviceToHost));
     return LSF_OK;
 }
@@ -1876,15 +1825,9 @@ int lsf_sample_points(const double* phi, const int32_t* mask, const double* q, i
     if ((rc = sample_points_args_ok(phi, mask, q, nx, ny, nz, dx, xLo, pts, npts, order, iso, iters, tol, val, grad, qval, foot, status))) return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double), np = (size_t)npts;
-    // q is an input only: into a slot of its own as lsf_extend_field stages q (from a current device twin under LSF_MIRROR_TRUST / LAZY,
-    // as lsf_measure_band does) and never copied back.  Staged before phi's twin is touched.
-    const double* d_q = nullptr;
-    if (q) {
-        if ((rc = ws(c.slot[S_SP_Q], bytes))) return rc;
-        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, q, bytes) : nullptr;
-        HIPCHK(hipMemcpy(c.slot[S_SP_Q].p, twin ? twin : (const void*)q, bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-        d_q = (const double*)c.slot[S_SP_Q].p;
-    }
+    const double* d_q;
+    const int32_t* d_mask;
+    if ((rc = input_in(c, S_SP_Q, q, bytes, &d_q))) return rc;
     // pts and the outputs are staged per call in one slot: pts(3), val(1), grad(3), qval(1), foot(3) doubles per point, then status.
     // The kernel writes every entry of every output, so nothing is copied in but pts; the outputs come home on LSF_OK only.
     if ((rc = ws(c.slot[S_SP_IO], np * (11 * sizeof(double) + sizeof(int32_t))))) return rc;
@@ -1893,15 +1836,8 @@ int lsf_sample_points(const double* phi, const int32_t* mask, const double* q, i
            *d_foot = foot ? io + 8 * np : nullptr;
     int32_t* d_status = status ? (int32_t*)(io + 11 * np) : nullptr;
     HIPCHK(hipMemcpy(d_pts, pts, 3 * np * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_extract_surface
-    const int32_t* d_mask = nullptr;
-    if (mask) { // as in lsf_curvature_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
-        const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-        Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-        const Slot sm = is_nb ? S_HNB : S_HSB;
-        if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-        d_mask = (const int32_t*)c.slot[sm].p;
-    }
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
     if ((rc = sample_points_core((const double*)c.slot[S_HPHI].p, d_mask, d_q, nx, ny, nz, dx, xLo, d_pts, npts, order, iso, iters, tol, d_val,
                                  d_grad, d_qval, d_foot, d_status, info, nullptr)))
         return rc;
@@ -1940,15 +1876,9 @@ int lsf_cast_rays(const double* phi, const int32_t* mask, const double* q, int n
         return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double), nr = (size_t)nrays;
-    // q is an input only: into a slot of its own, as lsf_sample_points stages its q, and never copied back.  Staged before phi's twin is
-    // touched.
-    const double* d_q = nullptr;
-    if (q) {
-        if ((rc = ws(c.slot[S_CR_Q], bytes))) return rc;
-        const void* twin = (c.mirror & (LSF_MIRROR_TRUST | LSF_MIRROR_LAZY)) ? twin_of(c, q, bytes) : nullptr;
-        HIPCHK(hipMemcpy(c.slot[S_CR_Q].p, twin ? twin : (const void*)q, bytes, twin ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-        d_q = (const double*)c.slot[S_CR_Q].p;
-    }
+    const double* d_q;
+    const int32_t* d_mask;
+    if ((rc = input_in(c, S_CR_Q, q, bytes, &d_q))) return rc;
     // org, dir and the outputs are staged per call in one slot: org(3), dir(3), thit(1), hit(3), grad(3), qval(1) doubles per ray, then
     // status.  The kernel writes every entry of every output, so nothing is copied in but org and dir; the outputs come home on LSF_OK only.
     if ((rc = ws(c.slot[S_CR_IO], nr * (14 * sizeof(double) + sizeof(int32_t))))) return rc;
@@ -1958,15 +1888,8 @@ int lsf_cast_rays(const double* phi, const int32_t* mask, const double* q, int n
     int32_t* d_status = status ? (int32_t*)(io + 14 * nr) : nullptr;
     HIPCHK(hipMemcpy(d_org, org, 3 * nr * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_dir, dir, 3 * nr * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only, as in lsf_sample_points
-    const int32_t* d_mask = nullptr;
-    if (mask) { // as in lsf_curvature_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
-        const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-        Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-        const Slot sm = is_nb ? S_HNB : S_HSB;
-        if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-        d_mask = (const int32_t*)c.slot[sm].p;
-    }
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
     if ((rc = cast_rays_core((const double*)c.slot[S_HPHI].p, d_mask, d_q, nx, ny, nz, dx, xLo, d_org, d_dir, nrays, order, iso, tmin, tmax, safety, smin,
                              smax, skip, refine, max_steps, d_thit, d_hit, d_grad, d_qval, d_status, info, nullptr)))
         return rc;
@@ -1997,20 +1920,15 @@ int lsf_label_band(const double* phi, const int32_t* mask, int32_t* label, int n
     if ((rc = label_band_args_ok(phi, mask, label, nx, ny, nz, iso, side, max_passes, comp, comp_cap))) return rc;
     Ctx& c = ctx();
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-    // label has no twin: as lsf_curvature_band stages kappa it is staged in an int32 slot of its own from the host on every call (what it
-    // holds outside the list stays bit for bit) and comes home on LSF_OK only.  Staged before phi's twin is touched.
-    if ((rc = ws(c.slot[S_LB_LABEL], n * sizeof(int32_t)))) return rc;
-    HIPCHK(hipMemcpy(c.slot[S_LB_LABEL].p, label, n * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // phi is an input only, as in lsf_curvature_band
-    // the mask travels as in lsf_reinit_band: through the twin of phiNB when it IS that array, through the twin of phiSB otherwise
-    const bool is_nb = c.twin_nb.host == (const void*)mask && c.twin_nb.bytes == n * sizeof(int32_t);
-    Twin& tm = is_nb ? c.twin_nb : c.twin_sb;
-    const Slot sm = is_nb ? S_HNB : S_HSB;
-    if ((rc = twin_in(c, tm, sm, mask, n * sizeof(int32_t)))) return rc;
-    if ((rc = label_band_core((const double*)c.slot[S_HPHI].p, (const int32_t*)c.slot[sm].p, (int32_t*)c.slot[S_LB_LABEL].p, nx, ny, nz, iso, side,
-                              max_passes, comp, comp_cap, ncomp, info, nullptr)))
+    int32_t* d_label;
+    const int32_t* d_mask;
+    if ((rc = stage_in(c, S_LB_LABEL, label, n * sizeof(int32_t), &d_label))) return rc; // no twin (off the list it stays bit for bit); home on LSF_OK
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc;       // phi is an input only
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    if ((rc = label_band_core((const double*)c.slot[S_HPHI].p, d_mask, d_label, nx, ny, nz, iso, side, max_passes, comp, comp_cap, ncomp, info,
+                              nullptr)))
         return rc;
-    HIPCHK(hipMemcpy(label, c.slot[S_LB_LABEL].p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(label, d_label, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return LSF_OK;
 }
 

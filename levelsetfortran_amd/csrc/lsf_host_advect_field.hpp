@@ -1,30 +1,7 @@
-// lsf_host_advect_field.hpp -- host side of lsf_advect_field (kernels and design: lsf_advect_field.hpp): validation, the scan of the
+// lsf_host_advect_field.hpp -- host side of lsf_advect_field (kernels and design: lsf_advect_field.hpp; argument checks: lsf_host_args.hpp): the scan of the
 // inputs (CFL number, non-finite values) and the steps, one plain launch per stage.  Included by lsf_api.hip inside its anonymous
 // namespace.
 #pragma once
-
-// what can be decided without the device; nothing is written anywhere before this and the scan have passed
-int advect_field_args_ok(const void* phi, const void* u, const void* v, const void* w, const void* speed, int nx, int ny, int nz, double dx,
-                         double dt, int steps, int scheme, int mode)
-{
-    if (!phi) return fail(LSF_ERR_INVALID, "phi is NULL");
-    const int nvel = (u != nullptr) + (v != nullptr) + (w != nullptr);
-    if (nvel != 0 && nvel != 3) return fail(LSF_ERR_INVALID, "lsf_advect_field: u, v, w are given together or all NULL (" + std::to_string(nvel) + " of 3 given)");
-    if (!nvel && !speed) return fail(LSF_ERR_INVALID, "lsf_advect_field: neither a velocity (u, v, w) nor a speed is given");
-    const int rc = check_dims(nx, ny, nz);
-    if (rc) return rc;
-    if ((double)(nx + 1.0) * (ny + 1.0) * (nz + 1.0) > 2147483647.0) return fail(LSF_ERR_INVALID, "lsf_advect_field: more than 2^31 - 1 points");
-    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "dx must be finite and > 0");
-    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(LSF_ERR_INVALID, "lsf_advect_field: dt must be finite and > 0");
-    if (steps < 0) return fail(LSF_ERR_INVALID, "lsf_advect_field: steps must be >= 0");
-    if (scheme != LSF_ADVECT_RK3 && scheme != LSF_ADVECT_EULER) return fail(LSF_ERR_INVALID, "lsf_advect_field: unknown scheme (LSF_ADVECT_RK3 or LSF_ADVECT_EULER)");
-    const int order = mode & LSF_ORDER_MASK;
-    if (order == LSF_ORDER_GS)
-        return fail(LSF_ERR_INVALID, "lsf_advect_field: LSF_ORDER_GS has no meaning for an explicit step (every stage reads the field as it was); "
-                                     "pass LSF_ORDER_JACOBI");
-    if (order != LSF_ORDER_JACOBI) return fail(LSF_ERR_INVALID, "unknown ordering");
-    return LSF_OK;
-}
 
 // read-only: cfl = (dt * max over all points (|u| + |v| + |w| + |speed|)) / dx; a non-finite input is LSF_ERR_INVALID with its count
 int advect_field_scan(const double* d_u, const double* d_v, const double* d_w, const double* d_f, int nx, int ny, int nz, double dx, double dt,

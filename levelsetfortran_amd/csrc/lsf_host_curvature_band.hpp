@@ -1,34 +1,6 @@
-// lsf_host_curvature_band.hpp -- host side of lsf_curvature_band (kernel and design: lsf_curvature_band.hpp): validation, the list,
+// lsf_host_curvature_band.hpp -- host side of lsf_curvature_band (kernel and design: lsf_curvature_band.hpp; argument checks: lsf_host_args.hpp): the list,
 // the one launch over it and the finish of its partials in block order.  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
-
-// what can be decided without the device (the pointers are the caller's, host or device: only compared); nothing is written anywhere
-// before this has passed
-int curvature_band_args_ok(const void* phi, const void* mask, const void* kappa, const void* gauss, const void* gmag, int nx, int ny, int nz,
-                           double dx, double clamp)
-{
-    int rc;
-    if (!phi) return fail(LSF_ERR_INVALID, "lsf_curvature_band: phi is NULL");
-    if (!mask) return fail(LSF_ERR_INVALID, "lsf_curvature_band: mask is NULL");
-    if (!kappa) return fail(LSF_ERR_INVALID, "lsf_curvature_band: kappa is NULL");
-    if ((rc = check_dims(nx, ny, nz))) return rc;
-    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-    if (n > (size_t)0x7fffffff)
-        return fail(LSF_ERR_INVALID, "lsf_curvature_band: more than 2^31 - 1 points (list entries are 32-bit point indices)");
-    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "lsf_curvature_band: dx must be finite and > 0");
-    if (!(clamp >= 0.0) || !std::isfinite(clamp)) return fail(LSF_ERR_INVALID, "lsf_curvature_band: clamp must be finite and >= 0 (0: no clamp)");
-    // an output is written while phi and the other outputs are still being read or written: none may share a byte with another
-    const void* a[4] = {phi, kappa, gauss, gmag};
-    const char* name[4] = {"phi", "kappa", "gauss", "gmag"};
-    for (int i = 1; i < 4; ++i)
-        for (int j = 0; j < i; ++j) {
-            if (!a[i] || !a[j]) continue;
-            const uintptr_t x = (uintptr_t)a[i], y = (uintptr_t)a[j];
-            if ((x > y ? x - y : y - x) < n * sizeof(double))
-                return fail(LSF_ERR_INVALID, std::string("lsf_curvature_band: ") + name[i] + " overlaps " + name[j]);
-        }
-    return LSF_OK;
-}
 
 // the arguments have passed curvature_band_args_ok.  info and kappa_max are written on LSF_OK only; on LSF_ERR_NAN the outputs hold
 // what was computed.  Returns after the stream is synchronised.

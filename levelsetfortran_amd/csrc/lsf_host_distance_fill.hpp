@@ -1,19 +1,6 @@
-// lsf_host_distance_fill.hpp -- host side of lsf_distance_fill (kernels and design: lsf_distance_fill.hpp): validation, the check
+// lsf_host_distance_fill.hpp -- host side of lsf_distance_fill (kernels and design: lsf_distance_fill.hpp; argument checks: lsf_host_args.hpp): the check
 // pass, and the rounds of 8 raster sweeps, one plain launch per tile plane.  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
-
-// what can be decided without the device; nothing is written anywhere before this and the check pass have passed
-int distance_fill_args_ok(const void* phi, const void* mask, int nx, int ny, int nz, double dx, double band, int max_rounds)
-{
-    if (!phi) return fail(LSF_ERR_INVALID, "phi is NULL");
-    if (nx < 1 || ny < 1 || nz < 1) return fail(LSF_ERR_INVALID, "lsf_distance_fill: nx, ny, nz must be >= 1");
-    if ((double)(nx + 1.0) * (ny + 1.0) * (nz + 1.0) > 2147483647.0) return fail(LSF_ERR_INVALID, "lsf_distance_fill: more than 2^31 - 1 points");
-    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "dx must be finite and > 0");
-    if (!mask && (!(band > 0.0) || !std::isfinite(band)))
-        return fail(LSF_ERR_INVALID, "lsf_distance_fill: without a mask, band must be finite and > 0 (the frozen set is |phi| < band*dx)");
-    if (max_rounds < 1) return fail(LSF_ERR_INVALID, "lsf_distance_fill: max_rounds must be >= 1");
-    return LSF_OK;
-}
 
 int distance_fill_core(double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, double band, int max_rounds, int* rounds_done,
                        int64_t* changed_trace, int trace_cap, int64_t* frozen_points, hipStream_t st)

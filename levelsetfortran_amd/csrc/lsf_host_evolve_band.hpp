@@ -1,5 +1,5 @@
 // lsf_host_evolve_band.hpp -- host side of lsf_evolve_band and lsf_evolve_band_curv (kernels and design: lsf_evolve_band.hpp; the
-// stage with the curvature term: lsf_evolve_band_curv.hpp; lsf_evolve_band is bcurv = clamp = 0): validation, the scan of the
+// stage with the curvature term: lsf_evolve_band_curv.hpp; lsf_evolve_band is bcurv = clamp = 0; argument checks: lsf_host_args.hpp): the scan of the
 // inputs over all points, the first list, the steps (stages and sweeps enqueued on the resident list), the checks (one 64-byte
 // record read per check) and the rebuilds.  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
@@ -28,26 +28,6 @@ void advect_band_curv_stage_launch(bool strict, const double* A, double* B, cons
         else LSF_ADVC_CALL(false, false, false);
     }
 #undef LSF_ADVC_CALL
-}
-
-// what can be decided without the device (lsf_evolve_band: bcurv = clamp = 0)
-int evolve_band_args_ok(const void* phi, const void* mask, const void* u, const void* v, const void* w, const void* speed, int nx, int ny, int nz,
-                        double dx, double dt, int steps, int scheme, int mode, double core, int ring, int reinit_sweeps, double h, int check_every,
-                        double bcurv, double clamp)
-{
-    int rc;
-    if (!(bcurv >= 0.0) || !std::isfinite(bcurv)) return fail(LSF_ERR_INVALID, "lsf_evolve_band_curv: bcurv must be finite and >= 0");
-    if (!(clamp >= 0.0) || !std::isfinite(clamp)) return fail(LSF_ERR_INVALID, "lsf_evolve_band_curv: clamp must be finite and >= 0 (0: no clamp)");
-    // with bcurv > 0 the term moves the surface and both input groups may be absent: that check alone is answered here
-    const bool none = !u && !v && !w && !speed;
-    if ((rc = advect_field_args_ok(phi, u, v, w, none && bcurv > 0.0 ? phi : speed, nx, ny, nz, dx, dt, steps, scheme, mode))) return rc;
-    if (!mask) return fail(LSF_ERR_INVALID, "lsf_evolve_band: mask is NULL");
-    if (!(core > 0.0) || !std::isfinite(core)) return fail(LSF_ERR_INVALID, "lsf_evolve_band: core must be finite and > 0");
-    if (ring < 1 || ring > 8) return fail(LSF_ERR_INVALID, "lsf_evolve_band: ring must be in 1..8");
-    if (reinit_sweeps < 0) return fail(LSF_ERR_INVALID, "lsf_evolve_band: reinit_sweeps must be >= 0");
-    if (reinit_sweeps > 0 && (!(h > 0.0) || !std::isfinite(h))) return fail(LSF_ERR_INVALID, "lsf_evolve_band: h must be finite and > 0");
-    if (check_every < 1) return fail(LSF_ERR_INVALID, "lsf_evolve_band: check_every must be >= 1");
-    return LSF_OK;
 }
 
 // Every error is found before anything is written: the arguments, then the inputs at all points.  info and margin are written on

@@ -1,32 +1,7 @@
-// lsf_host_extend_band.hpp -- host side of lsf_extend_field_band (kernels and design: lsf_extend_band.hpp): validation, the list, the
+// lsf_host_extend_band.hpp -- host side of lsf_extend_field_band (kernels and design: lsf_extend_band.hpp; argument checks: lsf_host_args.hpp): the list, the
 // plan pass with its error counts, the Jacobi passes enqueued CHECK_EVERY at a time, and the final count.  Included by lsf_api.hip
 // inside its anonymous namespace.
 #pragma once
-
-// what can be decided without the device (the pointers are the caller's, host or device: only compared); nothing is written anywhere
-// before this and the plan pass have passed
-int extend_band_args_ok(const void* q, const void* phi, const void* mask, const void* known, int nx, int ny, int nz, double dx, double band,
-                        int max_passes, int trace_cap)
-{
-    int rc;
-    if (!q) return fail(LSF_ERR_INVALID, "lsf_extend_field_band: q is NULL");
-    if (!phi) return fail(LSF_ERR_INVALID, "lsf_extend_field_band: phi is NULL");
-    if (!mask) return fail(LSF_ERR_INVALID, "lsf_extend_field_band: mask is NULL");
-    if ((rc = check_dims(nx, ny, nz))) return rc;
-    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-    if (n > (size_t)0x7fffffff)
-        return fail(LSF_ERR_INVALID, "lsf_extend_field_band: more than 2^31 - 1 points (list entries are 32-bit point indices)");
-    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "lsf_extend_field_band: dx must be finite and > 0");
-    if (!known && (!(band > 0.0) || !std::isfinite(band)))
-        return fail(LSF_ERR_INVALID, "lsf_extend_field_band: without known, band must be finite and > 0 (the frozen cells are the list cells "
-                                     "with |phi| < band*dx)");
-    if (max_passes < 1) return fail(LSF_ERR_INVALID, "lsf_extend_field_band: max_passes must be >= 1");
-    if (trace_cap < 0) return fail(LSF_ERR_INVALID, "lsf_extend_field_band: trace_cap must be >= 0");
-    // q is written while phi is still being read
-    const uintptr_t x = (uintptr_t)q, y = (uintptr_t)phi;
-    if ((x > y ? x - y : y - x) < n * sizeof(double)) return fail(LSF_ERR_INVALID, "lsf_extend_field_band: q overlaps phi");
-    return LSF_OK;
-}
 
 // the arguments have passed extend_band_args_ok.  passes_done, changed_trace and info are written on LSF_OK only, q after every error
 // has been decided.  Returns after the stream is synchronised.

@@ -1,21 +1,7 @@
-// lsf_host_extend_field.hpp -- host side of lsf_extend_field (kernels and design: lsf_extend_field.hpp): validation, the check pass,
+// lsf_host_extend_field.hpp -- host side of lsf_extend_field (kernels and design: lsf_extend_field.hpp; argument checks: lsf_host_args.hpp): the check pass,
 // the rounds of 8 raster sweeps, one plain launch per tile plane, and the final count.  Included by lsf_api.hip inside its anonymous
 // namespace.
 #pragma once
-
-// what can be decided without the device; nothing is written anywhere before this and the check pass have passed
-int extend_field_args_ok(const void* q, const void* phi, const void* mask, int nx, int ny, int nz, double dx, double band, int max_rounds)
-{
-    if (!q) return fail(LSF_ERR_INVALID, "lsf_extend_field: q is NULL");
-    if (!phi) return fail(LSF_ERR_INVALID, "lsf_extend_field: phi is NULL");
-    if (nx < 1 || ny < 1 || nz < 1) return fail(LSF_ERR_INVALID, "lsf_extend_field: nx, ny, nz must be >= 1");
-    if ((double)(nx + 1.0) * (ny + 1.0) * (nz + 1.0) > 2147483647.0) return fail(LSF_ERR_INVALID, "lsf_extend_field: more than 2^31 - 1 points");
-    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "lsf_extend_field: dx must be finite and > 0");
-    if (!mask && (!(band > 0.0) || !std::isfinite(band)))
-        return fail(LSF_ERR_INVALID, "lsf_extend_field: without a mask, band must be finite and > 0 (the frozen set is |phi| < band*dx)");
-    if (max_rounds < 1) return fail(LSF_ERR_INVALID, "lsf_extend_field: max_rounds must be >= 1");
-    return LSF_OK;
-}
 
 int extend_field_core(double* d_q, const double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, double band, int max_rounds,
                       int* rounds_done, int64_t* changed_trace, int trace_cap, int64_t* info, hipStream_t st)

@@ -1,4 +1,4 @@
-// lsf_host_extract_surface.hpp -- host side of lsf_extract_surface (kernels and design: lsf_extract_surface.hpp): validation, the
+// lsf_host_extract_surface.hpp -- host side of lsf_extract_surface (kernels and design: lsf_extract_surface.hpp; argument checks: lsf_host_args.hpp): the
 // launches, the two totals the host reads, and the result kept for the calling thread until lsf_extract_get copies it out.
 // Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
@@ -19,18 +19,6 @@ void extract_drop()
     if (R.x) (void)hipFree(R.x);
     if (R.e) (void)hipFree(R.e);
     R = ExtractResult{};
-}
-
-// what can be decided without the device
-int extract_args_ok(const void* phi, int nx, int ny, int nz, double dx, const double* xLo, double iso, const int* nSurfNode, const int* nSurfElem)
-{
-    if (!phi) return fail(LSF_ERR_INVALID, "phi is NULL");
-    if (!xLo || !nSurfNode || !nSurfElem) return fail(LSF_ERR_INVALID, "lsf_extract_surface: NULL xLo or count pointer");
-    if (nx < 1 || ny < 1 || nz < 1) return fail(LSF_ERR_INVALID, "lsf_extract_surface: nx, ny, nz must be >= 1");
-    if ((double)(nx + 1.0) * (ny + 1.0) * (nz + 1.0) > 2147483647.0) return fail(LSF_ERR_INVALID, "lsf_extract_surface: more than 2^31 - 1 points");
-    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "dx must be finite and > 0");
-    if (!std::isfinite(iso)) return fail(LSF_ERR_INVALID, "lsf_extract_surface: iso must be finite");
-    return LSF_OK;
 }
 
 // arguments validated; d_phi is a device array.  Returns after the stream is synchronised.

@@ -1,34 +1,7 @@
-// lsf_host_label_band.hpp -- host side of lsf_label_band (kernels and design: lsf_label_band.hpp): validation, the list, the check
+// lsf_host_label_band.hpp -- host side of lsf_label_band (kernels and design: lsf_label_band.hpp; argument checks: lsf_host_args.hpp): the list, the check
 // launch with its error counts, the link / flatten passes enqueued CHECK_EVERY at a time, and the table of components.  Included by
 // lsf_api.hip inside its anonymous namespace.
 #pragma once
-
-// what can be decided without the device (the pointers are the caller's, host or device: only compared); nothing is written anywhere
-// before this and the check launch have passed
-int label_band_args_ok(const void* phi, const void* mask, const void* label, int nx, int ny, int nz, double iso, int side, int max_passes,
-                       const void* comp, int comp_cap)
-{
-    int rc;
-    if (!phi) return fail(LSF_ERR_INVALID, "lsf_label_band: phi is NULL");
-    if (!mask) return fail(LSF_ERR_INVALID, "lsf_label_band: mask is NULL");
-    if (!label) return fail(LSF_ERR_INVALID, "lsf_label_band: label is NULL");
-    if ((rc = check_dims(nx, ny, nz))) return rc;
-    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-    if (n > (size_t)0x7fffffff)
-        return fail(LSF_ERR_INVALID, "lsf_label_band: more than 2^31 - 1 points (list entries and labels are 32-bit point indices)");
-    if (!std::isfinite(iso)) return fail(LSF_ERR_INVALID, "lsf_label_band: iso must be finite");
-    if (side != LSF_LABEL_INSIDE && side != LSF_LABEL_OUTSIDE && side != LSF_LABEL_BOTH)
-        return fail(LSF_ERR_INVALID, "lsf_label_band: side must be LSF_LABEL_INSIDE, LSF_LABEL_OUTSIDE or LSF_LABEL_BOTH");
-    if (max_passes < 1) return fail(LSF_ERR_INVALID, "lsf_label_band: max_passes must be >= 1");
-    if (comp_cap < 0) return fail(LSF_ERR_INVALID, "lsf_label_band: comp_cap must be >= 0");
-    if (!comp && comp_cap > 0) return fail(LSF_ERR_INVALID, "lsf_label_band: comp is NULL with comp_cap > 0");
-    // label is written while phi and the mask are still being read
-    const uintptr_t l0 = (uintptr_t)label, l1 = l0 + n * sizeof(int32_t);
-    const uintptr_t p0 = (uintptr_t)phi, m0 = (uintptr_t)mask;
-    if (l0 < p0 + n * sizeof(double) && p0 < l1) return fail(LSF_ERR_INVALID, "lsf_label_band: label overlaps phi");
-    if (l0 < m0 + n * sizeof(int32_t) && m0 < l1) return fail(LSF_ERR_INVALID, "lsf_label_band: label overlaps mask");
-    return LSF_OK;
-}
 
 // the arguments have passed label_band_args_ok.  comp, ncomp and info are host arrays and are written on LSF_OK only, d_label after every
 // error has been decided.  Returns after the stream is synchronised.

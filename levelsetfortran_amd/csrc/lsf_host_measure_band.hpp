@@ -1,41 +1,7 @@
-// lsf_host_measure_band.hpp -- host side of lsf_measure_band (kernels and design: lsf_measure_band.hpp): validation, the list, the
+// lsf_host_measure_band.hpp -- host side of lsf_measure_band (kernels and design: lsf_measure_band.hpp; argument checks: lsf_host_args.hpp): the list, the
 // two launches over it and the finish of the per-block partials in block order.  Included by lsf_api.hip inside its anonymous
 // namespace.
 #pragma once
-
-// what can be decided without the device (phi, mask, q and cell_area are the caller's, host or device: only compared; xLo and M are
-// host arrays on both seams); nothing is written anywhere before this has passed
-int measure_band_args_ok(const void* phi, const void* mask, const void* q, const void* cell_area, int nx, int ny, int nz, double dx,
-                         const double* xLo, double iso, const double* M)
-{
-    int rc;
-    if (!phi) return fail(LSF_ERR_INVALID, "lsf_measure_band: phi is NULL");
-    if (!mask) return fail(LSF_ERR_INVALID, "lsf_measure_band: mask is NULL");
-    if (!xLo) return fail(LSF_ERR_INVALID, "lsf_measure_band: xLo is NULL");
-    if (!M) return fail(LSF_ERR_INVALID, "lsf_measure_band: M is NULL");
-    if ((rc = check_dims(nx, ny, nz))) return rc;
-    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-    if (n > (size_t)0x7fffffff)
-        return fail(LSF_ERR_INVALID, "lsf_measure_band: more than 2^31 - 1 points (list entries are 32-bit point indices)");
-    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "lsf_measure_band: dx must be finite and > 0");
-    if (!std::isfinite(iso)) return fail(LSF_ERR_INVALID, "lsf_measure_band: iso must be finite");
-    if (!std::isfinite(xLo[0]) || !std::isfinite(xLo[1]) || !std::isfinite(xLo[2]))
-        return fail(LSF_ERR_INVALID, "lsf_measure_band: xLo must hold three finite values");
-    // cell_area is written while phi, mask and q are still being read: it may share a byte with none of them
-    if (cell_area) {
-        const void* a[3] = {phi, mask, q};
-        const size_t bytes[3] = {n * sizeof(double), n * sizeof(int32_t), n * sizeof(double)};
-        const char* name[3] = {"phi", "mask", "q"};
-        const uintptr_t x = (uintptr_t)cell_area;
-        for (int i = 0; i < 3; ++i) {
-            if (!a[i]) continue;
-            const uintptr_t y = (uintptr_t)a[i];
-            if (x < y ? y - x < n * sizeof(double) : x - y < bytes[i])
-                return fail(LSF_ERR_INVALID, std::string("lsf_measure_band: cell_area overlaps ") + name[i]);
-        }
-    }
-    return LSF_OK;
-}
 
 // the arguments have passed measure_band_args_ok.  M and info are written on LSF_OK only.  Returns after the stream is synchronised.
 int measure_band_core(const double* d_phi, const int32_t* d_mask, const double* d_q, double* d_cell, int nx, int ny, int nz, double dx,

@@ -90,20 +90,6 @@ int mesh_prepare(const double* surfX, int nSurfNode, const int32_t* surfElem, in
     return LSF_OK;
 }
 
-int mesh_args_ok(int nx, int ny, int nz, double dx, const double* xLo, double width, int flags)
-{
-    int rc = check_dims(nx, ny, nz);
-    if (rc) return rc;
-    if (!xLo) return fail(LSF_ERR_INVALID, "NULL pointer");
-    if (!(dx > 0.0) || !std::isfinite(dx)) return fail(LSF_ERR_INVALID, "dx must be > 0");
-    if (!std::isfinite(width) || width < 1.5)
-        return fail(LSF_ERR_INVALID, "lsf_mesh_distance: width must be finite and >= 1.5 (the column fill needs both neighbours of a "
-                                     "crossing inside the tube)");
-    if (!std::isfinite(xLo[0]) || !std::isfinite(xLo[1]) || !std::isfinite(xLo[2])) return fail(LSF_ERR_INVALID, "xLo is not finite");
-    if (flags & ~LSF_MESH_UNSIGNED) return fail(LSF_ERR_INVALID, "lsf_mesh_distance: unknown flag");
-    return LSF_OK;
-}
-
 // validation and mesh preparation of one call; nothing is written anywhere before this has passed
 int mesh_distance_prepare(int nx, int ny, int nz, double dx, const double* xLo, const double* surfX, int nSurfNode, const int32_t* surfElem,
                           int nSurfElem, double width, int flags, MeshPrep& M)

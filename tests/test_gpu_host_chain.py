@@ -15,6 +15,10 @@ test_the_cases_are_what_the_docstring_says asserts on the serial statements (CPU
 cells (19 chunks of 256, the last one ragged) and no cell next to a wall; the 279 frozen cells of link 5 lie in the interior phiNB list and
 link 5 leaves no cell unreached; link 7 rebuilds once with no flips; no NaN anywhere.  A second grid (24,20,22) takes the slots over.
 
+The calls that only read their mask (READERS: curvatureBand, extendFieldBand, measureBand, labelBand, distanceFill, and samplePoints /
+castRays with mask=) run on the same state after link 3, their points and rays at the 162 nodes of the body; every array they write begins
+with a sentinel and is compared whole, so what the arrays without a twin (kappa, gauss, q, cell_area, label) hold off the list is compared too.
+
 What the refused calls (LSF_ERR_INVALID) of test_a_refused_call_leaves_the_unsynced_result leave behind, per call: lsf_advect_field,
 lsf_advect_field_band, lsf_evolve_band, lsf_extend_field_band, lsf_curvature_band and lsf_extract_surface all keep the twins as they were,
 whether the argument check or the core check refuses -- so the host array is what it was before until the sync, and the sync brings the EARLIER
@@ -346,7 +350,132 @@ def test_the_mask_goes_through_the_twin_of_the_array_it_is(lsf, base, name, flag
             assert _same(S[other], getattr(base, other)) and (which != "third" or _same(S["sb"], base.sb))
 
 
+READERS = ["curvatureBand", "extendFieldBand", "measureBand", "labelBand", "distanceFill", "samplePoints", "castRays"]
+LABEL_SENT = -7
+
+
+def _rays(K):
+    """points and rays at the body of the chain: its 162 nodes, and from 1.5 radii out of each node towards the centre"""
+    X = K.body[0]
+    c = X.mean(axis=0)
+    return np.asfortranarray(X), np.asfortranarray(c + 1.5 * (X - c)), np.asfortranarray(c - X)
+
+
+def _reader(lsf, name, K, phi, mask, q=None):
+    """one of READERS on phi and mask (all numpy: host seam, or all CUDA tensors: device seam) with fresh inputs and outputs of its own;
+    returns (what it reports, the arrays it wrote) as tuples and host arrays.  q: the second field of measureBand, samplePoints and
+    castRays (default: v of the chain).  The outputs without a twin begin with a sentinel everywhere: what they hold off the list
+    is part of what is compared."""
+    import torch
+
+    dev = not isinstance(phi, np.ndarray)
+    mk, home = (_dev, _home) if dev else (_F, lambda a: a)
+    n, dx = K.n, K.dx
+    vec = (lambda a: torch.from_numpy(np.array(a.T, order="C")).cuda().t()) if dev else _F  # (npts, 3), Fortran order (a copy: the inputs are read-only)
+    vhome = (lambda t: np.asfortranarray(t.cpu().numpy())) if dev else (lambda a: a)
+    q = mk(K.v) if q is None else q
+    if name == "curvatureBand":
+        kap, ga = mk(_fresh()["kappa"]), mk(_fresh()["q"])
+        return tuple(lsf.curvatureBand(phi, mask, *n, dx, kap, gauss=ga, clamp=1.0)), (home(kap), home(ga))
+    if name == "extendFieldBand":
+        ext = mk(K.u)
+        return tuple(lsf.extendFieldBand(ext, phi, mask, dx, band=EXT_BAND)[1]), (home(ext),)
+    if name == "measureBand":
+        cell = mk(_fresh()["q"])
+        return tuple(lsf.measureBand(phi, mask, *n, dx, K.xlo, q=q, cell_area=cell)), (home(cell),)
+    if name == "labelBand":
+        lab = mk(np.full(K.npts, LABEL_SENT, np.int32, order="F"))
+        r = lsf.labelBand(phi, mask, *n, lab, side="both")
+        return (r.ncomp, r.components.tolist(), r.passes, r.certified, r.info), (home(lab),)
+    if name == "distanceFill":  # phi is in/out here: the caller compares it
+        return tuple(lsf.distanceFill(phi, *n, dx, mask=mask)), ()
+    pts, org, dirs = (vec(a) for a in _rays(K))
+    if name == "samplePoints":
+        r = lsf.samplePoints(phi, *n, dx, K.xlo, pts, mask=mask, q=q, iters=2)
+    else:
+        assert name == "castRays"
+        r = lsf.castRays(phi, *n, dx, K.xlo, org, dirs, mask=mask, q=q)
+    return r.info, tuple(vhome(a) for a in r[:-1] if a is not None)
+
+
+@MODES
+@pytest.mark.parametrize("name", READERS)
+def test_a_read_only_mask_goes_through_the_twin_of_the_array_it_is(lsf, base, name, flags):
+    """test_the_mask_goes_through_the_twin_of_the_array_it_is for the calls that only read their mask.  Every array the call writes is
+    compared whole, so label, cell_area, kappa and q also keep, under lsf_mirror, what they held off the list."""
+    K = _setup()
+    lazy = flags == LAZY
+    third = np.asfortranarray(np.where(np.abs(base.phi) < 6.0 * K.dx, 1, 5).astype(np.int32))
+    phi0 = base.phi
+    if name == "distanceFill":  # writes phi: beyond both bands the field is no distance any more, so that the fill has something to change
+        phi0 = np.asfortranarray(np.where(np.abs(base.phi) < 8.1 * K.dx, base.phi, 1.5 * base.phi))
+    for which in ("nb", "sb", "third"):
+        mask_in = third if which == "third" else getattr(base, which)
+        p = _dev(phi0)
+        want_rep, want_out = _reader(lsf, name, K, p, _dev(mask_in))
+        want_phi = _home(p)
+        assert (name == "distanceFill") != _same(want_phi, phi0)  # distanceFill alone writes phi
+        with _mirror(flags) as lib:
+            S = dict(_fresh(), phi=_F(phi0))
+            lsf.narrowBand(*K.n, K.dx, S["phi"], S["nb"], S["sb"])  # the twins of phiNB and phiSB: un-synced under LAZY
+            mask = _F(third) if which == "third" else S[which]
+            rep, out = _reader(lsf, name, K, S["phi"], mask)
+            assert rep == want_rep, (which, rep, want_rep)
+            assert len(out) == len(want_out) and all(_same(a, b) for a, b in zip(out, want_out)), which
+            # the arrays without a twin: written on the list, and off the list bit for bit what they held on entry
+            held = {"curvatureBand": (_fresh()["kappa"], _fresh()["q"]), "extendFieldBand": (K.u,), "measureBand": (_fresh()["q"],),
+                    "labelBand": (np.full(K.npts, LABEL_SENT, np.int32, order="F"),)}.get(name, ())
+            lst = B.list_of(mask_in)
+            for a, h in zip(out, held):
+                assert _same(a[~lst], h[~lst]) and not _same(a[lst], h[lst]), (which, name)
+            other = "sb" if which == "nb" else "nb"
+            if which == "third":
+                # phiSB's un-synced result is home as soon as the third array takes its slot; phiNB's twin is not touched
+                assert _same(S["sb"], base.sb) and _same(S["nb"], base.nb if not lazy else _fresh()["nb"])
+            else:
+                assert _same(S[other], getattr(base, other) if not lazy else _fresh()[other]), which  # the other twin is untouched
+                assert _same(S[which], getattr(base, which) if not lazy else _fresh()[which]), which  # ... and the mask's is not written home
+            assert _same(S["phi"], phi0 if lazy else want_phi)  # distanceFill's result is not home before the sync
+            _sync(lib, S["phi"], S["nb"], S["sb"], mask)
+            assert _same(S["phi"], want_phi), which
+            assert _same(S["nb"], base.nb) and _same(S["sb"], base.sb) and _same(mask, mask_in), which  # what narrowBand made; the mask as given
+
+
 # ------------------------------------------------------------------------------------------------ 2: inputs from a twin
+@pytest.mark.parametrize("name", ["measureBand", "samplePoints", "castRays"])
+def test_an_input_only_field_with_a_stale_host_copy_is_read_from_its_twin(lsf, base, name):
+    """q of measureBand, samplePoints and castRays: under LAZY the latest content of the array lives in phi's twin slot only; the call
+    reads that, and with lsf_mirror(0) it reads the host copy"""
+    from levelsetfortran_amd import fields
+
+    K = _setup()
+    A0 = fields.sphere_phi0(GRID, radius=0.8)[0]
+    a1 = _dev(A0)
+    lsf.reinit(a1, None, None, *K.n, 1, K.dx, K.h, tol=0.0, order="jacobi", arith="strict")
+    A1 = _home(a1)
+    assert not _same(A1, A0) and np.isfinite(A1).all()
+    want = _reader(lsf, name, K, _dev(base.phi), _dev(base.sb), q=_dev(A1))
+    stale = _reader(lsf, name, K, _dev(base.phi), _dev(base.sb), q=_dev(A0))
+    differs = lambda x, y: (["report"] if x[0] != y[0] else []) + [k for k, (a, b) in enumerate(zip(x[1], y[1])) if not _same(a, b)]  # which parts
+    assert differs(want, stale)  # the two inputs give different results: the test bites
+    with _mirror(LAZY):
+        A, Bphi, m = _F(A0), _F(base.phi), _F(base.sb)
+        lsf.reinit(A, None, None, *K.n, 1, K.dx, K.h, tol=0.0, order="jacobi", arith="strict")
+        assert _same(A, A0)  # the host copy is stale
+        got = _reader(lsf, name, K, Bphi, m, q=A)
+        assert not differs(got, want), (differs(got, want), differs(got, stale), differs(want, stale))
+        assert _same(A, A1)  # phi has taken the slot: A is home with the reinit result
+    with _mirror(0):  # (the twins of these arrays are forgotten on the way out: their addresses will be reused)
+        # without lsf_mirror the host copy is the truth: A has a current twin that holds A1, and other values on the host
+        A = _F(A0)
+        lsf.reinit(A, None, None, *K.n, 1, K.dx, K.h, tol=0.0, order="jacobi", arith="strict")
+        assert _same(A, A1)
+        A[...] = A0  # same address, same size, new content
+        got = _reader(lsf, name, K, _F(base.phi), _F(base.sb), q=A)
+        assert not differs(got, stale), (differs(got, stale), differs(got, want))
+        assert _same(A, A0)
+
+
 @pytest.mark.parametrize("name", TRANSPORT)
 def test_an_input_with_a_stale_host_copy_is_read_from_its_twin(lsf, base, name):
     """the complement of test_host_inputs_are_read_from_the_host_not_from_an_earlier_twin (tests/test_gpu_advect_field.py)"""
