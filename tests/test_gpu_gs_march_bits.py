@@ -52,22 +52,28 @@ def _hash01(n, seed):
     return (x >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
 
 
+def rough_phi0(npts):
+    """the "rough" field on a grid of npts points (see the module's text): (phi0 Fortran-ordered, dx)"""
+    from levelsetfortran_amd import fields
+
+    phi0, dx = fields.two_sphere_phi0(npts)
+    n = phi0.size
+    flat = phi0.ravel(order="F").copy()
+    flat *= 1.0 + (2.0 * _hash01(n, 1) - 1.0) * 2.0 ** -10
+    pick = np.floor(_hash01(n, 2) * 23.0 * 3.0).astype(np.int64)  # 0, 1, 2: planted; everything else stays
+    out = flat > 0.0  # a zero among negative neighbours has a zero gradient: the 0 / 0 of subs.f90:169, NaN by the book
+    flat[(pick == 0) & out] = 0.0
+    flat[(pick == 1) & out] = -0.0
+    flat[pick == 2] *= -1.0
+    return np.asfortranarray(flat.reshape(npts, order="F")), dx
+
+
 def make_field(grid, field):
     """(phi0 Fortran-ordered, dx, h)"""
     from levelsetfortran_amd import fields
 
     npts = GRIDS[grid][0]
-    phi0, dx = fields.two_sphere_phi0(npts)
-    if field == "rough":
-        n = phi0.size
-        flat = phi0.ravel(order="F").copy()
-        flat *= 1.0 + (2.0 * _hash01(n, 1) - 1.0) * 2.0 ** -10
-        pick = np.floor(_hash01(n, 2) * 23.0 * 3.0).astype(np.int64)  # 0, 1, 2: planted; everything else stays
-        out = flat > 0.0  # a zero among negative neighbours has a zero gradient: the 0 / 0 of subs.f90:169, NaN by the book
-        flat[(pick == 0) & out] = 0.0
-        flat[(pick == 1) & out] = -0.0
-        flat[pick == 2] *= -1.0
-        phi0 = np.asfortranarray(flat.reshape(npts, order="F"))
+    phi0, dx = rough_phi0(npts) if field == "rough" else fields.two_sphere_phi0(npts)
     return phi0, dx, fields.reinit_step(dx)
 
 
