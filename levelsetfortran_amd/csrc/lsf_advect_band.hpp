@@ -11,13 +11,8 @@
 // blend at its own point of the output field.  The stage buffers are FULL fields that start as copies of phi: off-list points never
 // change in any of them, so a stencil point outside the list reads phi as it came, whatever the stage.
 //
-// Bounds.  The argument of DESIGN.md sections 4.2 / 4.12, restated for a list: no address is formed outside the field, by
-// construction and not by a range check.  A list entry is an interior point (k_mb_collect<true> keeps 1..n-1 on each axis only, and
-// the host refuses fields beyond 2^31 - 1 points, so an entry is a non-negative 32-bit index below the number of points).  An
-// interior point has all six neighbours at distance 1 inside the field: the first-order branch reads +-1 on each axis and nothing
-// else.  The WENO branch reads +-3 on each axis and is taken only if 4 <= i <= nx-5, 4 <= j <= ny-5 and 4 <= k <= nz-5, where
-// i-3 >= 1 and i+3 <= nx-2 (likewise j, k).  The edge pass reads the mask at the six neighbours of an interior point: the same
-// argument.  u, v, w, speed, the old phi and the store are at the lane's own point.  Lanes with e >= nL touch no memory.
+// Bounds: lsf_band_cell.hpp.  The edge pass reads the mask at the six neighbours of an interior point (band_listed6); u, v, w,
+// speed, the old phi and the store are at the lane's own point.
 //
 // The trace is lsf_advect_field's: the last stage of a step reduces the bit pattern of |new - old| (wave_umax_x) to one partial per
 // block and k_advect_finish, reused as it is, closes the step.  Plain launches only: no atomics, no block waits for another.
@@ -26,19 +21,12 @@
 #include <stdint.h>
 
 #include "lsf_advect_field.hpp"
+#include "lsf_band_cell.hpp"
 #include "lsf_minmax_band.hpp"
 
 namespace lsf {
 
 constexpr int ADVB_EDGE = 1, ADVB_NEG = 2; // the byte of the edge pass: the entry is an edge cell | phi < 0 on entry
-
-// (i, j, k) of a point index
-__device__ __forceinline__ void advb_decode(unsigned p, int nx, int ny, int& i, int& j, int& k)
-{
-    const unsigned sx = (unsigned)(nx + 1), sy = (unsigned)(ny + 1);
-    const unsigned q = p / sx;
-    i = (int)(p - q * sx), k = (int)(q / sy), j = (int)(q - (unsigned)k * sy);
-}
 
 // One stage: list cell e of chunk blockIdx.x.  A = the stage's input field, Bout = its output (never A); P0 = the field at the start
 // of the step, or nullptr: out = t = a - dt R(a); with P0: out = c_old * P0 + c_new * t.  P0 may BE Bout (stage 3 of RK3 writes the
@@ -52,33 +40,19 @@ __global__ __launch_bounds__(MB_CH) void k_advect_band_stage(const double* __res
                                                              double c_old, double c_new, unsigned long long* __restrict__ partials,
                                                              const int* __restrict__ done)
 {
-    __shared__ unsigned long long red[MB_CH / 64];
     if (done[CTL_STOP]) return;
     const int e = blockIdx.x * MB_CH + threadIdx.x;
     unsigned long long acc = 0ull;
     if (e < nL) {
         const unsigned p = (unsigned)L[e];
         int i, j, k;
-        advb_decode(p, nx, ny, i, j, k);
+        band_decode(p, nx, ny, i, j, k);
         const bool weno_ok = i > 3 && i < nx - 4 && j > 3 && j < ny - 4 && k > 3 && k < nz - 4;
         const long rs = nx + 1, ps = (long)(nx + 1) * (ny + 1);
         const double* c = A + p;
         double qx[7], qy[7], qz[7];
         const double phic = c[0];
-        if (weno_ok) { // 4 <= i <= nx-5 and likewise j, k: +-3 on every axis lies inside the field
-#pragma unroll
-            for (int m = 0; m < 7; ++m) {
-                qx[m] = m == 3 ? phic : c[m - 3];
-                qy[m] = m == 3 ? phic : c[(m - 3) * rs];
-                qz[m] = m == 3 ? phic : c[(m - 3) * ps];
-            }
-        } else { // an interior point: +-1 on every axis lies inside the field
-#pragma unroll
-            for (int m = 0; m < 7; ++m) qx[m] = qy[m] = qz[m] = 0.0;
-            qx[2] = c[-1], qx[3] = phic, qx[4] = c[1];
-            qy[2] = c[-rs], qy[3] = phic, qy[4] = c[rs];
-            qz[2] = c[-ps], qz[3] = phic, qz[4] = c[ps];
-        }
+        band_stencil7(c, rs, ps, weno_ok, qx, qy, qz);
         double u = 0.0, v = 0.0, w = 0.0, f = 0.0;
         if constexpr (HASV) u = U[p], v = V[p], w = W[p];
         if constexpr (HASF) f = F[p];
@@ -90,73 +64,29 @@ __global__ __launch_bounds__(MB_CH) void k_advect_band_stage(const double* __res
         axis_pair<STRICT>(qy, weno_ok, false, dx, floor2, ay, by);
         axis_pair<STRICT>(qz, weno_ok, false, dx, floor2, az, bz);
         const double R = advect_rhs<STRICT, HASV, HASF>(ax, bx, ay, by, az, bz, u, v, w, f, inv_dx);
-        double out;
-        if constexpr (STRICT) {
-#pragma clang fp contract(off)
-            const double t = phic - dt * R;
-            out = blend ? c_old * old + c_new * t : t;
-        } else {
-            const double t = __builtin_fma(-dt, R, phic);
-            out = blend ? __builtin_fma(c_old, old, c_new * t) : t;
-        }
+        const double out = stage_blend<STRICT>(phic, dt, R, blend, c_old, old, c_new);
         Bout[p] = out;
         acc = (unsigned long long)__double_as_longlong(__builtin_fabs(out - old));
     }
     if (partials) {
-        acc = wave_umax_x(acc);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long t = red[0];
-            for (int q = 1; q < MB_CH / 64; ++q) t = red[q] > t ? red[q] : t;
-            partials[blockIdx.x] = t;
-        }
+        acc = block_umax<MB_CH / 64>(wave_umax_x(acc), threadIdx.x);
+        if (threadIdx.x == 0) partials[blockIdx.x] = acc;
     }
 }
 
 // The inputs AT LIST CELLS, once per call: the largest |u| + |v| + |w| + |speed| (absent fields left out, added left to right) and
 // the number of non-finite values.  One pair of partials per block; the host finishes (at most ADV_SCAN_BLOCKS pairs), as with
-// k_advect_scan.  Nothing of the inputs outside the list is read: a NaN there is legal.
+// k_advect_scan, whose body this is.  Nothing of the inputs outside the list is read: a NaN there is legal.
 static __global__ __launch_bounds__(256) void k_advect_band_scan(const double* __restrict__ U, const double* __restrict__ V,
                                                                  const double* __restrict__ W, const double* __restrict__ F,
                                                                  const int* __restrict__ L, int nL, double* __restrict__ pmax,
                                                                  unsigned long long* __restrict__ pcnt)
 {
-#pragma clang fp contract(off)
-    __shared__ double rm[4];
-    __shared__ unsigned long long rc[4];
-    double m = 0.0;
-    unsigned long long c = 0ull;
-    for (long e = blockIdx.x * 256L + threadIdx.x; e < nL; e += 256L * gridDim.x) {
-        const int p = L[e];
-        double s = 0.0;
-        if (U) {
-            const double a = U[p], b = V[p], d = W[p];
-            c += (unsigned long long)(!__builtin_isfinite(a)) + (unsigned long long)(!__builtin_isfinite(b)) + (unsigned long long)(!__builtin_isfinite(d));
-            s = (__builtin_fabs(a) + __builtin_fabs(b)) + __builtin_fabs(d);
-        }
-        if (F) {
-            const double a = F[p];
-            c += (unsigned long long)(!__builtin_isfinite(a));
-            s = s + __builtin_fabs(a);
-        }
-        m = __builtin_fmax(m, s);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        m = __builtin_fmax(m, __shfl_xor(m, o, 64));
-        c += __shfl_xor(c, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) rm[threadIdx.x >> 6] = m, rc[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        pmax[blockIdx.x] = __builtin_fmax(__builtin_fmax(rm[0], rm[1]), __builtin_fmax(rm[2], rm[3]));
-        pcnt[blockIdx.x] = (rc[0] + rc[1]) + (rc[2] + rc[3]);
-    }
+    advect_scan_body<true>(U, V, W, F, L, nL, pmax, pcnt);
 }
 
 // The edge pass, once per call, before the first step: one byte per list entry.  ADVB_EDGE: at least one of the six axis
-// neighbours is not in LIST (a wall point never is; any mask value but 1 means "not in the list"); ADVB_NEG: phi < 0 on entry.
+// neighbours is not in LIST (band_listed6); ADVB_NEG: phi < 0 on entry.
 static __global__ __launch_bounds__(256) void k_advect_band_edge(const int32_t* __restrict__ mask, const double* __restrict__ phi,
                                                                  const int* __restrict__ L, int nL, int nx, int ny, int nz,
                                                                  unsigned char* __restrict__ flag)
@@ -165,12 +95,8 @@ static __global__ __launch_bounds__(256) void k_advect_band_edge(const int32_t* 
     if (e >= nL) return;
     const unsigned p = (unsigned)L[e];
     int i, j, k;
-    advb_decode(p, nx, ny, i, j, k);
-    const long rs = nx + 1, ps = (long)(nx + 1) * (ny + 1);
-    const int32_t* m = mask + p;
-    // the neighbour along an axis is in LIST if it is interior on that axis (the other two coordinates are this cell's) and its mask is 1
-    const bool in = (i > 1 && m[-1] == 1) && (i < nx - 1 && m[1] == 1) && (j > 1 && m[-rs] == 1) && (j < ny - 1 && m[rs] == 1) &&
-                    (k > 1 && m[-ps] == 1) && (k < nz - 1 && m[ps] == 1);
+    band_decode(p, nx, ny, i, j, k);
+    const bool in = band_listed6(mask + p, i, j, k, nx, ny, nz, nx + 1, (long)(nx + 1) * (ny + 1));
     flag[e] = (unsigned char)((in ? 0 : ADVB_EDGE) | (phi[p] < 0.0 ? ADVB_NEG : 0));
 }
 
@@ -194,12 +120,9 @@ static __global__ __launch_bounds__(256) void k_advect_band_close(const double* 
             nf += (unsigned long long)((x < 0.0) != ((fl & ADVB_NEG) != 0));
         }
     }
-    mn = ~wave_umax_x(~mn);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        ne += __shfl_xor(ne, o, 64);
-        nf += __shfl_xor(nf, o, 64);
-    }
+    // counts and a minimum: the wave-level pieces of lsf_block_reduce.hpp, one barrier
+    mn = wave_umin(mn);
+    wave_usum_each(ne, nf);
     if ((threadIdx.x & 63) == 0) rmn[threadIdx.x >> 6] = mn, re[threadIdx.x >> 6] = ne, rf[threadIdx.x >> 6] = nf;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lsf_block_reduce.hpp"
 #include "lsf_kernels.hpp"
 
 namespace lsf {
@@ -34,38 +35,6 @@ constexpr int ADV_SCAN_BLOCKS = 1024;  // most blocks of the input scan (k_advec
 // the largest of them and every NaN (sign cleared) lies above +inf -- one integer maximum gives "the largest change, NaN if any
 // is NaN" whatever the order of the operands, so the trace is the same from run to run and between the seams.
 constexpr unsigned long long ADV_INF_BITS = 0x7ff0000000000000ull;
-
-// butterfly maximum over the 64 lanes, the lane exchanges of wave_sum_x (lsf_kernels.hpp): no LDS round trips
-__device__ __forceinline__ unsigned long long wave_umax_x(unsigned long long v)
-{
-    auto lo = [](unsigned long long x) { return (int)(unsigned)(x & 0xffffffffull); };
-    auto hi = [](unsigned long long x) { return (int)(unsigned)(x >> 32); };
-    auto join = [](int l, int h) { return ((unsigned long long)(unsigned)h << 32) | (unsigned long long)(unsigned)l; };
-    auto mx = [](unsigned long long a, unsigned long long b) { return a > b ? a : b; };
-    {   // partner 32 lanes away
-        const auto l = __builtin_amdgcn_permlane32_swap(lo(v), lo(v), false, false);
-        const auto h = __builtin_amdgcn_permlane32_swap(hi(v), hi(v), false, false);
-        v = mx(join(l[0], h[0]), join(l[1], h[1]));
-    }
-    {   // 16 lanes away
-        const auto l = __builtin_amdgcn_permlane16_swap(lo(v), lo(v), false, false);
-        const auto h = __builtin_amdgcn_permlane16_swap(hi(v), hi(v), false, false);
-        v = mx(join(l[0], h[0]), join(l[1], h[1]));
-    }
-    // 8 lanes away: row_ror:8
-    v = mx(v, join(__builtin_amdgcn_update_dpp(0, lo(v), 0x128, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(0, hi(v), 0x128, 0xf, 0xf, false)));
-    {   // 4 lanes away: row_ror:12 for banks 0 and 2, row_ror:4 for banks 1 and 3
-        int l = __builtin_amdgcn_update_dpp(0, lo(v), 0x12c, 0xf, 0x5, false);
-        l = __builtin_amdgcn_update_dpp(l, lo(v), 0x124, 0xf, 0xa, false);
-        int h = __builtin_amdgcn_update_dpp(0, hi(v), 0x12c, 0xf, 0x5, false);
-        h = __builtin_amdgcn_update_dpp(h, hi(v), 0x124, 0xf, 0xa, false);
-        v = mx(v, join(l, h));
-    }
-    // 2 and 1 lanes away: quad_perm [2,3,0,1] and [1,0,3,2]
-    v = mx(v, join(__builtin_amdgcn_update_dpp(0, lo(v), 0x4e, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(0, hi(v), 0x4e, 0xf, 0xf, false)));
-    v = mx(v, join(__builtin_amdgcn_update_dpp(0, lo(v), 0xb1, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(0, hi(v), 0xb1, 0xf, 0xf, false)));
-    return v;
-}
 
 // R = u . grad(phi) + F |grad(phi)| of one cell from its three pairs of one-sided derivatives (include/lsf.h, lsf_advect_field).
 // STRICT: true derivatives, evaluated as written, left to right, no contraction.  FAST: derivatives times dx (axis_pair<false>),
@@ -111,6 +80,25 @@ __device__ __forceinline__ double advect_rhs(double ax, double bx, double ay, do
     }
 }
 
+// What a stage stores for one cell: t = a - dt R (TRANSPORT) + dt C (CURV, lsf_evolve_band_curv.hpp), or c_old * old + c_new * t
+// when the stage blends.  STRICT: as written, no contraction.  Shared by the stage kernels of the grid and of the band.
+template <bool STRICT, bool TRANSPORT = true, bool CURV = false>
+__device__ __forceinline__ double stage_blend(double phic, double dt, double R, bool blend, double c_old, double old, double c_new, double C = 0.0)
+{
+    if constexpr (STRICT) {
+#pragma clang fp contract(off)
+        double t = phic;
+        if constexpr (TRANSPORT) t = phic - dt * R;
+        if constexpr (CURV) t = t + dt * C;
+        return blend ? c_old * old + c_new * t : t;
+    } else {
+        double t = phic;
+        if constexpr (TRANSPORT) t = __builtin_fma(-dt, R, phic);
+        if constexpr (CURV) t = __builtin_fma(dt, C, t);
+        return blend ? __builtin_fma(c_old, old, c_new * t) : t;
+    }
+}
+
 // One stage over the interior cells 1..n-1.  A = the stage's input field, Bout = its output (never A); P0 = the field at the start
 // of the step, or nullptr: out = t = a - dt R(a); with P0: out = c_old * P0 + c_new * t.  P0 may BE Bout (stage 3 of RK3 writes the
 // caller's field in place): a lane reads P0 at its own point only, before it stores there.  partials != nullptr: the last stage
@@ -125,7 +113,6 @@ __global__ __launch_bounds__(ADV_BX* ADV_BY) void k_advect_stage(const double* _
                                                                   unsigned long long* __restrict__ partials, const int* __restrict__ done,
                                                                   int nbx, int nby, int nbz)
 {
-    __shared__ unsigned long long red[ADV_BX * ADV_BY / 64];
     if (done && done[CTL_STOP]) return;
     const unsigned per = gridDim.x >> 3;
     const unsigned L = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
@@ -183,15 +170,7 @@ __global__ __launch_bounds__(ADV_BX* ADV_BY) void k_advect_stage(const double* _
             axis_pair<STRICT>(qy, weno_ok, false, dx, floor2, ay, by);
             axis_pair<STRICT>(qz, weno_ok, false, dx, floor2, az, bz);
             const double R = advect_rhs<STRICT, HASV, HASF>(ax, bx, ay, by, az, bz, u, v, w, f, inv_dx);
-            double out;
-            if constexpr (STRICT) {
-#pragma clang fp contract(off)
-                const double t = phic - dt * R;
-                out = blend ? c_old * old + c_new * t : t;
-            } else {
-                const double t = __builtin_fma(-dt, R, phic);
-                out = blend ? __builtin_fma(c_old, old, c_new * t) : t;
-            }
+            const double out = stage_blend<STRICT>(phic, dt, R, blend, c_old, old, c_new);
             {
                 typedef unsigned u2 __attribute__((ext_vector_type(2)));
                 u2 s;
@@ -206,13 +185,8 @@ __global__ __launch_bounds__(ADV_BX* ADV_BY) void k_advect_stage(const double* _
     if (partials) {
         acc = wave_umax_x(acc);
         const int tid = threadIdx.x + ADV_BX * threadIdx.y;
-        if ((tid & 63) == 0) red[tid >> 6] = acc;
-        __syncthreads();
-        if (tid == 0) {
-            unsigned long long t = red[0];
-            for (int q = 1; q < ADV_BX * ADV_BY / 64; ++q) t = red[q] > t ? red[q] : t;
-            partials[L] = t;
-        }
+        acc = block_umax<ADV_BX * ADV_BY / 64>(acc, tid);
+        if (tid == 0) partials[L] = acc;
     }
 }
 
@@ -255,16 +229,21 @@ static __global__ __launch_bounds__(RED_T) void k_advect_finish(const unsigned l
 
 // The inputs, once per call: the largest |u| + |v| + |w| + |speed| over all points (absent fields left out, added left to right)
 // and the number of non-finite values.  One pair of partials per block; the host finishes (at most ADV_SCAN_BLOCKS pairs).
-static __global__ __launch_bounds__(256) void k_advect_scan(const double* __restrict__ U, const double* __restrict__ V, const double* __restrict__ W,
-                                                            const double* __restrict__ F, long n, double* __restrict__ pmax,
-                                                            unsigned long long* __restrict__ pcnt)
+// The body scans n entries: the points 0 .. n-1 themselves (LIST false, k_advect_scan) or the points L[0 .. n-1] (LIST true,
+// k_advect_band_scan of lsf_advect_band.hpp).
+template <bool LIST>
+__device__ __forceinline__ void advect_scan_body(const double* __restrict__ U, const double* __restrict__ V, const double* __restrict__ W,
+                                                 const double* __restrict__ F, const int* __restrict__ L, long n, double* __restrict__ pmax,
+                                                 unsigned long long* __restrict__ pcnt)
 {
 #pragma clang fp contract(off)
     __shared__ double rm[4];
     __shared__ unsigned long long rc[4];
     double m = 0.0;
     unsigned long long c = 0ull;
-    for (long p = blockIdx.x * 256L + threadIdx.x; p < n; p += 256L * gridDim.x) {
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += 256L * gridDim.x) {
+        long p = e;
+        if constexpr (LIST) p = L[e];
         double s = 0.0;
         if (U) {
             const double a = U[p], b = V[p], d = W[p];
@@ -279,16 +258,21 @@ static __global__ __launch_bounds__(256) void k_advect_scan(const double* __rest
         m = __builtin_fmax(m, s);
     }
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        m = __builtin_fmax(m, __shfl_xor(m, o, 64));
-        c += __shfl_xor(c, o, 64);
-    }
+    for (int o = 32; o >= 1; o >>= 1) m = __builtin_fmax(m, __shfl_xor(m, o, 64));
+    c = wave_usum(c);
     if ((threadIdx.x & 63) == 0) rm[threadIdx.x >> 6] = m, rc[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
         pmax[blockIdx.x] = __builtin_fmax(__builtin_fmax(rm[0], rm[1]), __builtin_fmax(rm[2], rm[3]));
         pcnt[blockIdx.x] = (rc[0] + rc[1]) + (rc[2] + rc[3]);
     }
+}
+
+static __global__ __launch_bounds__(256) void k_advect_scan(const double* __restrict__ U, const double* __restrict__ V, const double* __restrict__ W,
+                                                            const double* __restrict__ F, long n, double* __restrict__ pmax,
+                                                            unsigned long long* __restrict__ pcnt)
+{
+    advect_scan_body<false>(U, V, W, F, nullptr, n, pmax, pcnt);
 }
 
 } // namespace lsf

@@ -10,21 +10,20 @@
 // contraction and stores up to three values at its own point.  The optional outputs are chosen by template instance: a lane never
 // branches on them and an instance without gauss does not compute K.
 //
-// Bounds.  The argument of lsf_advect_band.hpp, restated: no address is formed outside the field, by construction and not by a range
-// check.  A list entry is an interior point (k_mb_collect<true> keeps 1..n-1 on each axis only, and the host refuses fields beyond
-// 2^31 - 1 points, so an entry is a non-negative 32-bit index below the number of points).  Every stencil point is at an offset in
-// {-1, 0, 1}^3 of an interior point: 0 <= i-1, i+1 <= nx, likewise j and k.  The stores are at the lane's own point.  Lanes with
-// e >= nL touch no memory.
+// Bounds: lsf_band_cell.hpp.  What is this kernel's own: every stencil point, the 12 diagonals among them, is at an offset in
+// {-1, 0, 1}^3 of an interior point.  The stores are at the lane's own point.
 //
 // The report: per block three counts (degenerate, clamped and non-finite cells) and the bit pattern of the largest |kappa| as stored
-// (wave_umax_x; every NaN lies above +inf, and on LSF_OK there is none), finished by the host in block order.  Counts are integers
-// and the maximum is one of bit patterns, so no order of reduction reaches a result.  One plain launch: no atomics, no block waits
-// for another.
+// (wave_umax_x of lsf_block_reduce.hpp; every NaN lies above +inf, and on LSF_OK there is none), finished by the host in block order.
+// Counts are integers and the maximum is one of bit patterns, so no order of reduction reaches a result.  One plain launch: no
+// atomics, no block waits for another.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "lsf_advect_band.hpp"
+#include "lsf_band_cell.hpp"
+#include "lsf_block_reduce.hpp"
+#include "lsf_minmax_band.hpp"
 
 namespace lsf {
 
@@ -117,13 +116,9 @@ __global__ __launch_bounds__(MB_CH) void k_curvature_band(const double* __restri
         ndeg = deg ? 1ull : 0ull, nclamp = clamped ? 1ull : 0ull, nbad = bad ? 1ull : 0ull;
         amax = (unsigned long long)__double_as_longlong(__builtin_fabs(H));
     }
+    // counts and a maximum: the wave-level pieces of lsf_block_reduce.hpp, one LDS array, one barrier
     amax = wave_umax_x(amax);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        ndeg += __shfl_xor(ndeg, o, 64);
-        nclamp += __shfl_xor(nclamp, o, 64);
-        nbad += __shfl_xor(nbad, o, 64);
-    }
+    wave_usum_each(ndeg, nclamp, nbad);
     if ((threadIdx.x & 63) == 0) {
         unsigned long long* r = red[threadIdx.x >> 6];
         r[0] = ndeg, r[1] = nclamp, r[2] = nbad, r[3] = amax;

@@ -18,13 +18,11 @@
 //   k_evb_edge       over the new list, after k_evb_enter has completed the mask: the open-edge flag, the sign of phi (the reference
 //                    of the flips until the next build) and the wall-adjacent flag, one byte per list entry.
 //
-// Bounds.  The argument of DESIGN.md sections 4.2 / 4.12 / 4.15, restated: no address is formed outside the field, by construction.
-// A list entry is an interior point (the first list comes from k_mb_collect<true>, which keeps 1..n-1 on each axis; every later one
-// from the same kernel run on the scratch mask, which k_evb_dilate writes at interior points only), a non-negative 32-bit index
-// below the number of points.  k_evb_dilate clips its cube to 1..n-1 on each axis BEFORE it forms an address: i0 = max(i - ring, 1),
-// i1 = min(i + ring, nx - 1), likewise j and k, and 1 <= i0 <= i <= i1 <= nx - 1 because the cell itself is interior.  k_evb_edge
-// reads the mask at the six neighbours of an interior point: distance 1, inside the field.  Every other access is at the lane's own
-// point or its own list entry; lanes with e >= nL touch no memory.
+// Bounds: lsf_band_cell.hpp.  What is this file's own: every list after the first comes from k_mb_collect<true> run on the scratch
+// mask, which k_evb_dilate writes at interior points only, so its entries are interior points too.  k_evb_dilate clips its cube to
+// 1..n-1 on each axis BEFORE it forms an address: i0 = max(i - ring, 1), i1 = min(i + ring, nx - 1), likewise j and k, and
+// 1 <= i0 <= i <= i1 <= nx - 1 because the cell itself is interior.  k_evb_edge reads the mask at the six neighbours of an interior
+// point: distance 1, inside the field.  Every other access is at the lane's own point or its own list entry.
 //
 // Plain launches only: no atomics, no block waits for another; every reduction is a bit-pattern minimum or an integer count, so the
 // order of the list reaches no result.
@@ -80,13 +78,9 @@ static __global__ __launch_bounds__(256) void k_evb_check(const double* __restri
             if (fl & EVB_WALL) nw += (unsigned long long)(__builtin_fabs(x) < core_dx);
         }
     }
-    mn = ~wave_umax_x(~mn);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        ne += __shfl_xor(ne, o, 64);
-        nf += __shfl_xor(nf, o, 64);
-        nw += __shfl_xor(nw, o, 64);
-    }
+    // counts and a minimum: the wave-level pieces of lsf_block_reduce.hpp, one barrier
+    mn = wave_umin(mn);
+    wave_usum_each(ne, nf, nw);
     if ((threadIdx.x & 63) == 0) rmn[threadIdx.x >> 6] = mn, re[threadIdx.x >> 6] = ne, rf[threadIdx.x >> 6] = nf, rw[threadIdx.x >> 6] = nw;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -111,13 +105,8 @@ static __global__ __launch_bounds__(256) void k_evb_check_finish(const unsigned 
         mn = x < mn ? x : mn;
         ne += part[nb + b], nf += part[2 * nb + b], nw += part[3 * nb + b];
     }
-    mn = ~wave_umax_x(~mn);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        ne += __shfl_xor(ne, o, 64);
-        nf += __shfl_xor(nf, o, 64);
-        nw += __shfl_xor(nw, o, 64);
-    }
+    mn = wave_umin(mn);
+    wave_usum_each(ne, nf, nw);
     if ((threadIdx.x & 63) == 0) rmn[threadIdx.x >> 6] = mn, re[threadIdx.x >> 6] = ne, rf[threadIdx.x >> 6] = nf, rw[threadIdx.x >> 6] = nw;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -142,7 +131,7 @@ static __global__ __launch_bounds__(256) void k_evb_dilate(const double* __restr
     const unsigned p = (unsigned)L[e];
     if (!(__builtin_fabs(phi[p]) < core_dx)) return;
     int i, j, k;
-    advb_decode(p, nx, ny, i, j, k);
+    band_decode(p, nx, ny, i, j, k);
     const int i0 = max(i - ring, 1), i1 = min(i + ring, nx - 1);
     const int j0 = max(j - ring, 1), j1 = min(j + ring, ny - 1);
     const int k0 = max(k - ring, 1), k1 = min(k + ring, nz - 1);
@@ -172,7 +161,6 @@ static __global__ __launch_bounds__(256) void k_evb_enter(const int* __restrict_
                                                           double* __restrict__ W1, double* __restrict__ W2, int32_t* __restrict__ mask,
                                                           unsigned long long* __restrict__ counts)
 {
-    __shared__ unsigned long long rc[4];
     const int e = blockIdx.x * 256 + threadIdx.x;
     unsigned long long c = 0ull;
     if (e < nL) {
@@ -186,24 +174,17 @@ static __global__ __launch_bounds__(256) void k_evb_enter(const int* __restrict_
             c = 1ull;
         }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) rc[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (rc[0] + rc[1]) + (rc[2] + rc[3]);
+    c = block_usum<4>(c, threadIdx.x);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
 // the entering cells of a rebuild, added to the record's running sum (one block)
 static __global__ __launch_bounds__(256) void k_evb_enter_finish(const unsigned long long* __restrict__ counts, int n, unsigned long long* __restrict__ rec)
 {
-    __shared__ unsigned long long rc[4];
     unsigned long long c = 0ull;
     for (int b = threadIdx.x; b < n; b += 256) c += counts[b];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) rc[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) rec[EVB_R_ENTERED] += (rc[0] + rc[1]) + (rc[2] + rc[3]);
+    c = block_usum<4>(c, threadIdx.x);
+    if (threadIdx.x == 0) rec[EVB_R_ENTERED] += c;
 }
 
 // the open-edge/sign pass: one byte per list entry, from the caller's mask (1 on the list, 0 elsewhere) and the field as they are.
@@ -216,7 +197,7 @@ static __global__ __launch_bounds__(256) void k_evb_edge(const int32_t* __restri
     if (e >= nL) return;
     const unsigned p = (unsigned)L[e];
     int i, j, k;
-    advb_decode(p, nx, ny, i, j, k);
+    band_decode(p, nx, ny, i, j, k);
     const long rs = nx + 1, ps = (long)(nx + 1) * (ny + 1);
     const int32_t* m = mask + p;
     const bool open = (i > 1 && m[-1] != 1) || (i < nx - 1 && m[1] != 1) || (j > 1 && m[-rs] != 1) || (j < ny - 1 && m[rs] != 1) ||

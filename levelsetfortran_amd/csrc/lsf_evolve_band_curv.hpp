@@ -3,21 +3,19 @@
 //
 //     phi_t + u . grad(phi) + F |grad(phi)| = bcurv * kappa * |grad(phi)|
 //
-// k_advect_band_curv_stage is k_advect_band_stage with one more term: one lane per list cell, MB_CH consecutive entries per block.  A
-// lane decodes (i, j, k), gathers from the stage's input field the cell, +-1 on each axis and the 12 edge diagonals (the 19 values of
-// lsf_curvature_band.hpp) and, where a velocity or a speed is present and the cell is WENO, +-2 and +-3 on each axis (31 values in
-// all); it reads u, v, w, speed and the step's old phi at its own point and stores the blend at its own point of the output field.
-// axis_pair, advect_rhs and advb_decode are used unchanged; the curvature arithmetic is curv_derivs / curv_mean of
-// lsf_curvature_band.hpp, uncontracted in STRICT and in FAST alike.  The instance without velocity and speed is pure curvature flow:
-// it holds no transport code and gathers 19 values.  The partials / done protocol and the in-place stage 3 are those of
-// k_advect_band_stage.
+// k_advect_band_curv_stage is k_advect_band_stage with one more term, built from the same pieces (band_decode and band_stencil7 of
+// lsf_band_cell.hpp, axis_pair, advect_rhs, stage_blend, block_umax): one lane per list cell, MB_CH consecutive entries per block.
+// The two kernels stay two bodies: a per-cell function shared between them is optimised on its own before it is inlined and
+// changes the machine code of both (see lsf_band_cell.hpp on the WENO rule).  A lane gathers from the stage's
+// input field the cell, +-1 on each axis and the 12 edge diagonals (the 19 values of lsf_curvature_band.hpp) and, where a velocity
+// or a speed is present and the cell is WENO, +-2 and +-3 on each axis (31 values in all); it reads u, v, w, speed and the step's old
+// phi at its own point and stores the blend at its own point of the output field.  The curvature arithmetic is curv_derivs /
+// curv_mean of lsf_curvature_band.hpp, uncontracted in STRICT and in FAST alike.  The instance without velocity and speed is pure
+// curvature flow: it holds no transport code and gathers 19 values.  The partials / done protocol and the in-place stage 3 are those
+// of k_advect_band_stage.
 //
-// Bounds.  The argument of lsf_advect_band.hpp, restated: no address is formed outside the field, by construction and not by a range
-// check.  A list entry is an interior point (k_mb_collect<true> keeps 1..n-1 on each axis only, and the host refuses fields beyond
-// 2^31 - 1 points, so an entry is a non-negative 32-bit index below the number of points).  Every one of the 19 curvature values,
-// the 12 diagonals among them, is at an offset in {-1, 0, 1}^3 of that interior point: 0 <= i-1, i+1 <= nx, likewise j and k.  The
-// WENO values at +-2 and +-3 are read only if 4 <= i <= nx-5, 4 <= j <= ny-5 and 4 <= k <= nz-5, where i-3 >= 1 and i+3 <= nx-2
-// (likewise j, k).  u, v, w, speed, the old phi and the store are at the lane's own point.  Lanes with e >= nL touch no memory.
+// Bounds: lsf_band_cell.hpp.  What is this kernel's own: every one of the 19 curvature values, the 12 diagonals among them, is at an
+// offset in {-1, 0, 1}^3 of an interior point.
 //
 // Plain launches only: no atomics, no block waits for another.
 #pragma once
@@ -41,7 +39,6 @@ __global__ __launch_bounds__(MB_CH) void k_advect_band_curv_stage(const double* 
                                                                   double four_dx2, double lim, unsigned long long* __restrict__ partials,
                                                                   const int* __restrict__ done)
 {
-    __shared__ unsigned long long red[MB_CH / 64];
     if (done[CTL_STOP]) return;
     const int e = blockIdx.x * MB_CH + threadIdx.x;
     unsigned long long acc = 0ull;
@@ -67,23 +64,10 @@ __global__ __launch_bounds__(MB_CH) void k_advect_band_curv_stage(const double* 
         double R = 0.0;
         if constexpr (HASV || HASF) {
             int i, j, k;
-            advb_decode(p, nx, ny, i, j, k);
+            band_decode(p, nx, ny, i, j, k);
             const bool weno_ok = i > 3 && i < nx - 4 && j > 3 && j < ny - 4 && k > 3 && k < nz - 4;
             double qx[7], qy[7], qz[7];
-            if (weno_ok) { // 4 <= i <= nx-5 and likewise j, k: +-3 on every axis lies inside the field
-#pragma unroll
-                for (int m = 0; m < 7; ++m) {
-                    qx[m] = m == 3 ? phic : c[m - 3];
-                    qy[m] = m == 3 ? phic : c[(m - 3) * rs];
-                    qz[m] = m == 3 ? phic : c[(m - 3) * ps];
-                }
-            } else { // an interior point: +-1 on every axis lies inside the field
-#pragma unroll
-                for (int m = 0; m < 7; ++m) qx[m] = qy[m] = qz[m] = 0.0;
-                qx[2] = c[-1], qx[3] = phic, qx[4] = c[1];
-                qy[2] = c[-rs], qy[3] = phic, qy[4] = c[rs];
-                qz[2] = c[-ps], qz[3] = phic, qz[4] = c[ps];
-            }
+            band_stencil7(c, rs, ps, weno_ok, qx, qy, qz);
             double u = 0.0, v = 0.0, w = 0.0, f = 0.0;
             if constexpr (HASV) u = U[p], v = V[p], w = W[p];
             if constexpr (HASF) f = F[p];
@@ -94,31 +78,13 @@ __global__ __launch_bounds__(MB_CH) void k_advect_band_curv_stage(const double* 
             axis_pair<STRICT>(qz, weno_ok, false, dx, floor2, az, bz);
             R = advect_rhs<STRICT, HASV, HASF>(ax, bx, ay, by, az, bz, u, v, w, f, inv_dx);
         }
-        double out;
-        if constexpr (STRICT) {
-#pragma clang fp contract(off)
-            double t0 = phic;
-            if constexpr (HASV || HASF) t0 = phic - dt * R;
-            const double t = t0 + dt * C;
-            out = blend ? c_old * old + c_new * t : t;
-        } else {
-            double t0 = phic;
-            if constexpr (HASV || HASF) t0 = __builtin_fma(-dt, R, phic);
-            const double t = __builtin_fma(dt, C, t0);
-            out = blend ? __builtin_fma(c_old, old, c_new * t) : t;
-        }
+        const double out = stage_blend<STRICT, HASV || HASF, true>(phic, dt, R, blend, c_old, old, c_new, C);
         Bout[p] = out;
         acc = (unsigned long long)__double_as_longlong(__builtin_fabs(out - old));
     }
     if (partials) {
-        acc = wave_umax_x(acc);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long t = red[0];
-            for (int q = 1; q < MB_CH / 64; ++q) t = red[q] > t ? red[q] : t;
-            partials[blockIdx.x] = t;
-        }
+        acc = block_umax<MB_CH / 64>(wave_umax_x(acc), threadIdx.x);
+        if (threadIdx.x == 0) partials[blockIdx.x] = acc;
     }
 }
 

@@ -21,10 +21,8 @@
 // p > 0 of a batch return at once when cnt[p - 1] == 0: their own cnt[p] stays 0 and the rest of the batch drains empty.  The only
 // atomic is that integer add, one per block and pass: no arrival order reaches a result.
 //
-// Bounds, by construction and not by a range check (the argument of lsf_advect_band.hpp): a list entry is an interior point
-// (k_mb_collect<true> keeps 1..n-1 on each axis only, and the host refuses fields beyond 2^31 - 1 points), so p - 1, p + 1 and the
-// points one row and one plane away exist.  The plan's indices are such neighbours or p itself.  Per-entry arrays are indexed by
-// e < nL only.  Lanes with e >= nL touch no memory.
+// Bounds: lsf_band_cell.hpp (a list entry is an interior point, so p - 1, p + 1 and the points one row and one plane away exist).
+// What is this file's own: the plan's indices are such neighbours or p itself, and per-entry arrays are indexed by e < nL only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,28 +32,6 @@
 namespace lsf {
 
 constexpr int EXTB_NPART = 3; // partials per block of k_extb_plan: frozen cells, frozen cells with a non-finite q, cells that see a non-finite phi
-
-// block sum of up to EXTB_NPART per-lane counts, written by lane 0 to out[0..N)
-template <int N>
-__device__ __forceinline__ void extb_block_sum(unsigned long long (&v)[N], unsigned long long* out)
-{
-    __shared__ unsigned long long red[MB_CH / 64][N];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1)
-#pragma unroll
-        for (int m = 0; m < N; ++m) v[m] += __shfl_xor(v[m], o, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int m = 0; m < N; ++m) red[threadIdx.x >> 6][m] = v[m];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int m = 0; m < N; ++m) {
-            unsigned long long t = red[0][m];
-            for (int w = 1; w < MB_CH / 64; ++w) t += red[w][m];
-            out[m] = t;
-        }
-}
 
 // nb: 3 x nL point indices, wt: 3 x nL weights (axis-major), fz: nL flags, part: EXTB_NPART words per block.
 // known == nullptr: frozen = |phi| < far.
@@ -93,7 +69,7 @@ __global__ __launch_bounds__(MB_CH) void k_extb_plan(const double* __restrict__ 
         v[1] = frozen && !__builtin_isfinite(q[p]) ? 1ull : 0ull;
         v[2] = badphi ? 1ull : 0ull;
     }
-    extb_block_sum<EXTB_NPART>(v, part + (size_t)blockIdx.x * EXTB_NPART);
+    block_usum_out<MB_CH / 64>(v, threadIdx.x, part + (size_t)blockIdx.x * EXTB_NPART);
 }
 
 __global__ __launch_bounds__(MB_CH) void k_extb_init(double* __restrict__ q, const int* __restrict__ L, const unsigned char* __restrict__ fz, int nL)
@@ -161,7 +137,7 @@ __global__ __launch_bounds__(MB_CH) void k_extb_count(const double* __restrict__
         v[0] = x == x ? 1ull : 0ull;
         v[1] = x == x ? 0ull : 1ull;
     }
-    extb_block_sum<2>(v, part + (size_t)blockIdx.x * 2);
+    block_usum_out<MB_CH / 64>(v, threadIdx.x, part + (size_t)blockIdx.x * 2);
 }
 
 } // namespace lsf

@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lsf_block_reduce.hpp"
+
 namespace lsf {
 
 constexpr int XS_BX = 64, XS_BY = 4; // a block of k_extract_count: 64 points along x by 4 rows
@@ -107,13 +109,6 @@ __host__ __device__ __forceinline__ void xs_classify(unsigned lowp, unsigned upp
     bad = (unsigned)__builtin_popcount(mask & ((nonf & 1u) ? 0x7fu : (nonf >> 1)));
 }
 
-__device__ __forceinline__ unsigned long long xs_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- classify and count ------------------------------------------------------------------------------------------------
 // The launch is one-dimensional: block L = x block fastest, then y, then the chunks along z.
 static __global__ __launch_bounds__(XS_BX* XS_BY) void k_extract_count(const double* __restrict__ phi, int nx, int ny, int nz, double iso,
@@ -158,8 +153,8 @@ static __global__ __launch_bounds__(XS_BX* XS_BY) void k_extract_count(const dou
             lowp = upp;
         }
     }
-    cells = xs_wave_sum(cells);
-    bad = xs_wave_sum(bad);
+    cells = wave_usum(cells);
+    bad = wave_usum(bad);
     if (((threadIdx.x + XS_BX * threadIdx.y) & 63u) == 0u) {
         if (cells) atomicAdd(&ctl[XS_CELLS], cells);
         if (bad) atomicAdd(&ctl[XS_BAD], bad);
@@ -297,7 +292,7 @@ static __global__ __launch_bounds__(XS_T) void k_extract_emit(const double* __re
             });
         }
     }
-    t1 = xs_wave_sum(t1);
+    t1 = wave_usum(t1);
     if ((threadIdx.x & 63u) == 0u && t1) atomicAdd(&ctl[XS_T1], t1);
 }
 

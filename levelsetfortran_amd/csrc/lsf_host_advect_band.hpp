@@ -9,19 +9,10 @@ void advect_band_stage_launch(bool strict, const double* A, double* B, const dou
                               double c_new, unsigned long long* part, const int* ctl, hipStream_t st)
 {
     const dim3 grid((unsigned)nchunks), blk(MB_CH);
-#define LSF_ADVB_CALL(S, HV, HF) \
-    hipLaunchKernelGGL((k_advect_band_stage<S, HV, HF>), grid, blk, 0, st, A, B, P0, d_u, d_v, d_w, d_f, L, nL, nx, ny, nz, dx, dt, c_old, c_new, part, ctl)
-    const bool hv = d_u != nullptr, hf = d_f != nullptr;
-    if (strict) {
-        if (hv && hf) LSF_ADVB_CALL(true, true, true);
-        else if (hv) LSF_ADVB_CALL(true, true, false);
-        else LSF_ADVB_CALL(true, false, true);
-    } else {
-        if (hv && hf) LSF_ADVB_CALL(false, true, true);
-        else if (hv) LSF_ADVB_CALL(false, true, false);
-        else LSF_ADVB_CALL(false, false, true);
-    }
-#undef LSF_ADVB_CALL
+    with_stage_instance<false>(strict, d_u != nullptr, d_f != nullptr, [&](auto S, auto HV, auto HF) {
+        hipLaunchKernelGGL((k_advect_band_stage<decltype(S)::value, decltype(HV)::value, decltype(HF)::value>), grid, blk, 0, st, A, B, P0, d_u,
+                           d_v, d_w, d_f, L, nL, nx, ny, nz, dx, dt, c_old, c_new, part, ctl);
+    });
 }
 
 // Every error is found before anything is written: the arguments, then the list (the mask is read once), then the inputs at its
@@ -56,22 +47,8 @@ int advect_band_core(double* d_phi, const int32_t* d_mask, const double* d_u, co
     // the inputs at list cells: cfl and the non-finite count
     {
         double* pmax = (double*)c.slot[S_PART2].p;
-        unsigned long long* pcnt = (unsigned long long*)(pmax + nb);
-        hipLaunchKernelGGL(k_advect_band_scan, dim3((unsigned)nb), dim3(256), 0, st, d_u, d_v, d_w, d_f, L, nL, pmax, pcnt);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h.data(), pmax, (size_t)nb * 16, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        double m = 0.0;
-        unsigned long long bad = 0;
-        for (int b = 0; b < nb; ++b) {
-            double x;
-            std::memcpy(&x, &h[b], sizeof x);
-            m = x > m ? x : m;
-            bad += h[(size_t)nb + b];
-        }
-        if (bad)
-            return fail(LSF_ERR_INVALID, "lsf_advect_field_band: " + std::to_string(bad) + " non-finite value(s) in u, v, w, speed at list cells");
-        if (cfl) *cfl = (dt * m) / dx;
+        hipLaunchKernelGGL(k_advect_band_scan, dim3((unsigned)nb), dim3(256), 0, st, d_u, d_v, d_w, d_f, L, nL, pmax, (unsigned long long*)(pmax + nb));
+        if ((rc = advect_scan_finish(pmax, nb, dx, dt, cfl, "lsf_advect_field_band", " at list cells", st))) return rc;
     }
     if (steps_done) *steps_done = 0;
 
@@ -101,13 +78,8 @@ int advect_band_core(double* d_phi, const int32_t* d_mask, const double* d_u, co
         };
         double* bufs[2] = {d_phi, w1};
         for (int s = 0; s < steps; ++s) {
-            if (rk3) {
-                stage(d_phi, w1, nullptr, 0.0, 1.0, false);
-                stage(w1, w2, d_phi, 0.75, 0.25, false);
-                stage(w2, d_phi, d_phi, 1. / 3., 2. / 3., true); // in place: a lane reads the old phi at its own point only
-            } else {
-                stage(bufs[s & 1], bufs[(s + 1) & 1], nullptr, 0.0, 1.0, true);
-            }
+            if (rk3) rk3_stages(stage, d_phi, w1, w2);
+            else stage(bufs[s & 1], bufs[(s + 1) & 1], nullptr, 0.0, 1.0, true);
             hipLaunchKernelGGL(k_advect_finish, dim3(1), dim3(RED_T), 0, st, (const unsigned long long*)part, (long)nchunks, stop.d_trace, tcap,
                                stop.ctl);
             if (stop.poll(s, steps)) break;

@@ -3,18 +3,10 @@
 // namespace.
 #pragma once
 
-// read-only: cfl = (dt * max over all points (|u| + |v| + |w| + |speed|)) / dx; a non-finite input is LSF_ERR_INVALID with its count
-int advect_field_scan(const double* d_u, const double* d_v, const double* d_w, const double* d_f, int nx, int ny, int nz, double dx, double dt,
-                      double* cfl, hipStream_t st)
+// The partials of k_advect_scan or k_advect_band_scan (nb maxima, then nb counts, enqueued on st) finished in block order:
+// cfl = (dt * max (|u| + |v| + |w| + |speed|)) / dx; a non-finite input is LSF_ERR_INVALID with its count (`where` ends the message)
+int advect_scan_finish(const double* pmax, int nb, double dx, double dt, double* cfl, const char* call, const char* where, hipStream_t st)
 {
-    int rc;
-    Ctx& c = ctx();
-    const long n = (long)(nx + 1) * (ny + 1) * (nz + 1);
-    const int nb = (int)std::min<long>(ADV_SCAN_BLOCKS, (n + 255) / 256);
-    if ((rc = ws(c.slot[S_PART2], (size_t)nb * 16))) return rc;
-    double* pmax = (double*)c.slot[S_PART2].p;
-    unsigned long long* pcnt = (unsigned long long*)(pmax + nb);
-    hipLaunchKernelGGL(k_advect_scan, dim3((unsigned)nb), dim3(256), 0, st, d_u, d_v, d_w, d_f, n, pmax, pcnt);
     HIPCHK(hipGetLastError());
     std::vector<double> h((size_t)2 * nb);
     HIPCHK(hipMemcpyAsync(h.data(), pmax, (size_t)nb * 16, hipMemcpyDeviceToHost, st));
@@ -27,9 +19,51 @@ int advect_field_scan(const double* d_u, const double* d_v, const double* d_w, c
         bad += k;
         m = h[b] > m ? h[b] : m;
     }
-    if (bad) return fail(LSF_ERR_INVALID, "lsf_advect_field: " + std::to_string(bad) + " non-finite value(s) in u, v, w, speed");
+    if (bad) return fail(LSF_ERR_INVALID, std::string(call) + ": " + std::to_string(bad) + " non-finite value(s) in u, v, w, speed" + where);
     if (cfl) *cfl = (dt * m) / dx;
     return LSF_OK;
+}
+
+// read-only: the scan of the inputs over all points
+int advect_field_scan(const double* d_u, const double* d_v, const double* d_w, const double* d_f, int nx, int ny, int nz, double dx, double dt,
+                      double* cfl, hipStream_t st)
+{
+    int rc;
+    Ctx& c = ctx();
+    const long n = (long)(nx + 1) * (ny + 1) * (nz + 1);
+    const int nb = (int)std::min<long>(ADV_SCAN_BLOCKS, (n + 255) / 256);
+    if ((rc = ws(c.slot[S_PART2], (size_t)nb * 16))) return rc;
+    double* pmax = (double*)c.slot[S_PART2].p;
+    hipLaunchKernelGGL(k_advect_scan, dim3((unsigned)nb), dim3(256), 0, st, d_u, d_v, d_w, d_f, n, pmax, (unsigned long long*)(pmax + nb));
+    return advect_scan_finish(pmax, nb, dx, dt, cfl, "lsf_advect_field", "", st);
+}
+
+// (strict, hv, hf) as compile-time constants: calls f(S, HV, HF) with std::true_type / std::false_type objects for the arithmetic and
+// the terms present.  NONE: the instance without velocity and speed exists (the curvature stage); without it such a call takes the
+// speed instance, as the stage launchers always did (the argument checks refuse it before).
+template <bool NONE, class Fn>
+void with_stage_instance(bool strict, bool hv, bool hf, Fn&& f)
+{
+    using Y = std::true_type;
+    using N = std::false_type;
+    auto terms = [&](auto S) {
+        if (hv && hf) f(S, Y{}, Y{});
+        else if (hv) f(S, Y{}, N{});
+        else if (hf || !NONE) f(S, N{}, Y{});
+        else if constexpr (NONE) f(S, N{}, N{});
+    };
+    if (strict) terms(Y{});
+    else terms(N{});
+}
+
+// The three stages of a TVD-RK3 step (Shu and Osher) through stage(A, B, P0, c_old, c_new, last): phi -> w1, then w2 = 3/4 phi +
+// 1/4 t(w1), then phi = 1/3 phi + 2/3 t(w2) in place (a lane reads the old phi at its own point only, before it stores there).
+template <class Stage>
+void rk3_stages(Stage&& stage, double* phi, double* w1, double* w2)
+{
+    stage(phi, w1, nullptr, 0.0, 1.0, false);
+    stage(w1, w2, phi, 0.75, 0.25, false);
+    stage(w2, phi, phi, 1. / 3., 2. / 3., true);
 }
 
 // one stage launch: the instance for the arithmetic and the terms present
@@ -38,19 +72,10 @@ void advect_stage_launch(bool strict, const double* A, double* B, const double* 
                          const int* ctl, int nbx, int nby, int nbz, hipStream_t st)
 {
     const dim3 grid((unsigned)(((long)nbx * nby * nbz + 7) & ~7L)), blk(ADV_BX, ADV_BY);
-#define LSF_ADV_CALL(S, HV, HF) \
-    hipLaunchKernelGGL((k_advect_stage<S, HV, HF>), grid, blk, 0, st, A, B, P0, d_u, d_v, d_w, d_f, nx, ny, nz, dx, dt, c_old, c_new, part, ctl, nbx, nby, nbz)
-    const bool hv = d_u != nullptr, hf = d_f != nullptr;
-    if (strict) {
-        if (hv && hf) LSF_ADV_CALL(true, true, true);
-        else if (hv) LSF_ADV_CALL(true, true, false);
-        else LSF_ADV_CALL(true, false, true);
-    } else {
-        if (hv && hf) LSF_ADV_CALL(false, true, true);
-        else if (hv) LSF_ADV_CALL(false, true, false);
-        else LSF_ADV_CALL(false, false, true);
-    }
-#undef LSF_ADV_CALL
+    with_stage_instance<false>(strict, d_u != nullptr, d_f != nullptr, [&](auto S, auto HV, auto HF) {
+        hipLaunchKernelGGL((k_advect_stage<decltype(S)::value, decltype(HV)::value, decltype(HF)::value>), grid, blk, 0, st, A, B, P0, d_u, d_v, d_w,
+                           d_f, nx, ny, nz, dx, dt, c_old, c_new, part, ctl, nbx, nby, nbz);
+    });
 }
 
 // the steps (arguments validated, inputs scanned, steps >= 1).  Workspace: one field for Euler, two for RK3.
@@ -84,13 +109,8 @@ int advect_field_steps(double* d_phi, const double* d_u, const double* d_v, cons
     };
     double* bufs[2] = {d_phi, w1};
     for (int s = 0; s < steps; ++s) {
-        if (rk3) {
-            stage(d_phi, w1, nullptr, 0.0, 1.0, false);
-            stage(w1, w2, d_phi, 0.75, 0.25, false);
-            stage(w2, d_phi, d_phi, 1. / 3., 2. / 3., true); // in place: a lane reads the old phi at its own point only
-        } else {
-            stage(bufs[s & 1], bufs[(s + 1) & 1], nullptr, 0.0, 1.0, true);
-        }
+        if (rk3) rk3_stages(stage, d_phi, w1, w2);
+        else stage(bufs[s & 1], bufs[(s + 1) & 1], nullptr, 0.0, 1.0, true);
         hipLaunchKernelGGL(k_advect_finish, dim3(1), dim3(RED_T), 0, st, (const unsigned long long*)part, nblk, stop.d_trace, tcap, ctl);
         if (stop.poll(s, steps)) break;
     }

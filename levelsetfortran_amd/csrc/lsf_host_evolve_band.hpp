@@ -12,22 +12,10 @@ void advect_band_curv_stage_launch(bool strict, const double* A, double* B, cons
 {
     const dim3 grid((unsigned)nchunks), blk(MB_CH);
     const double two_dx = 2. * dx, dx2 = dx * dx, four_dx2 = 4. * dx2;
-#define LSF_ADVC_CALL(S, HV, HF)                                                                                                                  \
-    hipLaunchKernelGGL((k_advect_band_curv_stage<S, HV, HF>), grid, blk, 0, st, A, B, P0, d_u, d_v, d_w, d_f, L, nL, nx, ny, nz, dx, dt, c_old, \
-                       c_new, bcurv, two_dx, dx2, four_dx2, lim, part, ctl)
-    const bool hv = d_u != nullptr, hf = d_f != nullptr;
-    if (strict) {
-        if (hv && hf) LSF_ADVC_CALL(true, true, true);
-        else if (hv) LSF_ADVC_CALL(true, true, false);
-        else if (hf) LSF_ADVC_CALL(true, false, true);
-        else LSF_ADVC_CALL(true, false, false);
-    } else {
-        if (hv && hf) LSF_ADVC_CALL(false, true, true);
-        else if (hv) LSF_ADVC_CALL(false, true, false);
-        else if (hf) LSF_ADVC_CALL(false, false, true);
-        else LSF_ADVC_CALL(false, false, false);
-    }
-#undef LSF_ADVC_CALL
+    with_stage_instance<true>(strict, d_u != nullptr, d_f != nullptr, [&](auto S, auto HV, auto HF) {
+        hipLaunchKernelGGL((k_advect_band_curv_stage<decltype(S)::value, decltype(HV)::value, decltype(HF)::value>), grid, blk, 0, st, A, B, P0,
+                           d_u, d_v, d_w, d_f, L, nL, nx, ny, nz, dx, dt, c_old, c_new, bcurv, two_dx, dx2, four_dx2, lim, part, ctl);
+    });
 }
 
 // Every error is found before anything is written: the arguments, then the inputs at all points.  info and margin are written on
@@ -156,9 +144,7 @@ int evolve_band_core(double* d_phi, int32_t* d_mask, const double* d_u, const do
             const dim3 gl((unsigned)nchunks);
             double* cur = d_phi; // the buffer that holds the state
             if (rk3) {
-                stage(d_phi, w1, nullptr, 0.0, 1.0, false);
-                stage(w1, w2, d_phi, 0.75, 0.25, false);
-                stage(w2, d_phi, d_phi, 1. / 3., 2. / 3., true); // in place: a lane reads the old phi at its own point only
+                rk3_stages(stage, d_phi, w1, w2);
             } else {
                 stage(d_phi, w1, nullptr, 0.0, 1.0, true);
                 cur = w1;

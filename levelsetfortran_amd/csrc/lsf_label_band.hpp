@@ -84,7 +84,7 @@ __global__ __launch_bounds__(MB_CH) void k_label_check(const double* __restrict_
         v[1] = !bad && d < 0.0 ? 1ull : 0ull;
         v[2] = !bad && !(d < 0.0) ? 1ull : 0ull;
     }
-    extb_block_sum<LB_NCHECK>(v, part + (size_t)blockIdx.x * LB_NCHECK);
+    block_usum_out<MB_CH / 64>(v, threadIdx.x, part + (size_t)blockIdx.x * LB_NCHECK);
 }
 
 __global__ __launch_bounds__(MB_CH) void k_label_init(const double* __restrict__ phi, const int* __restrict__ L, int nL, double iso, int side,
@@ -125,16 +125,8 @@ __global__ __launch_bounds__(MB_CH) void k_label_link(const double* __restrict__
             }
         }
     }
-    __shared__ unsigned red[MB_CH / 64];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) found += __shfl_xor(found, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = found;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = red[0];
-        for (int w = 1; w < MB_CH / 64; ++w) t += red[w];
-        if (t) atomicAdd(cnt + pass, (unsigned long long)t);
-    }
+    found = block_usum<MB_CH / 64>(found, threadIdx.x);
+    if (threadIdx.x == 0 && found) atomicAdd(cnt + pass, (unsigned long long)found);
 }
 
 // ... second half: every labelled cell's word becomes its root
@@ -163,7 +155,7 @@ __global__ __launch_bounds__(MB_CH) void k_label_roots(const double* __restrict_
             v[1] = inside ? 0ull : 1ull;
         }
     }
-    extb_block_sum<LB_NROOTS>(v, part + (size_t)blockIdx.x * LB_NROOTS);
+    block_usum_out<MB_CH / 64>(v, threadIdx.x, part + (size_t)blockIdx.x * LB_NROOTS);
 }
 
 // roots[0 .. *head): the roots in any order; one returning atomic add per block that holds a root

@@ -20,10 +20,9 @@
 // block order.  Counts are integers.  Plain launches, no floating-point atomic, no block waits for another: the totals are a
 // function of field, mask and list order alone.
 //
-// Bounds.  The argument of lsf_advect_band.hpp, restated: a list entry is an interior point (k_mb_collect<true> keeps 1..n-1 on each
-// axis only, and the host refuses fields beyond 2^31 - 1 points), so i + 1 <= nx, j + 1 <= ny, k + 1 <= nz: the eight corners
-// p + {0,1} + {0,1}*row + {0,1}*plane exist, and so do the six face neighbours p +- 1, +- row, +- plane whose mask the OPEN test
-// reads.  The one store is at the lane's own point.  Lanes with e >= nL touch no memory.
+// Bounds: lsf_band_cell.hpp.  What is this file's own: a list entry is an interior point, so i + 1 <= nx, j + 1 <= ny, k + 1 <= nz
+// and the eight corners p + {0,1} + {0,1}*row + {0,1}*plane exist; the OPEN test is band_listed6.  The one store is at the lane's
+// own point.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -140,8 +139,8 @@ __global__ __launch_bounds__(MB_CH) void k_measure_check(const double* __restric
                 }
         }
     }
-    badf = xs_wave_sum(badf);
-    badq = xs_wave_sum(badq);
+    badf = wave_usum(badf);
+    badq = wave_usum(badq);
     if ((threadIdx.x & 63) == 0) {
         if (badf) atomicAdd(&ctl[MS_BAD_F], badf);
         if (badq) atomicAdd(&ctl[MS_BAD_Q], badq);
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(MB_CH) void k_measure_band(const double* __restrict
         ms_corners(c, rs, ps, iso, byte, nonf);
         if (byte != 0u && byte != 255u) {
             int i, j, k;
-            advb_decode(p, nx, ny, i, j, k);
+            band_decode(p, nx, ny, i, j, k);
             const double* cq = HASQ ? q + p : nullptr;
             unsigned tris = 0u, deg = 0u;
             xs_cell_emit(
@@ -182,23 +181,17 @@ __global__ __launch_bounds__(MB_CH) void k_measure_band(const double* __restrict
                     ms_triangle<HASQ>(A, B, C, acc, deg);
                     ++tris;
                 });
-            // OPEN: a face-neighbour cell whose lower corner is not in LIST (the test of k_advect_band_edge)
-            const int32_t* m = mask + p;
-            const bool in = (i > 1 && m[-1] == 1) && (i < nx - 1 && m[1] == 1) && (j > 1 && m[-rs] == 1) && (j < ny - 1 && m[rs] == 1) &&
-                            (k > 1 && m[-ps] == 1) && (k < nz - 1 && m[ps] == 1);
+            // OPEN: a face-neighbour cell whose lower corner is not in LIST
+            const bool in = band_listed6(mask + p, i, j, k, nx, ny, nz, rs, ps);
             ncross = 1ull, ntri = tris, nopen = in ? 0ull : 1ull, ndeg = deg;
         }
         if constexpr (HASCELL) cell_area[p] = acc[0];
     }
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
+    for (int o = 32; o >= 1; o >>= 1)
 #pragma unroll
         for (int m = 0; m < (HASQ ? MS_NQ : MS_NQ - 1); ++m) acc[m] = acc[m] + __shfl_xor(acc[m], o, 64);
-        ncross += __shfl_xor(ncross, o, 64);
-        ntri += __shfl_xor(ntri, o, 64);
-        nopen += __shfl_xor(nopen, o, 64);
-        ndeg += __shfl_xor(ndeg, o, 64);
-    }
+    wave_usum_each(ncross, ntri, nopen, ndeg); // (lsf_block_reduce.hpp; the block level shares the barrier of the sums)
     if ((threadIdx.x & 63) == 0) {
         const int w = threadIdx.x >> 6;
 #pragma unroll

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lsf_band_cell.hpp"
 #include "lsf_minmax_band.hpp"
 
 namespace lsf {
@@ -43,8 +44,7 @@ static __global__ __launch_bounds__(256) void k_rb_scatter(const int* __restrict
 }
 
 // One sweep: list cell e of chunk blockIdx.x.  A = the field at the start of the sweep, Bout = the other field buffer, phiS = the
-// compact sign field.  A list cell is an interior point (1..n-1): the first-order branch reads +-1, the WENO branch (cells 4..n-5)
-// +-3 -- nothing outside the field.  Point indices fit 32 bits (the host refuses larger fields).
+// compact sign field.  Bounds: lsf_band_cell.hpp (band_stencil7 forms every address that is not the lane's own).
 template <bool STRICT>
 __global__ __launch_bounds__(MB_CH) void k_reinit_band(const double* __restrict__ A, double* __restrict__ Bout, const double* __restrict__ phiS,
                                                        const int* __restrict__ L, int nL, int nx, int ny, int nz, double dx, double h,
@@ -55,28 +55,15 @@ __global__ __launch_bounds__(MB_CH) void k_reinit_band(const double* __restrict_
     const int e = blockIdx.x * MB_CH + threadIdx.x;
     double acc = 0.0;
     if (e < nL) {
-        const unsigned p = (unsigned)L[e], sx = (unsigned)(nx + 1), sy = (unsigned)(ny + 1);
-        const unsigned q = p / sx;
-        const int i = (int)(p - q * sx), k = (int)(q / sy), j = (int)(q - (unsigned)k * sy);
+        const unsigned p = (unsigned)L[e];
+        int i, j, k;
+        band_decode(p, nx, ny, i, j, k);
         const bool weno_ok = i > 3 && i < nx - 4 && j > 3 && j < ny - 4 && k > 3 && k < nz - 4;
-        const long rs = sx, ps = (long)sx * sy;
         const double* c = A + p;
-        double qx[7], qy[7], qz[7];
         const double phic = c[0];
-        if (weno_ok) {
-#pragma unroll
-            for (int m = 0; m < 7; ++m) {
-                qx[m] = m == 3 ? phic : c[m - 3];
-                qy[m] = m == 3 ? phic : c[(m - 3) * rs];
-                qz[m] = m == 3 ? phic : c[(m - 3) * ps];
-            }
-        } else {
-#pragma unroll
-            for (int m = 0; m < 7; ++m) qx[m] = qy[m] = qz[m] = 0.0;
-            qx[2] = c[-1], qx[3] = phic, qx[4] = c[1];
-            qy[2] = c[-rs], qy[3] = phic, qy[4] = c[rs];
-            qz[2] = c[-ps], qz[3] = phic, qz[4] = c[ps];
-        }
+        double qx[7], qy[7], qz[7];
+        const unsigned sx = (unsigned)(nx + 1), sy = (unsigned)(ny + 1);
+        band_stencil7(c, sx, (long)sx * sy, weno_ok, qx, qy, qz);
         const double inv_dx = 1.0 / dx, floor2 = 1.E-99 * dx * dx / 13.0;
         const double newv = cell_update<STRICT>(qx, qy, qz, weno_ok, phiS[e], dx, inv_dx, floor2, h);
         Bout[p] = newv;

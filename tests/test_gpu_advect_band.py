@@ -8,7 +8,8 @@ Grids and masks, the smallest on which each piece can go wrong (a chunk is 256 l
   general   (40,33,27), |phi| < 4.1 dx: about 6 000 cells, 25 chunks, the last ragged; x not a multiple of anything
   interior  (25,25,25), every interior point: the edge cells are the wall-adjacent ones
   onecell   a list of one cell (the WENO cell of (10,10,10))
-  values    (12,11,10): a mask carrying 0, 7, -1 and 1s on wall points"""
+  values    (12,11,10): a mask carrying 0, 7, -1 and 1s on wall points
+  big       (73,73,73), every interior point, steps = 0: 357 911 cells, more than one entry per thread of the scan and the closing pass"""
 import ctypes
 import functools
 import math
@@ -339,3 +340,65 @@ def test_zero_steps_empty_list_and_a_nan(lsf, seam):
     rep = e.value.report
     assert rep.steps == 1 and len(rep.change) == 1 and math.isnan(rep.change[0]) and rep.cfl == want.cfl
     assert (rep.cells, rep.edge_cells, rep.edge_flips, rep.margin) == (None, None, None, None)  # reported on LSF_OK only
+
+
+# ---------------------------------------------------------------------------------- 7: a list longer than one entry per thread
+# The scan and the closing pass run at most 1024 blocks of 256 threads (ADV_SCAN_BLOCKS in csrc/lsf_advect_field.hpp): beyond
+# 262 144 list cells a thread takes a second entry.  72^3 cells, every interior point in the list: 71^3 = 357 911 entries.
+# steps = 0 still runs the scan, the edge pass and the closing pass; what they report is computed here directly.
+BIG = (73, 73, 73)
+BIG_SPOTS = {"first": ((1, 1, 1), (1, 1, 1)), "middle": ((36, 36, 36), (1, 36, 36)), "last": ((71, 71, 71), (71, 71, 71))}
+
+
+@functools.lru_cache(maxsize=None)
+def _big():
+    """(phi, u, v, w, f, interior, edge): |phi| in [1, 2), the inputs in [-1, 1); edge = the wall-adjacent interior points, the only
+    list cells with a neighbour outside the list when every interior point is in it"""
+    rng = np.random.default_rng(72)
+    phi = np.asfortranarray((1.0 + rng.random(BIG)) * np.where(rng.random(BIG) < 0.5, -1.0, 1.0))
+    u, v, w, f = (np.asfortranarray(rng.uniform(-1.0, 1.0, BIG)) for _ in range(4))
+    interior = np.zeros(BIG, bool)
+    interior[1:-1, 1:-1, 1:-1] = True
+    edge = interior.copy()
+    edge[2:-2, 2:-2, 2:-2] = False
+    for a in (phi, u, v, w, f, interior, edge):
+        a.setflags(write=False)
+    return phi, u, v, w, f, interior, edge
+
+
+@pytest.mark.parametrize("spot", list(BIG_SPOTS))
+def test_a_list_longer_than_one_entry_per_thread(lsf, spot):
+    phi0, u0, v0, w0, f0, interior, edge = _big()
+    assert interior.sum() == 357911 > 1024 * 256 and edge.sum() == 71 ** 3 - 69 ** 3
+    at_max, at_min = BIG_SPOTS[spot]
+    assert interior[at_max] and edge[at_min]
+    phi, u, v, w, f = (a.copy(order="F") for a in (phi0, u0, v0, w0, f0))
+    u[at_max], v[at_max], w[at_max], f[at_max] = 2.0, -3.0, 1.5, -2.5  # |u| + |v| + |w| + |speed| = 9 there, below 4 elsewhere
+    phi[at_min] = -0.125  # the smallest |phi| of an edge cell
+    phi[36, 35, 36] = 0.0625  # a smaller one at a cell that is no edge cell
+    dx, dt = 1.0 / 72, 0.25 / 72
+    s = (np.abs(u) + np.abs(v)) + np.abs(w)
+    s = s + np.abs(f)
+    want_cfl = (dt * s[interior].max()) / dx
+    assert s[interior].max() == 9.0 == s[at_max] and np.abs(phi[edge]).min() == 0.125
+    mask = np.ones(BIG, np.int32, order="F")
+    got, rep = _run(lsf, "device", phi, mask, (u, v, w), f, (72, 72, 72), dx, dt, 0)
+    print(f"{spot}: cfl {rep.cfl!r} (want {want_cfl!r}), cells {rep.cells}, edge {rep.edge_cells}, flips {rep.edge_flips}, margin {rep.margin!r}")
+    assert np.array_equal(got, phi)
+    assert rep.steps == 0 and rep.change == [] and rep.cfl == want_cfl
+    assert (rep.cells, rep.edge_cells, rep.edge_flips) == (357911, int(edge.sum()), 0)
+    assert rep.margin == 0.125
+
+
+def test_a_long_list_counts_its_non_finite_inputs(lsf):
+    from levelsetfortran_amd import _lib
+
+    phi0, u0, v0, w0, f0, interior, _ = _big()
+    u = u0.copy(order="F")
+    for at, _ in BIG_SPOTS.values():
+        u[at] = np.nan
+    u[0, 5, 5] = np.nan  # a wall point: not a list cell, legal
+    mask = np.ones(BIG, np.int32, order="F")
+    with pytest.raises(lsf.LsfError) as e:
+        _run(lsf, "device", phi0, mask, (u, v0, w0), f0, (72, 72, 72), 1.0 / 72, 0.25 / 72, 0)
+    assert e.value.code == _lib.LSF_ERR_INVALID and "3 non-finite" in str(e.value), str(e.value)

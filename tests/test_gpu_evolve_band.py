@@ -12,6 +12,7 @@ it at the given CFL number (a chunk is 256 list entries, MB_CH in csrc/lsf_minma
   grow      (24,22,20), speed 1, core 2, ring 3, 2 sweeps, 8 steps: the list goes 1 626 -> 5 616, every workspace slot grows mid-call
   euler     (24,22,20), u = (1,.3,0), Euler, CFL 0.3, core 2, ring 3, 2 sweeps, 9 steps: no rebuild, an odd step count
   thinflip  20^3, u = (1,0,0), the mask |phi| < 0.6 dx, core .25, ring 1, no sweeps: ends after the first step with 44 flips
+  big       (section 7, its own fields) 73^3 points, every interior point, steps = 0: more than one entry per thread of scan and check
 The properties are asserted on the statement first (test_the_cases_show_their_properties): a case that stops exercising its path
 fails loudly."""
 import ctypes
@@ -363,3 +364,95 @@ def test_fast_takes_the_same_schedule_within_tolerance_of_strict(lsf):
     assert np.array_equal(m, want.mask) and rep.rebuilds == want.rebuilds and rep.steps == 16 and rep.cfl == want.cfl
     assert (rep.cells, rep.open_cells, rep.entered, rep.flips) == (want.cells, want.open_cells, want.entered, want.flips)
     assert rms <= FAST_RMS_TOL
+
+
+# ---------------------------------------------------------------------------------- 7: a list longer than one entry per thread
+# The scan of the inputs and the check run at most 1024 blocks of 256 threads (ADV_SCAN_BLOCKS, EVB_CHECK_BLOCKS): beyond 262 144
+# entries a thread takes a second one.  72^3 cells, every interior point in the list: 71^3 = 357 911 list cells, 73^3 scanned
+# points.  steps = 0 still runs the scan, the first list, the edge pass and the check; what they report is computed here directly:
+# the CFL number over ALL points, no open-edge cell (every interior neighbour of a list cell is in the list, so the margin is +inf)
+# and the wall-adjacent cells with |phi| < core dx.
+BIG = (73, 73, 73)
+BIG_SPOTS = {"first": (1, 1, 1), "middle": (36, 36, 36), "last": (71, 71, 71)}
+BIG_KW = dict(core=3.0, ring=3, reinit_sweeps=2)
+
+
+@functools.lru_cache(maxsize=None)
+def _big():
+    """(phi, u, v, w, f, interior, near): |phi| in [0, 0.1) -- core dx = 3 / 72 lies inside --, the inputs in [-1, 1); near = the
+    wall-adjacent interior points"""
+    rng = np.random.default_rng(73)
+    phi = np.asfortranarray(0.1 * rng.random(BIG) * np.where(rng.random(BIG) < 0.5, -1.0, 1.0))
+    u, v, w, f = (np.asfortranarray(rng.uniform(-1.0, 1.0, BIG)) for _ in range(4))
+    interior = np.zeros(BIG, bool)
+    interior[1:-1, 1:-1, 1:-1] = True
+    near = interior.copy()
+    near[2:-2, 2:-2, 2:-2] = False
+    for a in (phi, u, v, w, f, interior, near):
+        a.setflags(write=False)
+    return phi, u, v, w, f, interior, near
+
+
+@pytest.mark.parametrize("spot", list(BIG_SPOTS))
+def test_a_list_longer_than_one_entry_per_thread(lsf, spot):
+    phi0, u0, v0, w0, f0, interior, near = _big()
+    assert interior.sum() == 357911 > 1024 * 256
+    at = BIG_SPOTS[spot]
+    u, v, w, f = (a.copy(order="F") for a in (u0, v0, w0, f0))
+    u[at], v[at], w[at], f[at] = 2.0, -3.0, 1.5, -2.5  # |u| + |v| + |w| + |speed| = 9 there, below 4 elsewhere
+    dx, dt = 1.0 / 72, 0.25 / 72
+    s = (np.abs(u) + np.abs(v)) + np.abs(w)
+    s = s + np.abs(f)
+    assert s.max() == 9.0 == s[at]
+    want_cfl = (dt * s.max()) / dx
+    want_near = int((near & (np.abs(phi0) < 3.0 * dx)).sum())
+    assert 0 < want_near < near.sum()
+    mask = np.ones(BIG, np.int32, order="F")
+    got, m, rep = _run(lsf, "device", phi0, mask, (u, v, w), f, (72, 72, 72), dx, dt, 0, **BIG_KW)
+    print(f"{spot}: {rep}, want cfl {want_cfl!r}, near_wall {want_near}")
+    assert np.array_equal(got, phi0) and np.array_equal(m, interior.astype(np.int32))
+    assert rep.steps == 0 and rep.change == [] and rep.cfl == want_cfl
+    assert (rep.cells, rep.open_cells, rep.flips, rep.rebuilds, rep.entered, rep.near_wall) == (357911, 0, 0, 0, 0, want_near)
+    assert rep.margin == math.inf
+
+
+def test_a_long_list_with_open_edge_cells_behind_the_first_entry_per_thread(lsf):
+    """The mask of all ones has no open-edge cell.  One interior cell left out, (68,68,68), opens its six neighbours: the list is
+    sorted by bricks of 8 x 8 x 4 points, layer k >> 2 first, and all six have k >= 67, behind the 63 * 71 * 71 = 317 583 cells with
+    k <= 63 -- second entries of their threads -- so the minimum and the open and flip counts of the check come from there."""
+    phi0, u0, v0, w0, f0, interior, near = _big()
+    hole = (68, 68, 68)
+    opened = [(67, 68, 68), (69, 68, 68), (68, 67, 68), (68, 69, 68), (68, 68, 67), (68, 68, 69)]
+    assert 63 * 71 * 71 > 1024 * 256 and min(c[2] for c in opened) >> 2 >= 16
+    phi = phi0.copy(order="F")
+    for q, c in enumerate(opened):
+        phi[c] = (-1.0) ** q * (0.01 + 0.001 * q)  # the smallest |phi| of an open-edge cell is 0.01; both signs: no flip at steps = 0
+    phi[hole] = 0.0009765625  # smaller, but not a list cell
+    mask = np.ones(BIG, np.int32, order="F")
+    mask[hole] = 0
+    dx, dt = 1.0 / 72, 0.25 / 72
+    s = (np.abs(u0) + np.abs(v0)) + np.abs(w0)
+    s = s + np.abs(f0)
+    want_near = int((near & (np.abs(phi) < 3.0 * dx)).sum())
+    got, m, rep = _run(lsf, "device", phi, mask, (u0, v0, w0), f0, (72, 72, 72), dx, dt, 0, **BIG_KW)
+    print(f"hole: {rep}, want near_wall {want_near}")
+    want_mask = interior.astype(np.int32)
+    want_mask[hole] = 0
+    assert np.array_equal(got, phi) and np.array_equal(m, want_mask)
+    assert rep.steps == 0 and rep.cfl == (dt * s.max()) / dx
+    assert (rep.cells, rep.open_cells, rep.flips, rep.rebuilds, rep.entered, rep.near_wall) == (357910, 6, 0, 0, 0, want_near)
+    assert rep.margin == 0.01
+
+
+def test_a_long_list_counts_its_non_finite_inputs(lsf):
+    from levelsetfortran_amd import _lib
+
+    phi0, u0, v0, w0, f0, _, _ = _big()
+    u = u0.copy(order="F")
+    for at in BIG_SPOTS.values():
+        u[at] = np.nan
+    phi, mask = _dev(phi0), _dev(np.ones(BIG, np.int32, order="F"))
+    with pytest.raises(lsf.LsfError) as e:
+        lsf.evolveBand(phi, mask, 72, 72, 72, 1.0 / 72, 0.25 / 72, 0, velocity=tuple(_dev(a) for a in (u, v0, w0)), speed=_dev(f0), **BIG_KW)
+    assert e.value.code == _lib.LSF_ERR_INVALID and "3 non-finite" in str(e.value), str(e.value)
+    assert np.array_equal(_host(phi, BIG), phi0) and np.all(_host(mask, BIG) == 1)  # refused before anything is written
