@@ -1069,6 +1069,119 @@ int lsf_cast_rays_device(const double *d_phi, const int32_t *d_mask, const doubl
                          double *d_thit, double *d_hit, double *d_grad, double *d_qval, int32_t *d_status,
                          int64_t info[LSF_CAST_INFO_LEN], void *stream);
 
+/* ---- points carried through the fields that move phi ----------
+ * No reference counterpart (lsf_advect_nodes is the reference's own surface-node scheme and stays as it is).  Tracers, the nodes of
+ * lsf_extract_surface, the markers of a particle level set, or points traced backwards with dt < 0 move along
+ *     x' = (u, v, w)(x) + speed(x) * grad phi(x) / |grad phi(x)|
+ * in fields that are frozen for the call: the law under which lsf_advect_field and lsf_evolve_band move phi.  One lane per point, in
+ * the caller's order, the interpolant of lsf_sample_points unchanged.  u, v, w come together or all NULL; speed is optional; phi is
+ * required exactly when speed is given (phi without speed is refused); at least one of the two groups is present.  mask, status,
+ * cfl and info may be NULL.  xLo, cfl and info are host memory on both seams.  Every field is an input only.
+ *   arrays   pts is REAL a(npts,3) in Fortran order, in and out; status has npts entries.  The fields have (nx+1)(ny+1)(nz+1) points.
+ *   exact    every expression below is evaluated left to right as written, without contraction, with the IEEE / and sqrt: the numpy
+ *            transcription tests/points_ref.py is the yardstick bit for bit.
+ *   sample   K(y): the rules locate, stencil (the joint cubic rule with its linear fallback), band, weights and value of
+ *            lsf_sample_points apply word for word, to every field under one set of weights; the sample is OK, OUTSIDE or OFFBAND.
+ *            U_A is the value of u, v, w.  With speed: f the value of speed, g the grad of phi (its division by dx included),
+ *            m = (g0*g0 + g1*g1) + g2*g2; m == 0: the sample is FLAT; nrm = sqrt(m); k_A = U_A + (f*g_A)/nrm, or k_A = (f*g_A)/nrm
+ *            without the velocity group.  Without speed k_A = U_A.
+ *   step     LSF_ADVECT_RK3 from x0:  k = K(x0); x1_A = x0_A + dt*k_A
+ *                                     k = K(x1); x2_A = 0.75*x0_A + 0.25*(x1_A + dt*k_A)
+ *                                     k = K(x2); xn_A = (1./3.)*x0_A + (2./3.)*(x2_A + dt*k_A)
+ *            LSF_ADVECT_EULER: xn = x1.  A step COMPLETES when each of its samples was OK and xn is INSIDE on all three axes by
+ *            locate.  Otherwise the point keeps the bits of x0, takes the status of what failed -- the first failed sample's
+ *            OUTSIDE, OFFBAND or FLAT (later stages are not sampled); OUTSIDE for a wild xn, NaN included -- and stops.
+ *   status   a point that completes nsteps steps is LSF_POINTS_OK.  A point that is not INSIDE on entry (NaN, +-inf, 1e300) is
+ *            returned bit for bit with LSF_POINTS_OUTSIDE.  Every other returned point lies in the grid.  A non-finite field VALUE
+ *            is not an error: it makes a position non-finite, and that position fails locate before any index exists.
+ *   cfl      the largest fabs(dt*k_A)/dx over the stages and axes of completed steps, 0.0 if there is none; a maximum of bit
+ *            patterns, so no order of reduction enters it.
+ *   info     [0] points with status OK; [1] OUTSIDE; [2] OFFBAND; [3] FLAT -- they add up to npts; [4] completed steps summed over
+ *            the points; [5] samples with status OK that served a cubic request linearly (every OK sample taken counts, those of a
+ *            step that fails later included).  Written on LSF_OK only.
+ *   errors   LSF_ERR_INVALID, all detected before anything is written: a NULL pts or xLo; a partial u, v, w; no group at all; speed
+ *            and phi not given together; npts < 1; nx, ny or nz < 1 or more than 2^31 - 1 points; dx, xLo or dt not finite,
+ *            dx <= 0; an unknown order or scheme; nsteps outside 1..LSF_ADVECT_POINTS_MAX_STEPS (the cap keeps a launch bounded: a
+ *            caller loops for more); pts or status sharing a byte with each other or with an input.
+ *            No device: LSF_ERR_NO_DEVICE with nothing written -- there is no CPU fallback, no mode word, one arithmetic.
+ *   seams    u, v, w and speed are staged as lsf_advect_field stages them, phi goes through its twin as in lsf_sample_points, the
+ *            mask as lsf_curvature_band takes it; pts is copied in on every call and comes home with status on LSF_OK only.
+ *            lsf_advect_points_device returns after the stream is synchronised (the host finishes the block partials).
+ * Accuracy: third order in dt for RK3 on smooth fields; a constant velocity is an exact translation to rounding, a rigid rotation
+ * conserves the radius to third order (tests/test_points_cpu.py).  Work: one launch; per stage 8 or 64 gathered loads per field read
+ * (the mask as many).  Workspace: 56 bytes per 256 points; the host seam adds up to four fields and 28 bytes per point.  Out of
+ * scope: a velocity that changes inside a call, points sorted by brick, fp32, multi-GPU.
+ * Kernel: 12 instances (order x velocity / speed / both x mask), 78 - 245 VGPRs, none with scratch.
+ * Timed once on one MI355X on the markers of seedParticles(per_cell=16) around a sphere, in cell order, with the mask
+ * |phi| < 8.1 dx (profiles/points_time.txt, from profiles/micro/points_time.py; device seam, ms per call, one RK3 step): at 256^3
+ * (1 562 810 markers) linear 0.186 / with the mask 0.187, cubic 0.477 / 0.591, cubic with both groups and the mask 0.821, beside
+ * lsf_sample_points cubic 0.134 on the same points and one step of lsf_advect_field_band 0.534 on the same mask; at 512^3
+ * (6 269 922 markers) 0.504 / 0.481, 1.566 / 2.197, 2.933, beside 0.289 and 1.579.  No speed is claimed beyond that record. */
+#define LSF_ADVECT_POINTS_INFO_LEN 6
+#define LSF_ADVECT_POINTS_MAX_STEPS 4096
+#define LSF_POINTS_OK 0 /* status[t] */
+#define LSF_POINTS_OUTSIDE 1
+#define LSF_POINTS_OFFBAND 2
+#define LSF_POINTS_FLAT 3
+int lsf_advect_points(const double *u, const double *v, const double *w, const double *phi, const double *speed, const int32_t *mask,
+                      int nx, int ny, int nz, double dx, const double xLo[3], double *pts, int npts, int order, int scheme, double dt,
+                      int nsteps, int32_t *status, double *cfl, int64_t info[LSF_ADVECT_POINTS_INFO_LEN]);
+int lsf_advect_points_device(const double *d_u, const double *d_v, const double *d_w, const double *d_phi, const double *d_speed,
+                             const int32_t *d_mask, int nx, int ny, int nz, double dx, const double xLo[3], double *d_pts, int npts,
+                             int order, int scheme, double dt, int nsteps, int32_t *d_status, double *cfl,
+                             int64_t info[LSF_ADVECT_POINTS_INFO_LEN], void *stream);
+
+/* ---- the scatter from marker particles back to the grid: the correction of the particle level set ----------
+ * No reference counterpart.  Enright, Fedkiw, Ferziger and Mitchell (2002): markers with a side and a radius ride the velocity
+ * (lsf_advect_points); where one ends up on the wrong side of the surface by more than its radius, the grid values around it are
+ * rebuilt from its sphere.  rad[t] carries the side in its sign (> 0: the marker belongs where phi > 0) and the radius in
+ * r = fabs(rad); s = rad > 0 ? 1. : -1.  phi is in and out; mask, status, change and info may be NULL.  xLo, change and info are
+ * host memory on both seams.
+ *   arrays   pts is REAL a(npts,3) in Fortran order; rad and status have npts entries; phi and mask are fields.
+ *   exact    as above: tests/points_ref.py is the yardstick bit for bit.  One arithmetic, no mode word.
+ *   particle in this precedence: rad not finite or == 0: LSF_CORRECT_BADRADIUS.  Not INSIDE by locate of lsf_sample_points:
+ *            OUTSIDE.  With a mask, any of the 8 corners of its cell not IN (the LIST rule: interior and mask == 1): OFFBAND.
+ *            Otherwise val is the LINEAR value of phi at the point, read from the field as it was on entry (0*NaN and 0*inf are
+ *            NaN, so val is non-finite whenever a corner is); a non-finite val: NONFINITE.  ESCAPED iff s*val < -(slack*r)
+ *            (slack = 1 is Enright's rule, slack = 0 any marker on the wrong side).  Otherwise INPLACE.
+ *   scatter  per ESCAPED particle at each corner i0 + o of its cell: xc_A = xLo[A] + (double)(i0_A + o_A)*dx; e_A = xc_A - x_A;
+ *            d = sqrt((e0*e0 + e1*e1) + e2*e2); cand = s*(r - d); for s > 0 plus = max(plus, cand), otherwise
+ *            minus = min(minus, cand).  plus and minus both start as phi.  max and min are taken in the total order of the bit
+ *            patterns, in which -0.0 < +0.0: the result is a function of the SET of particles, not of their order.
+ *   merge    at every point (every list point under a mask): phi = fabs(plus) <= fabs(minus) ? plus : minus.  A point no
+ *            candidate reached keeps its bits.  Without a mask wall points are corrected like any other.
+ *   change   the largest fabs(new - old) over the points whose bits changed, 0.0 if none; a maximum of bit patterns.
+ *   info     [0] INPLACE; [1] ESCAPED; [2] OUTSIDE; [3] OFFBAND; [4] NONFINITE; [5] BADRADIUS -- they add up to npts; [6] points
+ *            whose bits changed.  Written on LSF_OK only.
+ *   errors   LSF_ERR_INVALID, all detected before anything is written: a NULL phi, pts, rad or xLo; npts < 1; nx, ny or nz < 1 or
+ *            more than 2^31 - 1 points; dx or xLo not finite, dx <= 0; slack not finite or < 0; status sharing a byte with
+ *            anything; phi sharing a byte with pts, rad or the mask.  No device: LSF_ERR_NO_DEVICE with nothing written.
+ *   seams    phi is in and out through its twin, as lsf_reinit_band takes its field, and comes home on LSF_OK only; the mask as
+ *            lsf_curvature_band takes it; pts and rad are staged per call.  lsf_correct_field_device returns after the stream is
+ *            synchronised.
+ * Work: three launches (keys over the list or the grid, one lane per particle with at most 8 integer atomics each, the merge).
+ * Workspace: two fields of 64-bit keys, the list under a mask, 48 bytes per 256 particles; the host seam adds 36 bytes per
+ * particle.  Out of scope: reseeding and deletion on the device, attraction of new markers to a target level, the radius refresh
+ * (rad = s*clip(s*val, rmin, rmax) from lsf_sample_points is the caller's one line), iso != 0, fp32, multi-GPU (DESIGN.md
+ * section 8).
+ * The statement on LeVeque's vortex at 33^3 points (64 steps out, 64 back, no reinitialisation): the volume
+ * falls from 0.013833 to 0.010747 (-22.3 %) without markers and to 0.012081 (-12.7 %) with 21 347 of them, the mean |phi - phi0|
+ * near the surface is 0.336 against 0.191 dx; 2 385 escapes were used.
+ * Timed once on the same markers as lsf_advect_points, phi shifted by 0.3 dx so that 1.2 % of them escape (profiles/points_time.txt;
+ * ms per call): at 256^3 0.411 without a mask and 0.265 with it, at 512^3 1.956 and 0.656.  No speed is claimed beyond that record. */
+#define LSF_CORRECT_INFO_LEN 7
+#define LSF_CORRECT_INPLACE 0 /* status[t] */
+#define LSF_CORRECT_ESCAPED 1
+#define LSF_CORRECT_OUTSIDE 2
+#define LSF_CORRECT_OFFBAND 3
+#define LSF_CORRECT_NONFINITE 4
+#define LSF_CORRECT_BADRADIUS 5
+int lsf_correct_field(double *phi, const int32_t *mask, int nx, int ny, int nz, double dx, const double xLo[3], const double *pts,
+                      const double *rad, int npts, double slack, int32_t *status, double *change, int64_t info[LSF_CORRECT_INFO_LEN]);
+int lsf_correct_field_device(double *d_phi, const int32_t *d_mask, int nx, int ny, int nz, double dx, const double xLo[3],
+                             const double *d_pts, const double *d_rad, int npts, double slack, int32_t *d_status, double *change,
+                             int64_t info[LSF_CORRECT_INFO_LEN], void *stream);
+
 /* ---- connected components of the level set on the cells of a caller's mask ----------
  * No reference counterpart.  How many bodies there are, which cell belongs to which, and whether two have merged or one has pinched
  * off: the 6-connected components of the list cells on either side of phi = iso, a pure graph problem on the cell list every band

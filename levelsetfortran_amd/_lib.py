@@ -31,6 +31,10 @@ LSF_SAMPLE_LINEAR, LSF_SAMPLE_CUBIC, LSF_SAMPLE_INFO_LEN = 0, 1, 6  # include/ls
 LSF_SAMPLE_OK, LSF_SAMPLE_OUTSIDE, LSF_SAMPLE_OFFBAND, LSF_SAMPLE_FLAT, LSF_SAMPLE_NOT_CONVERGED = 0, 1, 2, 3, 4  # ... its status[t]
 LSF_CAST_INFO_LEN = 9  # include/lsf.h: lsf_cast_rays
 LSF_CAST_HIT, LSF_CAST_MISS, LSF_CAST_NOGRID, LSF_CAST_BAD, LSF_CAST_LOST, LSF_CAST_STEPS = 0, 1, 2, 3, 4, 5  # ... its status[r]
+LSF_ADVECT_POINTS_INFO_LEN, LSF_ADVECT_POINTS_MAX_STEPS = 6, 4096  # include/lsf.h: lsf_advect_points
+LSF_POINTS_OK, LSF_POINTS_OUTSIDE, LSF_POINTS_OFFBAND, LSF_POINTS_FLAT = 0, 1, 2, 3  # ... its status[t]
+LSF_CORRECT_INFO_LEN = 7  # include/lsf.h: lsf_correct_field
+LSF_CORRECT_INPLACE, LSF_CORRECT_ESCAPED, LSF_CORRECT_OUTSIDE, LSF_CORRECT_OFFBAND, LSF_CORRECT_NONFINITE, LSF_CORRECT_BADRADIUS = 0, 1, 2, 3, 4, 5
 LSF_LABEL_INSIDE, LSF_LABEL_OUTSIDE, LSF_LABEL_BOTH = 0, 1, 2  # include/lsf.h: lsf_label_band
 LSF_LABEL_COMP_LEN, LSF_LABEL_INFO_LEN = 10, 8
 LSF_EXTEND_INFO_LEN = 3  # include/lsf.h: lsf_extend_field
@@ -130,6 +134,14 @@ SIGNATURES = {
     "lsf_cast_rays_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                      c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsf_advect_points": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int,
+                                  c_int, c_int, c_double, c_int, c_void_p, POINTER(c_double), c_void_p]),
+    "lsf_advect_points_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
+                                         c_int, c_int, c_int, c_double, c_int, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
+    "lsf_correct_field": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,
+                                  POINTER(c_double), c_void_p]),
+    "lsf_correct_field_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,
+                                         POINTER(c_double), c_void_p, c_void_p]),
     "lsf_label_band": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int,
                                POINTER(ctypes.c_int64), c_void_p]),
     "lsf_label_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int,

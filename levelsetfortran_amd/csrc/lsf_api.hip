@@ -37,6 +37,8 @@
 #include "lsf_measure_band.hpp"
 #include "lsf_sample_points.hpp"
 #include "lsf_cast_rays.hpp"
+#include "lsf_advect_points.hpp"
+#include "lsf_correct_field.hpp"
 #include "lsf_label_band.hpp"
 
 using namespace lsf;
@@ -194,7 +196,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_CR_Q, S_CR_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_CR_Q, S_CR_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_AP_IO, S_CF_IO, S_CF_PLUS, S_CF_MINUS, S_CF_CTL, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -463,6 +465,7 @@ BcWhole bc_whole(int nx, int ny, int nz)
 
 // check_dims and the *_args_ok of every call: pure host code, run on the CPU by tests/test_host_args_cpu.py
 #include "lsf_host_args.hpp"
+#include "lsf_host_args_points.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // One fp64 Jacobi sweep over the cells [lo, hi) of a box: picks the kernel and its launch geometry.
@@ -749,6 +752,7 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 
 #include "lsf_host_sample_points.hpp"
 #include "lsf_host_cast_rays.hpp"
+#include "lsf_host_points.hpp"
 
 #include "lsf_host_label_band.hpp"
 
@@ -1899,6 +1903,87 @@ int lsf_cast_rays(const double* phi, const int32_t* mask, const double* q, int n
     if (qval) HIPCHK(hipMemcpy(qval, d_qval, nr * sizeof(double), hipMemcpyDeviceToHost));
     if (status) HIPCHK(hipMemcpy(status, d_status, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
     return LSF_OK;
+}
+
+int lsf_advect_points_device(const double* d_u, const double* d_v, const double* d_w, const double* d_phi, const double* d_speed,
+                             const int32_t* d_mask, int nx, int ny, int nz, double dx, const double xLo[3], double* d_pts, int npts, int order,
+                             int scheme, double dt, int nsteps, int32_t* d_status, double* cfl, int64_t info[LSF_ADVECT_POINTS_INFO_LEN],
+                             void* stream)
+{
+    Trace trace_("lsf_advect_points_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = advect_points_args_ok(d_u, d_v, d_w, d_phi, d_speed, d_mask, nx, ny, nz, dx, xLo, d_pts, npts, order, scheme, dt, nsteps, d_status)))
+        return rc;
+    return advect_points_core(d_u, d_v, d_w, d_phi, d_speed, d_mask, nx, ny, nz, dx, xLo, d_pts, npts, order, scheme, dt, nsteps, d_status, cfl,
+                              info, (hipStream_t)stream);
+}
+
+int lsf_advect_points(const double* u, const double* v, const double* w, const double* phi, const double* speed, const int32_t* mask, int nx,
+                      int ny, int nz, double dx, const double xLo[3], double* pts, int npts, int order, int scheme, double dt, int nsteps,
+                      int32_t* status, double* cfl, int64_t info[LSF_ADVECT_POINTS_INFO_LEN])
+{
+    Trace trace_("lsf_advect_points");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = advect_points_args_ok(u, v, w, phi, speed, mask, nx, ny, nz, dx, xLo, pts, npts, order, scheme, dt, nsteps, status))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double), np = (size_t)npts;
+    const double* d_in[4];
+    const int32_t* d_mask;
+    if ((rc = velocity_in(c, u, v, w, speed, bytes, d_in))) return rc; // as lsf_advect_field stages them
+    // pts (in and out) and status are staged per call in one slot: 3 doubles per point, then status.  pts is copied in on every call;
+    // both come home on LSF_OK only.
+    if ((rc = ws(c.slot[S_AP_IO], np * (3 * sizeof(double) + sizeof(int32_t))))) return rc;
+    double* d_pts = (double*)c.slot[S_AP_IO].p;
+    int32_t* d_status = status ? (int32_t*)(d_pts + 3 * np) : nullptr;
+    HIPCHK(hipMemcpy(d_pts, pts, 3 * np * sizeof(double), hipMemcpyHostToDevice));
+    if (phi && (rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    if ((rc = advect_points_core(d_in[0], d_in[1], d_in[2], phi ? (const double*)c.slot[S_HPHI].p : nullptr, d_in[3], d_mask, nx, ny, nz, dx, xLo,
+                                 d_pts, npts, order, scheme, dt, nsteps, d_status, cfl, info, nullptr)))
+        return rc;
+    HIPCHK(hipMemcpy(pts, d_pts, 3 * np * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, d_status, np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return LSF_OK;
+}
+
+int lsf_correct_field_device(double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, const double xLo[3], const double* d_pts,
+                             const double* d_rad, int npts, double slack, int32_t* d_status, double* change,
+                             int64_t info[LSF_CORRECT_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_correct_field_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = correct_field_args_ok(d_phi, d_mask, nx, ny, nz, dx, xLo, d_pts, d_rad, npts, slack, d_status))) return rc;
+    return correct_field_core(d_phi, d_mask, nx, ny, nz, dx, xLo, d_pts, d_rad, npts, slack, d_status, change, info, (hipStream_t)stream);
+}
+
+int lsf_correct_field(double* phi, const int32_t* mask, int nx, int ny, int nz, double dx, const double xLo[3], const double* pts,
+                      const double* rad, int npts, double slack, int32_t* status, double* change, int64_t info[LSF_CORRECT_INFO_LEN])
+{
+    Trace trace_("lsf_correct_field");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = correct_field_args_ok(phi, mask, nx, ny, nz, dx, xLo, pts, rad, npts, slack, status))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), np = (size_t)npts;
+    const int32_t* d_mask;
+    // pts, rad and status are staged per call in one slot: 3 + 1 doubles per particle, then status, which comes home on LSF_OK only
+    if ((rc = ws(c.slot[S_CF_IO], np * (4 * sizeof(double) + sizeof(int32_t))))) return rc;
+    double *d_pts = (double*)c.slot[S_CF_IO].p, *d_rad = d_pts + 3 * np;
+    int32_t* d_status = status ? (int32_t*)(d_pts + 4 * np) : nullptr;
+    HIPCHK(hipMemcpy(d_pts, pts, 3 * np * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_rad, rad, np * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // in and out, as lsf_reinit_band takes its field
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    rc = correct_field_core((double*)c.slot[S_HPHI].p, d_mask, nx, ny, nz, dx, xLo, d_pts, d_rad, npts, slack, d_status, change, info, nullptr);
+    if (rc != LSF_OK) {
+        twin_drop(c.twin_phi);
+        return rc;
+    }
+    if (status) HIPCHK(hipMemcpy(status, d_status, np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return twin_out(c, c.twin_phi, S_HPHI, phi, n * sizeof(double));
 }
 
 int lsf_label_band_device(const double* d_phi, const int32_t* d_mask, int32_t* d_label, int nx, int ny, int nz, double iso, int side, int max_passes,

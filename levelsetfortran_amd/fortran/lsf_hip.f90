@@ -44,6 +44,11 @@
 !            iso,tmin,tmax,safety,smin,smax,skip,        marching by the field's own value and skipping what a band mask does
 !            refine,max_steps,thit,hit,grad,status       not hold; optionally a second field q sampled at the hit
 !            [,mask,q,qval])                             (include/lsf.h: lsf_cast_rays)
+!   advectPoints(pts,npts,nx,ny,nz,dx,xLo,order,scheme,  no reference counterpart: points carried through the fields that move
+!                dt,nsteps,status,cfl                    phi, x' = (u,v,w) + speed grad phi / |grad phi|, by TVD-RK3 or Euler over
+!                [,u,v,w,phi,speed,mask])                the interpolant of samplePoints (include/lsf.h: lsf_advect_points)
+!   correctField(phi,nx,ny,nz,dx,xLo,pts,rad,npts,       no reference counterpart: the correction of the particle level set, phi
+!                slack,status,change[,mask])             rebuilt around escaped markers (include/lsf.h: lsf_correct_field)
 !   labelBand(phi,mask,label,nx,ny,nz,iso,side,ncomp)    no reference counterpart: the connected components of the cells with
 !                                                        mask == 1 on either side of phi = iso (include/lsf.h: lsf_label_band)
 !   extendFieldBand(q,phi,mask,nx,ny,nz,dx,band)         no reference counterpart: extendField on the cells with mask == 1
@@ -122,6 +127,8 @@ PUBLIC :: curvatureBand
 PUBLIC :: measureBand
 PUBLIC :: samplePoints
 PUBLIC :: castRays
+PUBLIC :: advectPoints
+PUBLIC :: correctField
 PUBLIC :: labelBand
 PUBLIC :: extendFieldBand
 PUBLIC :: extractSurface, stlWrite
@@ -392,6 +399,36 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: info(9)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_cast_rays
+   ! int lsf_advect_points(const double*,const double*,const double*,const double*,const double*,const int32_t*,int,int,int,double,
+   !                       const double[3],double*,int,int,int,double,int,int32_t*,double*,int64_t[6])
+   FUNCTION lsf_advect_points(u,v,w,phi,speed,mask,nx,ny,nz,dx,xLo,pts,npts,order,scheme,dt,nsteps,status,cfl,info) &
+            BIND(C,NAME='lsf_advect_points') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      TYPE(c_ptr), VALUE :: u,v,w,phi,speed,mask   ! NULL: that group, or the band, is absent
+      INTEGER(c_int), VALUE :: nx,ny,nz,npts,order,scheme,nsteps
+      REAL(c_double), VALUE :: dx,dt
+      REAL(c_double), INTENT(IN) :: xLo(3)
+      REAL(c_double), INTENT(INOUT) :: pts(*)
+      INTEGER(c_int), INTENT(OUT) :: status(*)
+      REAL(c_double), INTENT(OUT) :: cfl
+      INTEGER(c_int64_t), INTENT(OUT) :: info(6)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_advect_points
+   ! int lsf_correct_field(double*,const int32_t*,int,int,int,double,const double[3],const double*,const double*,int,double,int32_t*,
+   !                       double*,int64_t[7])
+   FUNCTION lsf_correct_field(phi,mask,nx,ny,nz,dx,xLo,pts,rad,npts,slack,status,change,info) &
+            BIND(C,NAME='lsf_correct_field') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(INOUT) :: phi(*)
+      TYPE(c_ptr), VALUE :: mask             ! NULL: the whole grid
+      INTEGER(c_int), VALUE :: nx,ny,nz,npts
+      REAL(c_double), VALUE :: dx,slack
+      REAL(c_double), INTENT(IN) :: xLo(3),pts(*),rad(*)
+      INTEGER(c_int), INTENT(OUT) :: status(*)
+      REAL(c_double), INTENT(OUT) :: change
+      INTEGER(c_int64_t), INTENT(OUT) :: info(7)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_correct_field
    ! int lsf_extend_field_band(double*,const double*,const int32_t*,const int32_t*,int,int,int,double,double,int,int*,int64_t*,int,
    !                           int64_t[4])
    FUNCTION lsf_extend_field_band(q,phi,mask,known,nx,ny,nz,dx,band,max_passes,passes_done,changed_trace,trace_cap,info) &
@@ -1247,6 +1284,96 @@ PRINT*, " Rays: samples ",info(7),", strides ",info(8),", began inside ",info(9)
 PRINT*
 
 END SUBROUTINE castRays
+
+!*************************************************************************************!
+! Points carried through the fields that move phi (include/lsf.h: lsf_advect_points; no
+! reference counterpart -- advectNodes below is the reference's own surface-node scheme):
+! pts(npts,3), the layout of surfX, moves in place along
+!    x' = (u,v,w)(x) + speed(x) * grad phi(x) / |grad phi(x)|
+! by nsteps steps of size dt (dt < 0 traces backwards) of TVD-RK3 (scheme = 0) or Euler
+! (scheme = 1), over the interpolant of samplePoints (order = 0 trilinear, 1 Catmull-Rom).
+! u, v, w come together or not at all; speed and phi come together; at least one group.
+! status(t): 0 OK, 1 outside the grid, 2 off the band, 3 flat; a point that stops keeps the
+! position of its last completed step.  cfl: the largest |dt*k|/dx over the completed
+! steps.  The fields are read only.  Prints the counts.
+!*************************************************************************************!
+SUBROUTINE advectPoints(pts,npts,nx,ny,nz,dx,xLo,order,scheme,dt,nsteps,status,cfl,u,v,w,phi,speed,mask)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,order,scheme,nsteps
+INTEGER*4,INTENT(IN) :: npts
+REAL,INTENT(IN) :: dx,xLo(3),dt
+REAL,INTENT(INOUT) :: pts(npts,3)
+INTEGER*4,INTENT(OUT) :: status(npts)
+REAL,INTENT(OUT) :: cfl
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN),OPTIONAL,TARGET :: u,v,w,phi,speed
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN),OPTIONAL,TARGET :: mask
+TYPE(c_ptr) :: pu,pv,pw,pp,ps,pm
+INTEGER(c_int64_t) :: info(6)
+INTEGER(c_int) :: rc
+
+pu = c_null_ptr
+pv = c_null_ptr
+pw = c_null_ptr
+pp = c_null_ptr
+ps = c_null_ptr
+pm = c_null_ptr
+IF (PRESENT(u)) pu = C_LOC(u)
+IF (PRESENT(v)) pv = C_LOC(v)
+IF (PRESENT(w)) pw = C_LOC(w)
+IF (PRESENT(phi)) pp = C_LOC(phi)
+IF (PRESENT(speed)) ps = C_LOC(speed)
+IF (PRESENT(mask)) pm = C_LOC(mask)
+info = 0
+cfl = 0.
+CALL lsf_set_mirror()
+rc = lsf_advect_points(pu,pv,pw,pp,ps,pm,nx,ny,nz,dx,xLo,pts,npts,order,scheme,dt,nsteps,status,cfl,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_advect_points',rc)
+PRINT*, " Points: points ",npts,", ok ",info(1),", outside ",info(2)
+PRINT*, " Points: off the band ",info(3),", flat ",info(4)
+PRINT*, " Points: steps made ",info(5),", linear fallbacks ",info(6),", CFL ",cfl
+PRINT*
+
+END SUBROUTINE advectPoints
+
+!*************************************************************************************!
+! The correction of the particle level set (include/lsf.h: lsf_correct_field; no reference
+! counterpart): phi, in place, is rebuilt around every marker that has escaped.  pts(npts,3)
+! are the markers, rad(npts) their radii with the side in the sign (> 0: the marker belongs
+! where phi > 0).  A marker with phi on the wrong side by more than slack times its radius
+! offers s*(r - distance) to the 8 corners of its cell; the largest offer of the positive
+! markers and the smallest of the negative ones are merged by magnitude.  status(t):
+! 0 in place, 1 escaped, 2 outside the grid, 3 off the band, 4 non-finite phi, 5 bad radius.
+! change: the largest |new - old|.  mask: only cells with mask == 1 are corrected.  The
+! result does not depend on the order of the markers.  Prints the counts.
+!*************************************************************************************!
+SUBROUTINE correctField(phi,nx,ny,nz,dx,xLo,pts,rad,npts,slack,status,change,mask)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+INTEGER*4,INTENT(IN) :: npts
+REAL,INTENT(IN) :: dx,xLo(3),slack
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: phi
+REAL,INTENT(IN) :: pts(npts,3),rad(npts)
+INTEGER*4,INTENT(OUT) :: status(npts)
+REAL,INTENT(OUT) :: change
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN),OPTIONAL,TARGET :: mask
+TYPE(c_ptr) :: pm
+INTEGER(c_int64_t) :: info(7)
+INTEGER(c_int) :: rc
+
+pm = c_null_ptr
+IF (PRESENT(mask)) pm = C_LOC(mask)
+info = 0
+change = 0.
+CALL lsf_set_mirror()
+rc = lsf_correct_field(phi,pm,nx,ny,nz,dx,xLo,pts,rad,npts,slack,status,change,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_correct_field',rc)
+PRINT*, " Correction: markers ",npts,", in place ",info(1),", escaped ",info(2)
+PRINT*, " Correction: outside ",info(3),", off the band ",info(4)
+PRINT*, " Correction: non-finite ",info(5),", bad radius ",info(6)
+PRINT*, " Correction: points changed ",info(7),", largest change ",change
+PRINT*
+
+END SUBROUTINE correctField
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

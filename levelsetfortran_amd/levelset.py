@@ -42,6 +42,11 @@ and the first hit of a ray with the surface, marching by the field's own value a
 
   castRays(phi, nx, ny, nz, dx, xLo, org, dir, ...)             include/lsf.h: lsf_cast_rays
 
+and points carried through the fields that move phi, with the correction of the particle level set that they make possible:
+
+  advectPoints(pts, nx, ny, nz, dx, xLo, dt, steps, ...)        include/lsf.h: lsf_advect_points
+  correctField(phi, nx, ny, nz, dx, xLo, pts, rad, ...)         include/lsf.h: lsf_correct_field (markers from seedParticles)
+
 and how many bodies there are and which cell belongs to which, the connected components on the cells of a mask:
 
   labelBand(phi, mask, nx, ny, nz, label, ...)                  include/lsf.h: lsf_label_band
@@ -72,7 +77,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "castRays", "CastReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["advectPoints", "AdvectPointsReport", "correctField", "CorrectReport", "seedParticles", "reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "castRays", "CastReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -1252,6 +1257,190 @@ def castRays(phi, nx: int, ny: int, nz: int, dx: float, xLo, org, dir, *, order:
                                ptr(qval), ptr(status), info.ctypes.data)
     _lib.check(rc)
     return CastReport(thit, hit, grad, qval, status, tuple(int(v) for v in info))
+
+
+class AdvectPointsReport(NamedTuple):
+    """What lsf_advect_points returns (include/lsf.h): `pts` (npts, 3; the moved points, Fortran-ordered), `status` (npts, int32: 0 OK,
+    1 OUTSIDE, 2 OFFBAND, 3 FLAT), `cfl` (the largest |dt * k| / dx over the completed steps) and `info`, the six counts [OK, OUTSIDE,
+    OFFBAND, FLAT, completed steps summed over the points, linear fallbacks of a cubic request]."""
+    pts: object
+    status: object
+    cfl: float
+    info: tuple
+
+
+_POINT_SCHEMES = {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}
+
+
+def _points_common(nx, ny, nz, dx, xLo):
+    lo = np.ascontiguousarray(xLo, dtype=np.float64)
+    if lo.shape != (3,) or not np.all(np.isfinite(lo)):
+        raise ValueError("xLo must hold 3 finite values")
+    dx = float(dx)
+    if not (np.isfinite(dx) and dx > 0.0):
+        raise ValueError("dx must be finite and > 0")
+    if min(int(nx), int(ny), int(nz)) < 1:
+        raise ValueError("nx, ny, nz must be >= 1")
+    return lo, dx
+
+
+def _points_layout(pts, dev, name="pts"):
+    if len(pts.shape) != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError(f"{name} must have shape (npts, 3) with npts >= 1")
+    if dev:
+        import torch
+
+        if not pts.is_cuda or pts.dtype != torch.float64 or not pts.t().is_contiguous():
+            raise TypeError(f"{name} must be a float64 CUDA tensor of shape (npts, 3) in Fortran order (the transpose of a contiguous (3, npts))")
+    elif not isinstance(pts, np.ndarray) or pts.dtype != np.float64 or not pts.flags.f_contiguous:
+        raise TypeError(f"{name} must be a Fortran-ordered float64 numpy array of shape (npts, 3)")
+    return int(pts.shape[0])
+
+
+def advectPoints(pts, nx: int, ny: int, nz: int, dx: float, xLo, dt: float, steps: int, *, velocity=None, speed=None, phi=None, mask=None,
+                 order: str = "cubic", scheme: str = "rk3") -> AdvectPointsReport:
+    """Points carried through the fields that move phi (include/lsf.h: lsf_advect_points): x' = velocity(x) + speed(x) * grad phi(x) /
+    |grad phi(x)| in fields frozen for the call, `steps` steps of TVD-RK3 ("rk3") or Euler ("euler") of size dt (dt < 0 traces
+    backwards), over the interpolant of samplePoints (order="linear" or "cubic").
+
+    pts: (npts, 3) float64 in Fortran order -- tracers, the surfX of extractSurface, markers of seedParticles; it is never written:
+    the moved points come back in the report.  velocity: (u, v, w) fields; speed needs phi and phi needs speed.  A point that leaves
+    the grid, walks off the mask or meets a flat phi keeps the position of its last completed step and says why in status.
+    Numpy in gives numpy out (host seam); CUDA tensors in give CUDA tensors out (device seam, on the tensor's current stream).
+    """
+    lo, dx = _points_common(nx, ny, nz, dx, xLo)
+    dt, steps = float(dt), int(steps)
+    if not np.isfinite(dt):
+        raise ValueError("dt must be finite")
+    if order not in _SAMPLE_ORDERS:
+        raise ValueError("order must be 'linear' or 'cubic'")
+    if scheme not in _POINT_SCHEMES:
+        raise ValueError("scheme must be 'rk3' or 'euler'")
+    if not 1 <= steps <= _lib.LSF_ADVECT_POINTS_MAX_STEPS:
+        raise ValueError(f"steps must be in 1..{_lib.LSF_ADVECT_POINTS_MAX_STEPS}")
+    if velocity is not None and (len(velocity) != 3 or any(f is None for f in velocity)):
+        raise ValueError("velocity must be (u, v, w)")
+    if velocity is None and speed is None:
+        raise ValueError("neither a velocity nor a speed is given")
+    if (speed is None) != (phi is None):
+        raise ValueError("speed and phi are given together")
+    dev = _is_torch(pts)
+    named = [(n, a) for n, a in (("u", None if velocity is None else velocity[0]), ("v", None if velocity is None else velocity[1]),
+                                 ("w", None if velocity is None else velocity[2]), ("phi", phi), ("speed", speed), ("mask", mask))]
+    if any(_is_torch(a) != dev for _, a in named if a is not None):
+        raise TypeError("pts and the fields must all be numpy arrays or all be CUDA tensors")
+    npts = _points_layout(pts, dev)
+    lib = _lib.load()
+    info = np.zeros(_lib.LSF_ADVECT_POINTS_INFO_LEN, dtype=np.int64)
+    cfl = ctypes.c_double(0.0)
+    if dev:
+        import torch
+
+        if any(a.device != pts.device for _, a in named if a is not None):
+            raise ValueError("pts and the fields must live on one device")
+        f = [None if a is None else _dev_ptr(a, torch.int32 if n == "mask" else torch.float64, nx, ny, nz, n) for n, a in named]
+        out = pts.t().clone().t()
+        status = torch.empty(npts, dtype=torch.int32, device=pts.device)
+        rc = lib.lsf_advect_points_device(*f, nx, ny, nz, dx, lo.ctypes.data, out.data_ptr(), npts, _SAMPLE_ORDERS[order], _POINT_SCHEMES[scheme],
+                                          dt, steps, status.data_ptr(), ctypes.byref(cfl), info.ctypes.data, _stream_and_device(pts))
+    else:
+        f = [None if a is None else _host_ptr(a, np.int32 if n == "mask" else np.float64, nx, ny, nz, n) for n, a in named]
+        out = pts.copy(order="F")
+        status = np.zeros(npts, dtype=np.int32)
+        rc = lib.lsf_advect_points(*f, nx, ny, nz, dx, lo.ctypes.data, out.ctypes.data, npts, _SAMPLE_ORDERS[order], _POINT_SCHEMES[scheme], dt,
+                                   steps, status.ctypes.data, ctypes.byref(cfl), info.ctypes.data)
+    _lib.check(rc)
+    return AdvectPointsReport(out, status, float(cfl.value), tuple(int(v) for v in info))
+
+
+class CorrectReport(NamedTuple):
+    """What lsf_correct_field returns (include/lsf.h): `status` (npts, int32: 0 INPLACE, 1 ESCAPED, 2 OUTSIDE, 3 OFFBAND, 4 NONFINITE,
+    5 BADRADIUS), `change` (the largest |new - old| over the points whose bits changed) and `info`, the seven counts [INPLACE, ESCAPED,
+    OUTSIDE, OFFBAND, NONFINITE, BADRADIUS, points whose bits changed]."""
+    status: object
+    change: float
+    info: tuple
+
+
+def correctField(phi, nx: int, ny: int, nz: int, dx: float, xLo, pts, rad, *, mask=None, slack: float = 1.0) -> CorrectReport:
+    """The correction step of the particle level set (include/lsf.h: lsf_correct_field): phi, in place, is rebuilt around every marker
+    that has ESCAPED -- one that sits on the wrong side of the surface by more than slack times its radius -- from the marker's sphere.
+
+    pts: (npts, 3) float64 in Fortran order; rad: (npts) float64, the side in its sign (> 0: the marker belongs where phi > 0) and the
+    radius in its magnitude (seedParticles makes both).  With a mask only list cells are corrected and markers whose cell has a corner
+    off the list are left out (status OFFBAND).  The result does not depend on the order of the particles.  Numpy in: host seam; CUDA
+    tensors in: device seam, on the tensor's current stream.
+    """
+    lo, dx = _points_common(nx, ny, nz, dx, xLo)
+    slack = float(slack)
+    if not (np.isfinite(slack) and slack >= 0.0):
+        raise ValueError("slack must be finite and >= 0")
+    dev = _is_torch(phi)
+    if any(_is_torch(a) != dev for a in (pts, rad) + (() if mask is None else (mask,))):
+        raise TypeError("phi, mask, pts and rad must all be numpy arrays or all be CUDA tensors")
+    npts = _points_layout(pts, dev)
+    if tuple(rad.shape) != (npts,):
+        raise ValueError("rad must have shape (npts,)")
+    lib = _lib.load()
+    info = np.zeros(_lib.LSF_CORRECT_INFO_LEN, dtype=np.int64)
+    change = ctypes.c_double(0.0)
+    if dev:
+        import torch
+
+        if any(a.device != phi.device for a in (pts, rad) + (() if mask is None else (mask,))):
+            raise ValueError("phi, mask, pts and rad must live on one device")
+        if rad.dtype != torch.float64 or not rad.is_contiguous():
+            raise TypeError("rad must be a contiguous float64 CUDA tensor")
+        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        m = None if mask is None else _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+        status = torch.empty(npts, dtype=torch.int32, device=phi.device)
+        rc = lib.lsf_correct_field_device(p, m, nx, ny, nz, dx, lo.ctypes.data, pts.data_ptr(), rad.data_ptr(), npts, slack, status.data_ptr(),
+                                          ctypes.byref(change), info.ctypes.data, _stream_and_device(phi))
+    else:
+        if not isinstance(rad, np.ndarray) or rad.dtype != np.float64 or not rad.flags.c_contiguous:
+            raise TypeError("rad must be a contiguous float64 numpy array")
+        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
+        m = None if mask is None else _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+        status = np.zeros(npts, dtype=np.int32)
+        rc = lib.lsf_correct_field(p, m, nx, ny, nz, dx, lo.ctypes.data, pts.ctypes.data, rad.ctypes.data, npts, slack, status.ctypes.data,
+                                   ctypes.byref(change), info.ctypes.data)
+    _lib.check(rc)
+    return CorrectReport(status, float(change.value), tuple(int(v) for v in info))
+
+
+def seedParticles(phi, nx: int, ny: int, nz: int, dx: float, xLo, *, mask=None, per_cell: int = 16, rmin: float = 0.1, rmax: float = 0.5,
+                  band: float = 3.0, seed: int = 0):
+    """Marker particles for correctField, on the host (run once per simulation and at reseeds): (pts (npts, 3) Fortran-ordered, rad).
+
+    The cells whose 8 corners all have |phi| < band * dx (and, under a mask, are all interior points with mask == 1) each get per_cell
+    points drawn uniformly from np.random.default_rng(seed), cell after cell with k the slowest index; phi is sampled there with
+    samplePoints(order="linear"); the points with rmin * dx <= |val| <= band * dx are kept and rad = sign(val) * clip(|val|, rmin * dx,
+    rmax * dx).  phi and mask are numpy arrays of shape (nx+1, ny+1, nz+1) in Fortran order.
+    """
+    lo, dx = _points_common(nx, ny, nz, dx, xLo)
+    f = np.asarray(phi)
+    if f.shape != (nx + 1, ny + 1, nz + 1):
+        raise ValueError("phi must be a numpy array of shape (nx+1, ny+1, nz+1)")
+    near = np.abs(f) < band * dx
+    if mask is not None:
+        lst = np.zeros(f.shape, bool)
+        lst[1:-1, 1:-1, 1:-1] = np.asarray(mask)[1:-1, 1:-1, 1:-1] == 1
+        near &= lst
+    c = near[:-1, :-1, :-1].copy()
+    for oa in range(2):
+        for ob in range(2):
+            for oc in range(2):
+                c &= near[oa:nx + oa, ob:ny + ob, oc:nz + oc]
+    cells = np.argwhere(c)
+    off = np.random.default_rng(seed).random((cells.shape[0], int(per_cell), 3))
+    pts = np.asfortranarray((lo + (cells[:, None, :] + off) * dx).reshape(-1, 3))
+    if not pts.shape[0]:
+        return np.zeros((0, 3), order="F"), np.zeros(0)
+    val = samplePoints(phi, nx, ny, nz, dx, lo, pts, order="linear", mask=mask, want_grad=False).val
+    with np.errstate(invalid="ignore"):
+        keep = (np.abs(val) >= rmin * dx) & (np.abs(val) <= band * dx)
+    val = val[keep]
+    return np.asfortranarray(pts[keep]), np.sign(val) * np.clip(np.abs(val), rmin * dx, rmax * dx)
 
 
 class SurfaceInfo(NamedTuple):
