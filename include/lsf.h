@@ -894,6 +894,79 @@ int lsf_measure_band_device(const double *d_phi, const int32_t *d_mask, const do
                             int nz, double dx, const double xLo[3], double iso, double M[LSF_MEASURE_LEN],
                             int64_t info[LSF_MEASURE_INFO_LEN], void *stream);
 
+/* ---- cut-cell volume fractions and face apertures on the cells of a caller's mask ----------
+ * No reference counterpart.  What an embedded-boundary (cut-cell) flow solver needs of a level-set geometry: per cell of the list how
+ * much of it lies inside the body phi < iso, how much of each lower face is open to it, the surface's area vector inside the cell,
+ * and over the list the body's volume and the smallest cut-cell fraction (the "small cell" number).  The volume is an integral over
+ * cells: it needs no closed surface inside the list.  The per-cell outputs have phi's layout.  volume, vof_min and info are host
+ * scalars / a host array on both seams; all three may be NULL.
+ *   LIST     the rule of lsf_reinit_band: the interior points (1..n-1 on each axis) with mask == 1.  Any other mask value means
+ *            "not in the list"; a 1 on a wall point is ignored.  The mask is read and never written.
+ *   cell     a list point c0 names the cell whose lower corner it is.  Its seven other corners are read from phi whether they are
+ *            listed or not (c0 is interior, so i + 1 <= nx, j + 1 <= ny, k + 1 <= nz always hold).  f = phi - iso; INSIDE means
+ *            f < 0.  The corner byte has bit x + 2y + 4z set where that corner is inside.  The cell is cut into the six Kuhn
+ *            tetrahedra of lsf_extract_surface; nodes (t = fa / (fa - fb) from the lower endpoint u < v of a crossed edge),
+ *            triangles, their orientation and their order (tetrahedron 0..5, triangle 0..1) are that call's.
+ *   units    everything per cell is computed in CELL UNITS: c0 at the origin, dx = 1.  Coordinate A of the node on the edge {u, v}
+ *            is bit_A(u) + t where the edge runs along A and bit_A(u) where it does not -- the node of lsf_measure_band with
+ *            xLo = 0, (i,j,k) = 0 and dx = 1.  The per-cell outputs therefore do not depend on dx.
+ *   s(m, j)  the fraction of the edge from corner m to the zero crossing on the edge {m, j}: the node's own t when m is the edge's
+ *            lower endpoint, 1.0 - t otherwise.
+ *   tri(a, b, c)  the inside fraction of a face triangle with linear f: no vertex inside 0.0; all three 1.0; one inside, m, the
+ *            others o1, o2: s(m,o1) * s(m,o2); two inside i1, i2 and o outside: 1.0 - s(o,i1) * s(o,i2).
+ *   face(A, base)  the aperture of the face normal to axis A at base in {0, 1 << A}, with b < c the bits of the two other axes:
+ *              face = 0.5 * (tri(base, base|b, base|b|c) + tri(base, base|c, base|b|c))
+ *            -- the face cut along the Kuhn diagonal base - base|b|c, as the tetrahedra cut it.  The upper face of c0 is, bit for
+ *            bit, the lower face of c0 + e_A: the same four values through the same function.
+ *   outputs  at a list point (written at list points only, never anywhere else):
+ *              ax, ay, az   face(A, 0), the LOWER faces (the MAC convention: the upper face belongs to the neighbour);
+ *              bx, by, bz   the sum of 0.5 * n_A over the cell's triangles, n = (P1 - P0) x (P2 - P0) written as in
+ *                           lsf_measure_band, added to 0.0 in emission order: the surface's outward area vector in units of dx^2
+ *                           (b_A = face(A, 0) - face(A, 1 << A) up to rounding: the cell's inside part is closed);
+ *              vof          V = the sum of ((P0x*cx + P0y*cy) + P0z*cz) / 6. over the triangles, c = P1 x P2 as in lsf_measure_band,
+ *                           added to 0.0 in emission order;  raw = ((up_x + up_y) + up_z) / 3. + V  with up_A = face(A, 1 << A)
+ *                           -- the divergence theorem about c0, to which the lower faces contribute nothing;  the stored value is
+ *                           raw < 0 ? 0.0 : (raw > 1 ? 1.0 : raw).
+ *            Corner byte 0: vof = a = b = 0.0.  Corner byte 255: vof = 1.0, a = 1.0, b = 0.0.  Everything is evaluated exactly as
+ *            written, left to right, without contraction; there is one arithmetic and no mode word.
+ *   groups   vof, {ax, ay, az} and {bx, by, bz}: each group is given whole or left NULL.  At least one group, or volume, is given.
+ *   totals   volume = (the sum of the stored vof over the list cells) * ((dx * dx) * dx), summed in lsf_measure_band's fixed order
+ *            (an xor butterfly over the 64 lanes of a wave, the waves of a block of 256 entries in wave order, the blocks in block
+ *            order on the host): bit-identical from run to run, between the seams and on any stream, and within
+ *            N * 2^-53 * sum|vof| of the exact sum for N non-zero fractions.  vof_min: the smallest stored vof over the CUT cells
+ *            (corner byte neither 0 nor 255), +inf when there is none.
+ *   info     [0] list cells; [1] cut cells; [2] full cells (byte 255); [3] OPEN cut cells: at least one of the six face-neighbour
+ *            cells (lower corners c0 +- e_A) is not in LIST, a wall point included, so the caller lacks some aperture next to
+ *            it (lsf_measure_band's info[3]); [4] cut cells whose raw was clamped.  Written on LSF_OK only.
+ *   empty    an empty list: LSF_OK, info all 0, volume 0.0, vof_min +inf, nothing else written.
+ *   errors   LSF_ERR_INVALID, all detected before anything is written, with the count in lsf_last_error() where there is one: a
+ *            NULL phi or mask; the dimensions lsf_reinit_band refuses; dx not finite or <= 0; iso not finite; an incomplete
+ *            group; nothing requested; an output sharing a byte with phi, the mask or another output; a crossed edge of a listed
+ *            cell with a non-finite phi - iso on an endpoint, counted as lsf_measure_band counts it.  No device:
+ *            LSF_ERR_NO_DEVICE -- there is no CPU fallback.
+ *   result   every per-cell output, info and vof_min equal the serial statement tests/cut_cells_ref.py with ==, volume within the
+ *            bound above.
+ *   seams    lsf_cut_cells_band takes phi through its twin under lsf_mirror as lsf_measure_band does and the mask as
+ *            lsf_reinit_band does; each given output is staged in a slot of its own as cell_area is: copied in on every call,
+ *            copied back on LSF_OK only, no twin.  lsf_cut_cells_band_device returns after the stream is synchronised.
+ * Guidance: to have every aperture of every cut cell (the upper faces are the neighbours' lower ones), dilate the mask by one cell.
+ * A mask of phi < 2.1 dx (the inside plus a rim) makes volume the body's volume with no closed-surface assumption.  The fraction is
+ * that of the polyhedron lsf_extract_surface emits: second order, 2.17 % low on the sphere of radius 0.6 at 25^3 points, 0.54 % at
+ * 49^3.  Work: the list build and two launches over the list; 8 gathered loads per list cell, and for a cut cell its nodes and up to
+ * 24 edge fractions.  Workspace: that of the list; the host seam adds one field per given output.  Out of scope: fp32, multi-GPU,
+ * volume and face centroids, second moments, a per-step trace inside lsf_evolve_band, cell merging.
+ * Timed once on one MI355X beside lsf_measure_band (totals only) and lsf_curvature_band (all three outputs) on the same sphere and
+ * mask |phi| < 8.1 dx (profiles/cut_cells_time.txt, from profiles/micro/cut_cells_time.py; device seam, ms per call, list build
+ * included): 0.34 with all outputs and 0.32 with volume only against 0.38 and 0.26 at 256^3 (34 070 of 372 155 list cells cut),
+ * 0.68 and 0.62 against 0.82 and 0.52 at 512^3.  No speed is claimed beyond that record. */
+#define LSF_CUT_INFO_LEN 5
+int lsf_cut_cells_band(const double *phi, const int32_t *mask, int nx, int ny, int nz, double dx, double iso, double *vof, double *ax,
+                       double *ay, double *az, double *bx, double *by, double *bz, double *volume, double *vof_min,
+                       int64_t info[LSF_CUT_INFO_LEN]);
+int lsf_cut_cells_band_device(const double *d_phi, const int32_t *d_mask, int nx, int ny, int nz, double dx, double iso, double *d_vof,
+                              double *d_ax, double *d_ay, double *d_az, double *d_bx, double *d_by, double *d_bz, double *volume,
+                              double *vof_min, int64_t info[LSF_CUT_INFO_LEN], void *stream);
+
 /* ---- the field at arbitrary points: value, gradient, a second field and the foot point on phi = iso ----------
  * No reference counterpart (its setPhiSurf is private to lsf_advect_nodes, trilinear only, moves a node on the positive side only and
  * clamps instead of refusing).  A caller that holds particles, the nodes of another mesh or the nodes lsf_extract_surface has just
@@ -1305,7 +1378,7 @@ int lsf_mirror_sync(void *host);
  * copied to the host.  What becomes of the twins it touched depends on how far the call came:
  *   - a call refused before it wrote anything keeps them as they were, an un-synced earlier result included, which a later
  *     lsf_mirror_sync still brings home: every LSF_ERR_INVALID of lsf_advect_field, lsf_advect_field_band, lsf_evolve_band,
- *     lsf_evolve_band_curv, lsf_curvature_band, lsf_measure_band, lsf_sample_points, lsf_extend_field, lsf_extend_field_band and lsf_extract_surface (argument checks and the checks of
+ *     lsf_evolve_band_curv, lsf_curvature_band, lsf_measure_band, lsf_cut_cells_band, lsf_sample_points, lsf_extend_field, lsf_extend_field_band and lsf_extract_surface (argument checks and the checks of
  *     u, v, w, speed, q and the list alike: all are made before phi or the mask is written), and the argument checks of
  *     every other call, which come before the twins are looked at;
  *   - any other failure -- LSF_ERR_HIP anywhere, and an error that lsf_reinit, lsf_minmax, lsf_reinit_band or

@@ -27,6 +27,7 @@ LSF_EVOLVE_INFO_LEN = 6  # include/lsf.h: lsf_evolve_band
 LSF_CURV_INFO_LEN = 4  # include/lsf.h: lsf_curvature_band
 LSF_SURF_INFO_LEN = 4  # include/lsf.h: lsf_extract_surface
 LSF_MEASURE_LEN, LSF_MEASURE_INFO_LEN = 9, 5  # include/lsf.h: lsf_measure_band
+LSF_CUT_INFO_LEN = 5  # include/lsf.h: lsf_cut_cells_band
 LSF_SAMPLE_LINEAR, LSF_SAMPLE_CUBIC, LSF_SAMPLE_INFO_LEN = 0, 1, 6  # include/lsf.h: lsf_sample_points
 LSF_SAMPLE_OK, LSF_SAMPLE_OUTSIDE, LSF_SAMPLE_OFFBAND, LSF_SAMPLE_FLAT, LSF_SAMPLE_NOT_CONVERGED = 0, 1, 2, 3, 4  # ... its status[t]
 LSF_CAST_INFO_LEN = 9  # include/lsf.h: lsf_cast_rays
@@ -124,6 +125,10 @@ SIGNATURES = {
     "lsf_measure_band": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, c_void_p, c_void_p]),
     "lsf_measure_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, c_void_p, c_void_p,
                                         c_void_p]),
+    "lsf_cut_cells_band": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsf_cut_cells_band_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsf_sample_points": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
                                   c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsf_sample_points_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int, c_double,

@@ -35,6 +35,7 @@
 #include "lsf_extend_band.hpp"
 #include "lsf_extract_surface.hpp"
 #include "lsf_measure_band.hpp"
+#include "lsf_cut_cells_band.hpp"
 #include "lsf_sample_points.hpp"
 #include "lsf_cast_rays.hpp"
 #include "lsf_advect_points.hpp"
@@ -196,7 +197,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_CR_Q, S_CR_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_AP_IO, S_CF_IO, S_CF_PLUS, S_CF_MINUS, S_CF_CTL, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_CR_Q, S_CR_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_AP_IO, S_CF_IO, S_CF_PLUS, S_CF_MINUS, S_CF_CTL, S_CC_VOF, S_CC_AX, S_CC_AY, S_CC_AZ, S_CC_BX, S_CC_BY, S_CC_BZ, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -466,6 +467,7 @@ BcWhole bc_whole(int nx, int ny, int nz)
 // check_dims and the *_args_ok of every call: pure host code, run on the CPU by tests/test_host_args_cpu.py
 #include "lsf_host_args.hpp"
 #include "lsf_host_args_points.hpp"
+#include "lsf_host_args_cut.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // One fp64 Jacobi sweep over the cells [lo, hi) of a box: picks the kernel and its launch geometry.
@@ -749,6 +751,7 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_extract_surface.hpp"
 
 #include "lsf_host_measure_band.hpp"
+#include "lsf_host_cut_cells_band.hpp"
 
 #include "lsf_host_sample_points.hpp"
 #include "lsf_host_cast_rays.hpp"
@@ -1802,6 +1805,43 @@ int lsf_measure_band(const double* phi, const int32_t* mask, const double* q, do
     if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
     if ((rc = measure_band_core((const double*)c.slot[S_HPHI].p, d_mask, d_q, d_cell, nx, ny, nz, dx, xLo, iso, M, info, nullptr))) return rc;
     if (cell_area) HIPCHK(hipMemcpy(cell_area, d_cell, bytes, hipMemcpyDeviceToHost));
+    return LSF_OK;
+}
+
+int lsf_cut_cells_band_device(const double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, double iso, double* d_vof, double* d_ax,
+                              double* d_ay, double* d_az, double* d_bx, double* d_by, double* d_bz, double* volume, double* vof_min,
+                              int64_t info[LSF_CUT_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_cut_cells_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = cut_cells_args_ok(d_phi, d_mask, nx, ny, nz, dx, iso, d_vof, d_ax, d_ay, d_az, d_bx, d_by, d_bz, volume))) return rc;
+    return cut_cells_core(d_phi, d_mask, nx, ny, nz, dx, iso, d_vof, d_ax, d_ay, d_az, d_bx, d_by, d_bz, volume, vof_min, info, (hipStream_t)stream);
+}
+
+int lsf_cut_cells_band(const double* phi, const int32_t* mask, int nx, int ny, int nz, double dx, double iso, double* vof, double* ax, double* ay,
+                       double* az, double* bx, double* by, double* bz, double* volume, double* vof_min, int64_t info[LSF_CUT_INFO_LEN])
+{
+    Trace trace_("lsf_cut_cells_band");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = cut_cells_args_ok(phi, mask, nx, ny, nz, dx, iso, vof, ax, ay, az, bx, by, bz, volume))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), bytes = n * sizeof(double);
+    // the outputs have no twin (off the list they stay bit for bit): each in a slot of its own, in on every call, home on LSF_OK
+    double* const h_out[7] = {vof, ax, ay, az, bx, by, bz};
+    const Slot s_out[7] = {S_CC_VOF, S_CC_AX, S_CC_AY, S_CC_AZ, S_CC_BX, S_CC_BY, S_CC_BZ};
+    double* d_out[7];
+    const int32_t* d_mask;
+    for (int q = 0; q < 7; ++q)
+        if ((rc = stage_in(c, s_out[q], h_out[q], bytes, &d_out[q]))) return rc;
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, bytes))) return rc; // phi is an input only
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    if ((rc = cut_cells_core((const double*)c.slot[S_HPHI].p, d_mask, nx, ny, nz, dx, iso, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5],
+                             d_out[6], volume, vof_min, info, nullptr)))
+        return rc;
+    for (int q = 0; q < 7; ++q)
+        if (h_out[q]) HIPCHK(hipMemcpy(h_out[q], d_out[q], bytes, hipMemcpyDeviceToHost));
     return LSF_OK;
 }
 

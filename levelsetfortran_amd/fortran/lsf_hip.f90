@@ -37,6 +37,9 @@
 !   measureBand(phi,mask,nx,ny,nz,dx,xLo,iso,M)          no reference counterpart: area, enclosed volume, their first moments
 !                                                        and the surface's, summed over the cells with mask == 1 only
 !                                                        (include/lsf.h: lsf_measure_band)
+!   cutCellsBand(phi,mask,nx,ny,nz,dx,iso,vof,ax,ay,az,volume)  no reference counterpart: the volume fraction inside phi < iso and
+!                                                        the apertures of the lower faces of the cells with mask == 1, and
+!                                                        the body's volume (include/lsf.h: lsf_cut_cells_band)
 !   samplePoints(phi,nx,ny,nz,dx,xLo,pts,npts,order,     no reference counterpart: phi, its gradient and the foot point on
 !                iso,iters,tol,val,grad,foot,status      phi = iso at arbitrary points, trilinear or Catmull-Rom; optionally a
 !                [,mask,q,qval])                         second field q and a band mask (include/lsf.h: lsf_sample_points)
@@ -125,6 +128,7 @@ PUBLIC :: evolveBand
 PUBLIC :: evolveBandCurv
 PUBLIC :: curvatureBand
 PUBLIC :: measureBand
+PUBLIC :: cutCellsBand
 PUBLIC :: samplePoints
 PUBLIC :: castRays
 PUBLIC :: advectPoints
@@ -355,6 +359,21 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: info(5)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_measure_band
+   ! int lsf_cut_cells_band(const double*,const int32_t*,int,int,int,double,double,double*,double*,double*,double*,double*,double*,
+   !                        double*,double*,double*,int64_t[5])
+   FUNCTION lsf_cut_cells_band(phi,mask,nx,ny,nz,dx,iso,vof,ax,ay,az,bx,by,bz,volume,vof_min,info) &
+            BIND(C,NAME='lsf_cut_cells_band') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(IN) :: phi(*)
+      INTEGER(c_int), INTENT(IN) :: mask(*)
+      INTEGER(c_int), VALUE :: nx,ny,nz
+      REAL(c_double), VALUE :: dx,iso
+      REAL(c_double), INTENT(INOUT) :: vof(*),ax(*),ay(*),az(*)
+      TYPE(c_ptr), VALUE :: bx,by,bz         ! NULL: no area vector wanted
+      REAL(c_double), INTENT(OUT) :: volume,vof_min
+      INTEGER(c_int64_t), INTENT(OUT) :: info(5)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_cut_cells_band
    ! int lsf_label_band(const double*,const int32_t*,int32_t*,int,int,int,double,int,int,int64_t*,int,int64_t*,int64_t[8])
    FUNCTION lsf_label_band(phi,mask,label,nx,ny,nz,iso,side,max_passes,comp,comp_cap,ncomp,info) &
             BIND(C,NAME='lsf_label_band') RESULT(rc)
@@ -1150,6 +1169,42 @@ IF (info(4) > 0) PRINT*, " Measures on the band: ",info(4)," crossed cells at th
 PRINT*
 
 END SUBROUTINE measureBand
+
+!*************************************************************************************!
+! How much of each cell lies inside the body and how much of each face is open, on the
+! cells of a mask only (include/lsf.h: lsf_cut_cells_band; no reference counterpart):
+! what a cut-cell (embedded-boundary) solver takes from a level set.  At every interior
+! point with mask == 1 vof receives the fraction of the cell whose lower corner the point
+! is that lies in phi < iso, and ax, ay, az the open fractions of that cell's LOWER faces
+! (the upper ones are the neighbours' lower ones); nothing is written anywhere else.
+! volume is the sum of the fractions times dx**3: with a mask of phi < 2.1*dx the body's
+! volume.  phi and mask are read only.  Prints the volume, the cells and the smallest
+! cut-cell fraction.
+!*************************************************************************************!
+SUBROUTINE cutCellsBand(phi,mask,nx,ny,nz,dx,iso,vof,ax,ay,az,volume)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+REAL,INTENT(IN) :: dx,iso
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: mask
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: vof,ax,ay,az
+REAL,INTENT(OUT) :: volume
+REAL :: vof_min
+INTEGER(c_int64_t) :: info(5)
+INTEGER(c_int) :: rc
+
+volume = 0.
+vof_min = 0.
+info = 0
+CALL lsf_set_mirror()
+rc = lsf_cut_cells_band(phi,mask,nx,ny,nz,dx,iso,vof,ax,ay,az,c_null_ptr,c_null_ptr,c_null_ptr,volume,vof_min,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_cut_cells_band',rc)
+PRINT*, " Cut cells on the band: volume ",volume,", cut cells ",info(2),", full cells ",info(3)," of ",info(1), &
+        ", smallest cut-cell fraction ",vof_min
+IF (info(4) > 0) PRINT*, " Cut cells on the band: ",info(4)," cut cells at the edge of the list: an aperture is missing"
+PRINT*
+
+END SUBROUTINE cutCellsBand
 
 !*************************************************************************************!
 ! How many bodies there are and which cell belongs to which, on the cells of a mask only

@@ -34,6 +34,10 @@ and the area, the enclosed volume, the centroids and the integral of a field ove
 
   measureBand(phi, mask, nx, ny, nz, dx, xLo, ...)              include/lsf.h: lsf_measure_band
 
+and what a cut-cell solver takes from the geometry -- volume fraction, face apertures and area vector per cell of a mask:
+
+  cutCellsBand(phi, mask, nx, ny, nz, dx, ...)                  include/lsf.h: lsf_cut_cells_band
+
 and the field, its gradient, a second field and the foot point on the surface at arbitrary points (particles, nodes of another mesh):
 
   samplePoints(phi, nx, ny, nz, dx, xLo, pts, ...)              include/lsf.h: lsf_sample_points
@@ -77,7 +81,7 @@ import numpy as np
 from . import _lib
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 
-__all__ = ["advectPoints", "AdvectPointsReport", "correctField", "CorrectReport", "seedParticles", "reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "castRays", "CastReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["cutCellsBand", "CutCellsReport", "advectPoints","AdvectPointsReport", "correctField", "CorrectReport", "seedParticles", "reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "castRays", "CastReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -991,6 +995,71 @@ def measureBand(phi, mask, nx: int, ny: int, nz: int, dx: float, xLo, iso: float
     M = [float(v) for v in M]
     over = lambda num, den: tuple(v / den if den != 0.0 else float("nan") for v in num)
     return MeasureReport(M[0], M[1], over(M[2:5], M[1]), over(M[5:8], M[0]), M[8], *(int(v) for v in info))
+
+
+class CutCellsReport(NamedTuple):
+    """What lsf_cut_cells_band reports (include/lsf.h): the volume of the body over the list cells, the smallest stored fraction of
+    a cut cell (+inf without one) and info[0..4].  `open` > 0: a cut cell has a face neighbour outside the list, whose lower-face
+    aperture (this cell's upper one) the caller therefore lacks."""
+    volume: float
+    vof_min: float
+    cells: int
+    cut: int
+    full: int
+    open: int
+    clamped: int
+
+
+def cutCellsBand(phi, mask, nx: int, ny: int, nz: int, dx: float, iso: float = 0.0, vof=None, aperture=None, area_vector=None) -> CutCellsReport:
+    """Volume fraction, lower-face apertures and surface area vector of every cell of `mask`, for the body phi < iso
+    (include/lsf.h: lsf_cut_cells_band): the cell a list point names is cut by the triangles extractSurface would emit for it.
+
+    mask: int32, phi's layout and kind; the interior points where it is 1 are the list.  vof: a field of phi's layout and kind that
+    receives the fraction of each list cell inside the body; aperture: a 3-tuple (ax, ay, az) of such fields for the open fractions
+    of the cell's lower faces; area_vector: a 3-tuple (bx, by, bz) for the surface's outward area vector in units of dx^2.  Each is
+    written at list points only and may be left out; the report's volume is always formed.  phi and mask are read only.  All
+    arrays are numpy arrays (host seam) or all are torch CUDA tensors (device seam, on the tensor's current stream).
+    """
+    if mask is None:
+        raise ValueError("mask (int32) must be a field of phi's shape")
+    dx, iso = float(dx), float(iso)
+    if not (np.isfinite(dx) and dx > 0.0):
+        raise ValueError("dx must be finite and > 0")
+    if not np.isfinite(iso):
+        raise ValueError("iso must be finite")
+    outs = [] if vof is None else [("vof", vof)]
+    for name, group, parts in (("aperture", aperture, ("ax", "ay", "az")), ("area_vector", area_vector, ("bx", "by", "bz"))):
+        if group is None:
+            continue
+        if not isinstance(group, (tuple, list)) or len(group) != 3 or any(a is None for a in group):
+            raise ValueError(f"{name} must be a 3-tuple of fields of phi's shape")
+        outs += list(zip(parts, group))
+    dev = _is_torch(phi)
+    if any(_is_torch(a) != dev for _, a in outs + [("mask", mask)]):
+        raise TypeError("phi, mask and the outputs must all be numpy arrays or all be CUDA tensors")
+    if dev:
+        import torch
+
+        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
+        if any(a.device != phi.device for _, a in outs + [("mask", mask)]):
+            raise ValueError("phi, mask and the outputs must live on one device")
+        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+    else:
+        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
+        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+    p = ptr(phi, "phi")
+    o = {n: ptr(a, n) for n, a in outs}
+    lib = _lib.load()
+    tot = np.zeros(2, dtype=np.float64)  # volume, vof_min
+    info = np.zeros(_lib.LSF_CUT_INFO_LEN, dtype=np.int64)
+    args = (p, m, nx, ny, nz, dx, iso, *(o.get(n) for n in ("vof", "ax", "ay", "az", "bx", "by", "bz")), tot.ctypes.data,
+            tot.ctypes.data + 8, info.ctypes.data)
+    if dev:
+        rc = lib.lsf_cut_cells_band_device(*args, _stream_and_device(phi))
+    else:
+        rc = lib.lsf_cut_cells_band(*args)
+    _lib.check(rc)
+    return CutCellsReport(float(tot[0]), float(tot[1]), *(int(v) for v in info))
 
 
 class LabelReport(NamedTuple):
