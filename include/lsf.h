@@ -1255,6 +1255,78 @@ int lsf_correct_field_device(double *d_phi, const int32_t *d_mask, int nx, int n
                              const double *d_pts, const double *d_rad, int npts, double slack, int32_t *d_status, double *change,
                              int64_t info[LSF_CORRECT_INFO_LEN], void *stream);
 
+/* ---- the maintenance of the marker population: keep, drop, re-radius and top up, on the device ----------
+ * No reference counterpart.  The reseeding step of the particle level set (Enright et al. 2002) as one call: the old markers are
+ * classified against phi as it is now, the kept ones get their radius refreshed and are counted per cell, every under-populated
+ * cell next to the surface is topped up to per_cell with new markers attracted to a random target level, and one compacted set
+ * comes back.  With npts == 0 it seeds from scratch.  The call pattern is "reseed and keep, then copy out", exactly as
+ * lsf_extract_surface / lsf_extract_get: the call returns nout, the caller allocates, lsf_reseed_get fills the arrays and
+ * releases the kept result; every call first releases an un-fetched result, a failing call keeps nothing, a get without a result
+ * is LSF_ERR_INVALID, lsf_release_workspace drops the result.  phi, mask, pts and rad are inputs only; mask, status and info may
+ * be NULL, src_out may be NULL in the get; xLo, nout and info are host memory on both seams.  With npts == 0 pts, rad and status
+ * are ignored and may be NULL.
+ *   arrays   pts, pts_out are REAL a(n,3) in Fortran order; rad has npts entries, the side in its sign and the radius in fabs, as
+ *            for lsf_correct_field; status has npts entries; rad_out and src_out have nout.
+ *   exact    every expression is evaluated left to right as written, without contraction, with IEEE / and sqrt:
+ *            tests/reseed_ref.py is the yardstick bit for bit.  One arithmetic, no mode word.
+ *   old      per old marker, in the precedence of lsf_correct_field: rad not finite or == 0: LSF_RESEED_BADRADIUS.  Not INSIDE by
+ *            the locate of lsf_sample_points: OUTSIDE.  Under a mask, a corner of its cell not IN: OFFBAND.  val, the LINEAR value
+ *            there, not finite: NONFINITE.  fabs(val) > band*dx: FAR.  Otherwise KEPT: s = rad < 0 ? -1. : 1.;
+ *            rad' = s*fmin(fmax(s*val, rmin*dx), rmax*dx) (an escaped marker gets the smallest radius, as in Enright); its
+ *            position is returned bit for bit; it adds 1 to count[c] of its cell c, the i0 of locate (an integer sum).
+ *   cells    a cell is ELIGIBLE where all 8 corners have fabs(phi) < band*dx and, under a mask, are IN (the rule of seedParticles
+ *            of the Python package); need[c] = max(per_cell - count[c], 0) there, 0 elsewhere.
+ *   draws    candidate (c, j), 0 <= j < need[c]; p = i + (nx+1)*(j_c + (ny+1)*k) the index of the cell's lower corner, 64 bits.
+ *            For d = 0..3, all mod 2^64: ctr = (p*4096 + j)*4 + d; z = seed + 0x9E3779B97F4A7C15*(ctr + 1);
+ *            z = (z ^ (z >> 30))*0xBF58476D1CE4E5B9; z = (z ^ (z >> 27))*0x94D049BB133111EB; z = z ^ (z >> 31);
+ *            u_d = (double)(z >> 11)*2^-53 (the splitmix64 finaliser).  x_A = xLo[A] + ((double)c_A + u_A)*dx.
+ *   attract  v0 is the sample at x in the caller's order by the rules of lsf_sample_points (joint cubic rule, linear fallback, band
+ *            rule); not OK or not finite: rejected.  s = v0 < 0 ? -1. : 1.; goal = s*((rmin + (band - rmin)*u_3)*dx).  Then the
+ *            foot iteration of lsf_sample_points, word for word, with iso replaced by goal, the caller's iters and tol, y starting
+ *            at x; any end status but OK rejects.  vl is the LINEAR value at the final y (lsf_correct_field classifies with it);
+ *            accepted iff that sample is OK, fabs(vl) >= rmin*dx, fabs(vl) <= band*dx and (vl < 0 ? -1. : 1.) == s;
+ *            rad = s*fmin(fmax(fabs(vl), rmin*dx), rmax*dx).
+ *   output   the KEPT markers in the caller's order with src = their 1-based input position, then the accepted candidates in
+ *            ascending (p, j) with src = 0; nout is the total.  The candidates depend on the input markers only through the
+ *            integer counts: the new markers are a function of the SET of input markers, never of their order.  A caller varies
+ *            seed from reseed to reseed: the same seed redraws the same offsets in a cell.
+ *   info     [0..5] the six status counts (they add up to npts); [6] eligible cells; [7] candidates; [8] accepted; [9] rejected
+ *            before or during the attraction; [10] rejected by the final range/side test ([8]+[9]+[10] == [7]); [11] cells with
+ *            count > per_cell; [12] the largest count; [13] kept markers with s*val < 0.  nout == [0] + [8].  status, nout and
+ *            info are written on LSF_OK only.
+ *   errors   LSF_ERR_INVALID, all detected before anything is kept or written: a NULL phi, xLo or nout; npts < 0, or npts > 0 with
+ *            a NULL pts or rad; a dimension < 1 or more than 2^31 - 1 points; dx or xLo not finite, dx <= 0; per_cell outside
+ *            1..LSF_RESEED_MAX_PER_CELL; rmin, rmax or band not finite, or not 0 < rmin <= rmax, or not rmin < band; an unknown
+ *            order; iters outside 1..LSF_RESEED_MAX_ITERS; tol not finite or < 0; npts + candidates > 2^31 - 1 (found after the
+ *            count, the number in lsf_last_error()); status sharing a byte with an input.  No device: LSF_ERR_NO_DEVICE with
+ *            nothing written.
+ *   seams    phi goes through its twin as lsf_sample_points takes it, the mask as lsf_curvature_band takes it; pts and rad are
+ *            staged per call, as lsf_correct_field does.  lsf_reseed_points_device returns after the stream is synchronised (the
+ *            host reads totals).
+ * Work: a launch per old marker, one per cell of the grid (of the list under a mask), three one-block scans, one lane per candidate,
+ * two emits; two or three synchronisations.  Workspace: 4 bytes per grid point and per cell looked at, 16 per old marker, 36 per
+ * candidate; the kept result has 36 bytes per marker.  Out of scope: thinning of over-full cells (info[11], info[12] report them;
+ * which markers to drop is a policy that needs a per-cell order), iso != 0, per-side quotas, sorting by brick, fp32, multi-GPU
+ * (DESIGN.md section 8). */
+#define LSF_RESEED_INFO_LEN 14
+#define LSF_RESEED_MAX_PER_CELL 4096
+#define LSF_RESEED_MAX_ITERS 64
+#define LSF_RESEED_KEPT 0 /* status[t] of INPUT marker t */
+#define LSF_RESEED_OUTSIDE 1
+#define LSF_RESEED_OFFBAND 2
+#define LSF_RESEED_NONFINITE 3
+#define LSF_RESEED_BADRADIUS 4
+#define LSF_RESEED_FAR 5
+int lsf_reseed_points(const double *phi, const int32_t *mask, int nx, int ny, int nz, double dx, const double xLo[3], const double *pts,
+                      const double *rad, int npts, int per_cell, double rmin, double rmax, double band, int order, int iters, double tol,
+                      uint64_t seed, int32_t *status, int *nout, int64_t info[LSF_RESEED_INFO_LEN]);
+int lsf_reseed_points_device(const double *d_phi, const int32_t *d_mask, int nx, int ny, int nz, double dx, const double xLo[3],
+                             const double *d_pts, const double *d_rad, int npts, int per_cell, double rmin, double rmax, double band,
+                             int order, int iters, double tol, uint64_t seed, int32_t *d_status, int *nout,
+                             int64_t info[LSF_RESEED_INFO_LEN], void *stream);
+int lsf_reseed_get(double *pts_out, double *rad_out, int32_t *src_out);
+int lsf_reseed_get_device(double *d_pts_out, double *d_rad_out, int32_t *d_src_out, void *stream);
+
 /* ---- connected components of the level set on the cells of a caller's mask ----------
  * No reference counterpart.  How many bodies there are, which cell belongs to which, and whether two have merged or one has pinched
  * off: the 6-connected components of the list cells on either side of phi = iso, a pure graph problem on the cell list every band

@@ -36,6 +36,8 @@ LSF_ADVECT_POINTS_INFO_LEN, LSF_ADVECT_POINTS_MAX_STEPS = 6, 4096  # include/lsf
 LSF_POINTS_OK, LSF_POINTS_OUTSIDE, LSF_POINTS_OFFBAND, LSF_POINTS_FLAT = 0, 1, 2, 3  # ... its status[t]
 LSF_CORRECT_INFO_LEN = 7  # include/lsf.h: lsf_correct_field
 LSF_CORRECT_INPLACE, LSF_CORRECT_ESCAPED, LSF_CORRECT_OUTSIDE, LSF_CORRECT_OFFBAND, LSF_CORRECT_NONFINITE, LSF_CORRECT_BADRADIUS = 0, 1, 2, 3, 4, 5
+LSF_RESEED_INFO_LEN, LSF_RESEED_MAX_PER_CELL, LSF_RESEED_MAX_ITERS = 14, 4096, 64  # include/lsf.h: lsf_reseed_points
+LSF_RESEED_KEPT, LSF_RESEED_OUTSIDE, LSF_RESEED_OFFBAND, LSF_RESEED_NONFINITE, LSF_RESEED_BADRADIUS, LSF_RESEED_FAR = 0, 1, 2, 3, 4, 5
 LSF_LABEL_INSIDE, LSF_LABEL_OUTSIDE, LSF_LABEL_BOTH = 0, 1, 2  # include/lsf.h: lsf_label_band
 LSF_LABEL_COMP_LEN, LSF_LABEL_INFO_LEN = 10, 8
 LSF_EXTEND_INFO_LEN = 3  # include/lsf.h: lsf_extend_field
@@ -147,6 +149,12 @@ SIGNATURES = {
                                   POINTER(c_double), c_void_p]),
     "lsf_correct_field_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,
                                          POINTER(c_double), c_void_p, c_void_p]),
+    "lsf_reseed_points": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double,
+                                  c_double, c_int, c_int, c_double, ctypes.c_uint64, c_void_p, POINTER(c_int), c_void_p]),
+    "lsf_reseed_points_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                                         c_double, c_double, c_int, c_int, c_double, ctypes.c_uint64, c_void_p, POINTER(c_int), c_void_p, c_void_p]),
+    "lsf_reseed_get": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "lsf_reseed_get_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsf_label_band": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int,
                                POINTER(ctypes.c_int64), c_void_p]),
     "lsf_label_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int,

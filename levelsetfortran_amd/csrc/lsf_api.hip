@@ -40,6 +40,7 @@
 #include "lsf_cast_rays.hpp"
 #include "lsf_advect_points.hpp"
 #include "lsf_correct_field.hpp"
+#include "lsf_reseed_points.hpp"
 #include "lsf_label_band.hpp"
 
 using namespace lsf;
@@ -197,7 +198,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_CR_Q, S_CR_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_AP_IO, S_CF_IO, S_CF_PLUS, S_CF_MINUS, S_CF_CTL, S_CC_VOF, S_CC_AX, S_CC_AY, S_CC_AZ, S_CC_BX, S_CC_BY, S_CC_BZ, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_CR_Q, S_CR_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_AP_IO, S_CF_IO, S_CF_PLUS, S_CF_MINUS, S_CF_CTL, S_CC_VOF, S_CC_AX, S_CC_AY, S_CC_AZ, S_CC_BX, S_CC_BY, S_CC_BZ, S_RS_COUNT, S_RS_RANK, S_RS_OLD, S_RS_SCAN, S_RS_CTL, S_RS_CAND, S_RS_IO, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -756,6 +757,7 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_sample_points.hpp"
 #include "lsf_host_cast_rays.hpp"
 #include "lsf_host_points.hpp"
+#include "lsf_host_reseed.hpp"
 
 #include "lsf_host_label_band.hpp"
 
@@ -1196,6 +1198,7 @@ int lsf_release_workspace(void)
     Ctx& c = ctx();
     HIPCHK(hipDeviceSynchronize());
     extract_drop(); // an un-fetched lsf_extract_surface result of this thread
+    reseed_drop();  // ... and an un-fetched lsf_reseed_points result
     {   // lazy twins: the host copies they stand for are brought up to date before the device copies go
         struct { Twin* t; Slot s; } all[] = {{&c.twin_phi, S_HPHI}, {&c.twin_nb, S_HNB}, {&c.twin_sb, S_HSB}, {&c.twin_snap, S_SNAP}};
         for (auto& e : all) {
@@ -2024,6 +2027,66 @@ int lsf_correct_field(double* phi, const int32_t* mask, int nx, int ny, int nz, 
     }
     if (status) HIPCHK(hipMemcpy(status, d_status, np * sizeof(int32_t), hipMemcpyDeviceToHost));
     return twin_out(c, c.twin_phi, S_HPHI, phi, n * sizeof(double));
+}
+
+int lsf_reseed_points_device(const double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, const double xLo[3], const double* d_pts,
+                             const double* d_rad, int npts, int per_cell, double rmin, double rmax, double band, int order, int iters, double tol,
+                             uint64_t seed, int32_t* d_status, int* nout, int64_t info[LSF_RESEED_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_reseed_points_device");
+    reseed_drop(); // every call begins by releasing an un-fetched result
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = reseed_points_args_ok(d_phi, d_mask, nx, ny, nz, dx, xLo, d_pts, d_rad, npts, per_cell, rmin, rmax, band, order, iters, tol, d_status, nout)))
+        return rc;
+    return reseed_core(d_phi, d_mask, nx, ny, nz, dx, xLo, d_pts, d_rad, npts, per_cell, rmin, rmax, band, order, iters, tol, seed,
+                       npts ? d_status : nullptr, nout, info, (hipStream_t)stream);
+}
+
+int lsf_reseed_points(const double* phi, const int32_t* mask, int nx, int ny, int nz, double dx, const double xLo[3], const double* pts,
+                      const double* rad, int npts, int per_cell, double rmin, double rmax, double band, int order, int iters, double tol, uint64_t seed,
+                      int32_t* status, int* nout, int64_t info[LSF_RESEED_INFO_LEN])
+{
+    Trace trace_("lsf_reseed_points");
+    reseed_drop();
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = reseed_points_args_ok(phi, mask, nx, ny, nz, dx, xLo, pts, rad, npts, per_cell, rmin, rmax, band, order, iters, tol, status, nout))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1), np = (size_t)npts;
+    const int32_t* d_mask;
+    // pts, rad and status are staged per call in one slot, as lsf_correct_field stages them; status comes home on LSF_OK only
+    double *d_pts = nullptr, *d_rad = nullptr;
+    int32_t* d_status = nullptr;
+    if (np) {
+        if ((rc = ws(c.slot[S_RS_IO], np * (4 * sizeof(double) + sizeof(int32_t))))) return rc;
+        d_pts = (double*)c.slot[S_RS_IO].p, d_rad = d_pts + 3 * np;
+        d_status = status ? (int32_t*)(d_pts + 4 * np) : nullptr;
+        HIPCHK(hipMemcpy(d_pts, pts, 3 * np * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_rad, rad, np * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // phi is an input only, as lsf_sample_points takes it
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    int no = 0;
+    if ((rc = reseed_core((const double*)c.slot[S_HPHI].p, d_mask, nx, ny, nz, dx, xLo, d_pts, d_rad, npts, per_cell, rmin, rmax, band, order, iters,
+                          tol, seed, d_status, &no, info, nullptr)))
+        return rc;
+    if (d_status) {
+        const hipError_t e = hipMemcpy(status, d_status, np * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            reseed_drop();
+            return fail(LSF_ERR_HIP, std::string("lsf_reseed_points: ") + hipGetErrorString(e));
+        }
+    }
+    *nout = no;
+    return LSF_OK;
+}
+
+int lsf_reseed_get(double* pts_out, double* rad_out, int32_t* src_out) { return reseed_get(pts_out, rad_out, src_out, false, nullptr); }
+
+int lsf_reseed_get_device(double* d_pts_out, double* d_rad_out, int32_t* d_src_out, void* stream)
+{
+    return reseed_get(d_pts_out, d_rad_out, d_src_out, true, (hipStream_t)stream);
 }
 
 int lsf_label_band_device(const double* d_phi, const int32_t* d_mask, int32_t* d_label, int nx, int ny, int nz, double iso, int side, int max_passes,

@@ -52,6 +52,9 @@
 !                [,u,v,w,phi,speed,mask])                the interpolant of samplePoints (include/lsf.h: lsf_advect_points)
 !   correctField(phi,nx,ny,nz,dx,xLo,pts,rad,npts,       no reference counterpart: the correction of the particle level set, phi
 !                slack,status,change[,mask])             rebuilt around escaped markers (include/lsf.h: lsf_correct_field)
+!   reseedPoints(phi,nx,ny,nz,dx,xLo,pts,rad,npts,per_cell,rmin,rmax,band,order,iters,tol,seed,status,nout[,mask])
+!   reseedGet(pts_out,rad_out,src_out,nout)              no reference counterpart: the marker population kept, dropped, re-radiused
+!                                                        and topped up on the device (include/lsf.h: lsf_reseed_points)
 !   labelBand(phi,mask,label,nx,ny,nz,iso,side,ncomp)    no reference counterpart: the connected components of the cells with
 !                                                        mask == 1 on either side of phi = iso (include/lsf.h: lsf_label_band)
 !   extendFieldBand(q,phi,mask,nx,ny,nz,dx,band)         no reference counterpart: extendField on the cells with mask == 1
@@ -133,6 +136,8 @@ PUBLIC :: samplePoints
 PUBLIC :: castRays
 PUBLIC :: advectPoints
 PUBLIC :: correctField
+PUBLIC :: reseedPoints
+PUBLIC :: reseedGet
 PUBLIC :: labelBand
 PUBLIC :: extendFieldBand
 PUBLIC :: extractSurface, stlWrite
@@ -448,6 +453,28 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: info(7)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_correct_field
+   ! int lsf_reseed_points(const double*,const int32_t*,int,int,int,double,const double[3],const double*,const double*,int,int,double,
+   !                       double,double,int,int,double,uint64_t,int32_t*,int*,int64_t[14])
+   FUNCTION lsf_reseed_points(phi,mask,nx,ny,nz,dx,xLo,pts,rad,npts,per_cell,rmin,rmax,band,order,iters,tol,seed,status,nout,info) &
+            BIND(C,NAME='lsf_reseed_points') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t, c_ptr
+      REAL(c_double), INTENT(IN) :: phi(*)
+      TYPE(c_ptr), VALUE :: mask             ! NULL: the whole grid
+      INTEGER(c_int), VALUE :: nx,ny,nz,npts,per_cell,order,iters
+      REAL(c_double), VALUE :: dx,rmin,rmax,band,tol
+      REAL(c_double), INTENT(IN) :: xLo(3),pts(*),rad(*)
+      INTEGER(c_int64_t), VALUE :: seed      ! the bits of a uint64_t, taken as they are
+      INTEGER(c_int), INTENT(OUT) :: status(*)
+      INTEGER(c_int), INTENT(OUT) :: nout
+      INTEGER(c_int64_t), INTENT(OUT) :: info(14)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_reseed_points
+   FUNCTION lsf_reseed_get(pts_out,rad_out,src_out) BIND(C,NAME='lsf_reseed_get') RESULT(rc)
+      IMPORT :: c_int, c_double
+      REAL(c_double), INTENT(OUT) :: pts_out(*),rad_out(*)
+      INTEGER(c_int), INTENT(OUT) :: src_out(*)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_reseed_get
    ! int lsf_extend_field_band(double*,const double*,const int32_t*,const int32_t*,int,int,int,double,double,int,int*,int64_t*,int,
    !                           int64_t[4])
    FUNCTION lsf_extend_field_band(q,phi,mask,known,nx,ny,nz,dx,band,max_passes,passes_done,changed_trace,trace_cap,info) &
@@ -1429,6 +1456,63 @@ PRINT*, " Correction: points changed ",info(7),", largest change ",change
 PRINT*
 
 END SUBROUTINE correctField
+
+!*************************************************************************************!
+! The maintenance of the marker population (include/lsf.h: lsf_reseed_points; no reference
+! counterpart): the old markers pts(npts,3), rad(npts) that are still usable are kept with
+! their radius refreshed, every cell next to the surface with fewer than per_cell of them
+! is topped up with new markers attracted to a random level on their own side, and the
+! compacted set is kept on the device: nout is its size, reseedGet copies it out.
+! npts = 0 seeds from scratch.  status(t) of the INPUT markers: 0 kept, 1 outside the grid,
+! 2 off the band, 3 non-finite phi, 4 bad radius, 5 farther than band*dx from the surface.
+! order: 0 linear, 1 cubic.  seed: INTEGER(c_int64_t), its bits taken as they are; vary it
+! from reseed to reseed.  phi is read only.  Prints the counts.
+!*************************************************************************************!
+SUBROUTINE reseedPoints(phi,nx,ny,nz,dx,xLo,pts,rad,npts,per_cell,rmin,rmax,band,order,iters,tol,seed,status,nout,mask)
+
+INTEGER,INTENT(IN) :: nx,ny,nz,per_cell,order,iters
+INTEGER*4,INTENT(IN) :: npts
+REAL,INTENT(IN) :: dx,xLo(3),rmin,rmax,band,tol
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: phi
+REAL,INTENT(IN) :: pts(npts,3),rad(npts)
+INTEGER(c_int64_t),INTENT(IN) :: seed
+INTEGER*4,INTENT(OUT) :: status(npts)
+INTEGER*4,INTENT(OUT) :: nout
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN),OPTIONAL,TARGET :: mask
+TYPE(c_ptr) :: pm
+INTEGER(c_int64_t) :: info(14)
+INTEGER(c_int) :: rc
+
+pm = c_null_ptr
+IF (PRESENT(mask)) pm = C_LOC(mask)
+info = 0
+nout = 0
+CALL lsf_set_mirror()
+rc = lsf_reseed_points(phi,pm,nx,ny,nz,dx,xLo,pts,rad,npts,per_cell,rmin,rmax,band,order,iters,tol,seed,status,nout,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_reseed_points',rc)
+PRINT*, " Reseed: markers in ",npts,", kept ",info(1),", outside ",info(2),", off the band ",info(3)
+PRINT*, " Reseed: non-finite ",info(4),", bad radius ",info(5),", far ",info(6)
+PRINT*, " Reseed: eligible cells ",info(7),", candidates ",info(8),", accepted ",info(9)
+PRINT*, " Reseed: over-full cells ",info(12),", largest count ",info(13),", markers out ",nout
+PRINT*
+
+END SUBROUTINE reseedPoints
+
+!*************************************************************************************!
+! The marker set kept by reseedPoints -> pts_out(nout,3), rad_out(nout), src_out(nout)
+! (the 1-based input position of a kept marker, 0 for a new one); the kept set is released.
+!*************************************************************************************!
+SUBROUTINE reseedGet(pts_out,rad_out,src_out,nout)
+
+INTEGER*4,INTENT(IN) :: nout
+REAL,INTENT(OUT) :: pts_out(nout,3),rad_out(nout)
+INTEGER*4,INTENT(OUT) :: src_out(nout)
+INTEGER(c_int) :: rc
+
+rc = lsf_reseed_get(pts_out,rad_out,src_out)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_reseed_get',rc)
+
+END SUBROUTINE reseedGet
 
 !*************************************************************************************!
 ! Order-8 gradients on the stencil band + node advection: set3d.f90:470-501 as one call

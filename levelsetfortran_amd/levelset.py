@@ -1512,6 +1512,99 @@ def seedParticles(phi, nx: int, ny: int, nz: int, dx: float, xLo, *, mask=None, 
     return np.asfortranarray(pts[keep]), np.sign(val) * np.clip(np.abs(val), rmin * dx, rmax * dx)
 
 
+class ReseedReport(NamedTuple):
+    """What lsf_reseed_points and lsf_reseed_get return (include/lsf.h): the marker set `pts` (nout, 3; Fortran-ordered), `rad` (nout)
+    and `src` (nout, int32: the 1-based position of a kept marker in the input, 0 for a new one), `status` of the INPUT markers (npts,
+    int32: 0 KEPT, 1 OUTSIDE, 2 OFFBAND, 3 NONFINITE, 4 BADRADIUS, 5 FAR) and `info`, the fourteen counts [the six statuses, eligible
+    cells, candidates, accepted, rejected before or during the attraction, rejected by the final test, cells with more than per_cell
+    kept markers, the largest count, kept markers on the wrong side]."""
+    pts: object
+    rad: object
+    src: object
+    status: object
+    info: tuple
+
+
+def reseedParticles(phi, nx: int, ny: int, nz: int, dx: float, xLo, pts=None, rad=None, *, mask=None, per_cell: int = 16, rmin: float = 0.1,
+                    rmax: float = 0.5, band: float = 3.0, order: str = "cubic", iters: int = 4, tol: float = 1e-3, seed: int = 0) -> ReseedReport:
+    """The maintenance of the marker population on the device (include/lsf.h: lsf_reseed_points): the old markers (pts, rad) that are
+    still usable -- inside the grid, on the band, within band * dx of the surface, with a sound radius -- are kept with their radius
+    refreshed, every cell next to the surface that holds fewer than per_cell of them is topped up with new markers attracted to a
+    random level between rmin * dx and band * dx on their own side, and one compacted set comes back: the kept markers in the
+    caller's order, then the new ones.  Without pts and rad it seeds from scratch.
+
+    Vary `seed` from reseed to reseed (the step number will do): the same seed redraws the same offsets in a cell.  Over-full cells
+    are reported (info[11], info[12]) and left alone.  Numpy in gives numpy out (host seam); CUDA tensors in give CUDA tensors out
+    (device seam, on the tensor's current stream).
+    """
+    lo, dx = _points_common(nx, ny, nz, dx, xLo)
+    per_cell, iters, seed = int(per_cell), int(iters), int(seed)
+    rmin, rmax, band, tol = float(rmin), float(rmax), float(band), float(tol)
+    if order not in _SAMPLE_ORDERS:
+        raise ValueError("order must be 'linear' or 'cubic'")
+    if not 1 <= per_cell <= _lib.LSF_RESEED_MAX_PER_CELL:
+        raise ValueError(f"per_cell must be in 1..{_lib.LSF_RESEED_MAX_PER_CELL}")
+    if not 1 <= iters <= _lib.LSF_RESEED_MAX_ITERS:
+        raise ValueError(f"iters must be in 1..{_lib.LSF_RESEED_MAX_ITERS}")
+    if not (np.isfinite(rmin) and np.isfinite(rmax) and np.isfinite(band) and 0.0 < rmin <= rmax and rmin < band):
+        raise ValueError("0 < rmin <= rmax and rmin < band are required, all finite")
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError("tol must be finite and >= 0")
+    if (pts is None) != (rad is None):
+        raise ValueError("pts and rad are given together")
+    if pts is not None and pts.shape[0] == 0:
+        pts = rad = None
+    dev = _is_torch(phi)
+    others = tuple(a for a in (pts, rad, mask) if a is not None)
+    if any(_is_torch(a) != dev for a in others):
+        raise TypeError("phi, mask, pts and rad must all be numpy arrays or all be CUDA tensors")
+    npts = 0
+    if pts is not None:
+        npts = _points_layout(pts, dev)
+        if tuple(rad.shape) != (npts,):
+            raise ValueError("rad must have shape (npts,)")
+    lib = _lib.load()
+    info = np.zeros(_lib.LSF_RESEED_INFO_LEN, dtype=np.int64)
+    nout = ctypes.c_int(0)
+    useed = ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF)
+    if dev:
+        import torch
+
+        if any(a.device != phi.device for a in others):
+            raise ValueError("phi, mask, pts and rad must live on one device")
+        if rad is not None and (rad.dtype != torch.float64 or not rad.is_contiguous()):
+            raise TypeError("rad must be a contiguous float64 CUDA tensor")
+        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
+        m = None if mask is None else _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
+        status = torch.empty(npts, dtype=torch.int32, device=phi.device)
+        st = _stream_and_device(phi)
+        _lib.check(lib.lsf_reseed_points_device(p, m, nx, ny, nz, dx, lo.ctypes.data, pts.data_ptr() if npts else None,
+                                                rad.data_ptr() if npts else None, npts, per_cell, rmin, rmax, band, _SAMPLE_ORDERS[order], iters,
+                                                tol, useed, status.data_ptr() if npts else None, ctypes.byref(nout), info.ctypes.data, st))
+        n = nout.value
+        # (n,3) in Fortran order: the transpose of a contiguous (3,n)
+        out = torch.empty((3, n), dtype=torch.float64, device=phi.device)
+        orad = torch.empty(n, dtype=torch.float64, device=phi.device)
+        src = torch.empty(n, dtype=torch.int32, device=phi.device)
+        _lib.check(lib.lsf_reseed_get_device(out.data_ptr() if n else None, orad.data_ptr() if n else None, src.data_ptr() if n else None, st))
+        out = out.t()
+    else:
+        if rad is not None and (not isinstance(rad, np.ndarray) or rad.dtype != np.float64 or not rad.flags.c_contiguous):
+            raise TypeError("rad must be a contiguous float64 numpy array")
+        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
+        m = None if mask is None else _host_ptr(mask, np.int32, nx, ny, nz, "mask")
+        status = np.zeros(npts, dtype=np.int32)
+        _lib.check(lib.lsf_reseed_points(p, m, nx, ny, nz, dx, lo.ctypes.data, pts.ctypes.data if npts else None, rad.ctypes.data if npts else None,
+                                         npts, per_cell, rmin, rmax, band, _SAMPLE_ORDERS[order], iters, tol, useed,
+                                         status.ctypes.data if npts else None, ctypes.byref(nout), info.ctypes.data))
+        n = nout.value
+        out = np.zeros((n, 3), dtype=np.float64, order="F")
+        orad = np.zeros(n, dtype=np.float64)
+        src = np.zeros(n, dtype=np.int32)
+        _lib.check(lib.lsf_reseed_get(out.ctypes.data if n else None, orad.ctypes.data if n else None, src.ctypes.data if n else None))
+    return ReseedReport(out, orad, src, status, tuple(int(v) for v in info))
+
+
 class SurfaceInfo(NamedTuple):
     """The counts of lsf_extract_surface (include/lsf.h: info[0..3])."""
     nodes: int
