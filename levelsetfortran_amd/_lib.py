@@ -63,7 +63,7 @@ class LsfNaNError(LsfError):
 
 _dp, _ip, _i3 = POINTER(c_double), POINTER(c_int32), POINTER(c_int * 3)
 
-# name -> (restype, argtypes); every symbol include/lsf.h declares
+# name -> (restype, argtypes); every symbol include/lsf.h declares (the _device forms of DEVICE_TWINS are added below the table)
 SIGNATURES = {
     "lsf_version": (c_int, []),
     "lsf_last_error": (ctypes.c_char_p, []),
@@ -86,100 +86,51 @@ SIGNATURES = {
                                        c_int, POINTER(c_int), c_void_p, c_int, c_void_p]),
     "lsf_minmax": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double,
                            c_double, c_int, POINTER(c_int), c_void_p, c_int]),
-    "lsf_minmax_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double,
-                                  c_double, c_int, POINTER(c_int), c_void_p, c_int, c_void_p]),
     "lsf_narrowband": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double]),
-    "lsf_narrowband_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p]),
     "lsf_phi0": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                          c_void_p, c_int]),
-    "lsf_phi0_device": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                c_void_p, c_int, c_void_p]),
     "lsf_mesh_check": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, POINTER(c_double)]),
     "lsf_mesh_distance": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p, c_int, c_double,
                                   c_int, c_void_p]),
-    "lsf_mesh_distance_device": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                         c_double, c_int, c_void_p, c_void_p]),
     "lsf_distance_fill": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p, c_int,
                                   POINTER(ctypes.c_int64)]),
-    "lsf_distance_fill_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p,
-                                         c_int, POINTER(ctypes.c_int64), c_void_p]),
     "lsf_extend_field": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p, c_int,
                                  c_void_p]),
-    "lsf_extend_field_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int), c_void_p,
-                                        c_int, c_void_p, c_void_p]),
     "lsf_extend_field_band": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, POINTER(c_int),
                                       c_void_p, c_int, c_void_p]),
-    "lsf_extend_field_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int,
-                                             POINTER(c_int), c_void_p, c_int, c_void_p, c_void_p]),
     "lsf_advect_field": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_int, c_int,
                                  POINTER(c_int), POINTER(c_double), c_void_p, c_int]),
-    "lsf_advect_field_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_int,
-                                        c_int, POINTER(c_int), POINTER(c_double), c_void_p, c_int, c_void_p]),
     "lsf_advect_field_band": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int,
                                       c_int, c_int, POINTER(c_int), POINTER(c_double), c_void_p, c_int, c_void_p, POINTER(c_double)]),
-    "lsf_advect_field_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double,
-                                             c_int, c_int, c_int, POINTER(c_int), POINTER(c_double), c_void_p, c_int, c_void_p,
-                                             POINTER(c_double), c_void_p]),
     "lsf_curvature_band": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p,
                                    POINTER(c_double)]),
-    "lsf_curvature_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p,
-                                          POINTER(c_double), c_void_p]),
     "lsf_measure_band": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, c_void_p, c_void_p]),
-    "lsf_measure_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, c_void_p, c_void_p,
-                                        c_void_p]),
     "lsf_cut_cells_band": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "lsf_cut_cells_band_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsf_sample_points": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
                                   c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "lsf_sample_points_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int, c_double,
-                                         c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsf_cast_rays": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
                               c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p]),
-    "lsf_cast_rays_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                     c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsf_advect_points": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int,
                                   c_int, c_int, c_double, c_int, c_void_p, POINTER(c_double), c_void_p]),
-    "lsf_advect_points_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
-                                         c_int, c_int, c_int, c_double, c_int, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
     "lsf_correct_field": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,
                                   POINTER(c_double), c_void_p]),
-    "lsf_correct_field_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,
-                                         POINTER(c_double), c_void_p, c_void_p]),
     "lsf_reseed_points": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double,
                                   c_double, c_int, c_int, c_double, ctypes.c_uint64, c_void_p, POINTER(c_int), c_void_p]),
-    "lsf_reseed_points_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
-                                         c_double, c_double, c_int, c_int, c_double, ctypes.c_uint64, c_void_p, POINTER(c_int), c_void_p, c_void_p]),
     "lsf_reseed_get": (c_int, [c_void_p, c_void_p, c_void_p]),
-    "lsf_reseed_get_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsf_label_band": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int,
                                POINTER(ctypes.c_int64), c_void_p]),
-    "lsf_label_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int,
-                                      POINTER(ctypes.c_int64), c_void_p, c_void_p]),
     "lsf_evolve_band": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_int,
                                 c_int, c_double, c_int, c_int, c_double, c_int, POINTER(c_int), POINTER(c_double), c_void_p, c_int, c_void_p,
                                 POINTER(c_double)]),
-    "lsf_evolve_band_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int,
-                                       c_int, c_int, c_double, c_int, c_int, c_double, c_int, POINTER(c_int), POINTER(c_double), c_void_p, c_int,
-                                       c_void_p, POINTER(c_double), c_void_p]),
     "lsf_evolve_band_curv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int,
                                      c_int, c_int, c_double, c_int, c_int, c_double, c_int, c_double, c_double, POINTER(c_int), POINTER(c_double),
                                      POINTER(c_double), c_void_p, c_int, c_void_p, POINTER(c_double)]),
-    "lsf_evolve_band_curv_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double,
-                                            c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_int, c_double, c_double, POINTER(c_int),
-                                            POINTER(c_double), POINTER(c_double), c_void_p, c_int, c_void_p, POINTER(c_double), c_void_p]),
     "lsf_extract_surface": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, POINTER(c_int), POINTER(c_int), c_void_p]),
-    "lsf_extract_surface_device": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, POINTER(c_int), POINTER(c_int), c_void_p,
-                                           c_void_p]),
     "lsf_extract_get": (c_int, [c_void_p, c_void_p]),
-    "lsf_extract_get_device": (c_int, [c_void_p, c_void_p, c_void_p]),
     "lsf_stl_write": (c_int, [ctypes.c_char_p, c_void_p, c_int, c_void_p, c_int]),
     "lsf_advect_nodes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_int]),
-    "lsf_advect_nodes_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int,
-                                        c_int, c_void_p]),
     "lsf_mirror": (c_int, [c_int]),
     "lsf_mirror_sync": (c_int, [c_void_p]),
     "lsf_mirror_forget": (c_int, [c_void_p]),
@@ -230,6 +181,16 @@ SIGNATURES = {
     "lsf_pack_box_f32": (c_int, [c_void_p, POINTER(LsfBox), c_int * 3, c_int * 3, c_void_p, c_void_p]),
     "lsf_unpack_box_f32": (c_int, [c_void_p, POINTER(LsfBox), c_int * 3, c_int * 3, c_void_p, c_void_p]),
 }
+
+# The calls that exist on both seams: NAME_device takes NAME's arguments and the stream.  (The three reinit calls do not belong here:
+# their device forms, written out above, take phiS -- and lsf_reinit_device first_raster -- as well.)
+DEVICE_TWINS = ("lsf_minmax", "lsf_narrowband", "lsf_phi0", "lsf_mesh_distance", "lsf_distance_fill", "lsf_extend_field",
+                "lsf_extend_field_band", "lsf_advect_field", "lsf_advect_field_band", "lsf_curvature_band", "lsf_measure_band",
+                "lsf_cut_cells_band", "lsf_sample_points", "lsf_cast_rays", "lsf_advect_points", "lsf_correct_field", "lsf_reseed_points",
+                "lsf_reseed_get", "lsf_label_band", "lsf_evolve_band", "lsf_evolve_band_curv", "lsf_extract_surface", "lsf_extract_get",
+                "lsf_advect_nodes")
+for _name in DEVICE_TWINS:
+    SIGNATURES[_name + "_device"] = (SIGNATURES[_name][0], SIGNATURES[_name][1] + [c_void_p])
 
 _lib = None
 

@@ -78,8 +78,9 @@ from typing import List, NamedTuple, Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _seam
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
+from ._seam import Seam
 
 __all__ = ["cutCellsBand", "CutCellsReport", "advectPoints","AdvectPointsReport", "correctField", "CorrectReport", "seedParticles", "reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "castRays", "CastReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
@@ -113,48 +114,41 @@ class SweepReport:
         return out
 
 
-def _is_torch(x) -> bool:
-    return type(x).__module__.startswith("torch")
+_SCHEMES = {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}
+_ARITHS = {"strict": LSF_ARITH_STRICT, "fast": LSF_ARITH_FAST}
+_SAMPLE_ORDERS = {"linear": _lib.LSF_SAMPLE_LINEAR, "cubic": _lib.LSF_SAMPLE_CUBIC}
+_EXTEND_KINDS = ("numpy arrays (host seam)", "torch CUDA tensors (device seam)")
 
 
-def _npoints(nx: int, ny: int, nz: int) -> int:
-    return (nx + 1) * (ny + 1) * (nz + 1)
+def _sweep_report(rc, done, trace, tol, first_index, steady_msg, echo) -> SweepReport:
+    """The report of a sweep loop, echoed like the reference if asked for, then the library's verdict"""
+    n = done.value
+    rep = SweepReport(n, [float(v) for v in trace[:n]], bool(n and trace[n - 1] < tol))
+    if echo:
+        for ln in rep.lines(first_index, steady_msg):
+            print(ln)
+        print()
+        sys.stdout.flush()
+    _lib.check(rc)
+    return rep
 
 
-def _host_ptr(a: np.ndarray, dtype, nx, ny, nz, name: str) -> int:
-    if not isinstance(a, np.ndarray) or a.dtype != dtype:
-        raise TypeError(f"{name} must be a numpy array of {np.dtype(dtype).name}")
-    if a.ndim == 3:
-        if a.shape != (nx + 1, ny + 1, nz + 1) or not a.flags.f_contiguous:
-            raise ValueError(f"{name} must be Fortran-ordered with shape (nx+1, ny+1, nz+1) = {(nx+1, ny+1, nz+1)}")
-    elif a.ndim != 1 or a.size != _npoints(nx, ny, nz) or not a.flags.c_contiguous:
-        raise ValueError(f"{name} must have (nx+1)(ny+1)(nz+1) contiguous elements")
-    if not a.flags.writeable:
-        raise ValueError(f"{name} must be writeable (it is INTENT(INOUT) in the reference)")
-    return a.ctypes.data
+def _check_report(rc, rep):
+    """`rep` if the call succeeded; an LsfNaNError carries it as `.report` (the steps run, the NaN one included)"""
+    try:
+        _lib.check(rc)
+    except LsfNaNError as e:
+        e.report = rep
+        raise
+    return rep
 
 
-def _dev_ptr(t, torch_dtype, nx, ny, nz, name: str) -> int:
-    import torch
-
-    if not t.is_cuda or t.dtype != torch_dtype:
-        raise TypeError(f"{name} must be a CUDA tensor of {torch_dtype}")
-    if t.dim() == 3:
-        if tuple(t.shape) != (nz + 1, ny + 1, nx + 1):
-            raise ValueError(f"{name} must have shape (nz+1, ny+1, nx+1) (i is the unit-stride axis)")
-    elif t.dim() != 1 or t.numel() != _npoints(nx, ny, nz):
-        raise ValueError(f"{name} must have (nx+1)(ny+1)(nz+1) elements")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return t.data_ptr()
-
-
-def _stream_and_device(t):
-    import torch
-
-    lib = _lib.load()
-    _lib.check(lib.lsf_set_device(t.device.index or 0))
-    return torch.cuda.current_stream(t.device).cuda_stream
+def _transport_fields(velocity, speed):
+    """The (name, field) pairs that move phi in advectField and its band forms: u, v, w of a checked velocity, then the speed"""
+    if velocity is not None:
+        if not isinstance(velocity, (tuple, list)) or len(velocity) != 3 or any(c is None for c in velocity):
+            raise ValueError("velocity must be a 3-tuple (u, v, w) of fields")
+    return [(n, f) for n, f in zip("uvw", velocity or ())] + ([("speed", speed)] if speed is not None else [])
 
 
 def reinit(phi, gradPhi=None, gradPhiMag=None, nx: int = 0, ny: int = 0, nz: int = 0, iter: int = 0,
@@ -169,47 +163,29 @@ def reinit(phi, gradPhi=None, gradPhiMag=None, nx: int = 0, ny: int = 0, nz: int
     A float32 field (numpy or torch) selects the single-precision path of BASELINE configuration 5, which
     exists for order="jacobi", arith="fast" only (the reference is fp64; see include/lsf.h).
     """
-    lib = _lib.load()
     cap = int(iter) + 1
     trace = np.zeros(max(cap, 1), dtype=np.float64)
     done = ctypes.c_int(0)
     mode = mode_word(order, arith)
-    if _is_torch(phi):
-        import torch
-
-        f32 = phi.dtype == torch.float32
-        tdt = torch.float32 if f32 else torch.float64
-        p = _dev_ptr(phi, tdt, nx, ny, nz, "phi")
-        ps = _dev_ptr(phiS, tdt, nx, ny, nz, "phiS") if phiS is not None else None
-        st = _stream_and_device(phi)
-        if f32:  # single precision: Jacobi ordering, FAST arithmetic only (include/lsf.h)
+    s = Seam(phi, nx, ny, nz)
+    f32 = s.is_f32(phi)  # single precision: Jacobi ordering, FAST arithmetic only (include/lsf.h)
+    dtype = np.float32 if f32 else np.float64
+    p = s.field(phi, "phi", dtype)
+    head = (nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode)
+    tail = (ctypes.byref(done), trace.ctypes.data, cap)
+    if s.dev:  # the device forms take phiS, and the fp64 one first_raster, besides the stream
+        ps = s.optional(phiS, "phiS", dtype)
+        if f32:
             if first_raster != 0:
                 raise ValueError("first_raster has no meaning for the Jacobi ordering")
-            rc = lib.lsf_reinit_f32_device(p, ps, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode,
-                                           ctypes.byref(done), trace.ctypes.data, cap, st)
+            rc = _lib.load().lsf_reinit_f32_device(p, ps, *head, *tail, s.stream())
         else:
-            rc = lib.lsf_reinit_device(p, ps, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode,
-                                       int(first_raster), ctypes.byref(done), trace.ctypes.data, cap, st)
+            rc = _lib.load().lsf_reinit_device(p, ps, *head, int(first_raster), *tail, s.stream())
     else:
         if first_raster != 0 or phiS is not None:
             raise ValueError("first_raster / phiS are only available on the device seam")
-        if isinstance(phi, np.ndarray) and phi.dtype == np.float32:
-            p = _host_ptr(phi, np.float32, nx, ny, nz, "phi")
-            rc = lib.lsf_reinit_f32(p, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode,
-                                    ctypes.byref(done), trace.ctypes.data, cap)
-        else:
-            p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-            rc = lib.lsf_reinit(p, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode, ctypes.byref(done),
-                                trace.ctypes.data, cap)
-    n = done.value
-    rep = SweepReport(n, [float(v) for v in trace[:n]], bool(n and trace[n - 1] < tol))
-    if echo:
-        for ln in rep.lines(0, "  Distance function time integration has reached steady state "):
-            print(ln)
-        print()
-        sys.stdout.flush()
-    _lib.check(rc)
-    return rep
+        rc = s.call("lsf_reinit_f32" if f32 else "lsf_reinit", p, *head, *tail)
+    return _sweep_report(rc, done, trace, tol, 0, "  Distance function time integration has reached steady state ", echo)
 
 
 def reinitBand(phi, mask, nx: int, ny: int, nz: int, iter: int, dx: float, h: float, *, tol: float = REINIT_TOL,
@@ -223,53 +199,27 @@ def reinitBand(phi, mask, nx: int, ny: int, nz: int, iter: int, dx: float, h: fl
     makes a call continue an earlier one.  Make the mask wider than the band whose values are trusted: cells within three
     cells of its edge read frozen neighbours.  Raises LsfNaNError on a NaN RMS.
     """
-    lib = _lib.load()
     cap = int(iter) + 1
     trace = np.zeros(max(cap, 1), dtype=np.float64)
     done = ctypes.c_int(0)
     mode = mode_word("jacobi", arith)  # a raster order has no meaning on a list
-    if _is_torch(phi):
-        import torch
-
-        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-        ps = _dev_ptr(phiS, torch.float64, nx, ny, nz, "phiS") if phiS is not None else None
-        st = _stream_and_device(phi)
-        rc = lib.lsf_reinit_band_device(p, ps, m, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode,
-                                        ctypes.byref(done), trace.ctypes.data, cap, st)
+    s = Seam(phi, nx, ny, nz)
+    p, m = s.field(phi, "phi"), s.field(mask, "mask", np.int32)
+    args = (nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode, ctypes.byref(done), trace.ctypes.data, cap)
+    if s.dev:  # the device form takes phiS besides the stream
+        rc = _lib.load().lsf_reinit_band_device(p, s.optional(phiS, "phiS"), m, *args, s.stream())
     else:
         if phiS is not None:
             raise ValueError("phiS is only available on the device seam")
-        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-        rc = lib.lsf_reinit_band(p, m, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode, ctypes.byref(done),
-                                 trace.ctypes.data, cap)
-    n = done.value
-    rep = SweepReport(n, [float(v) for v in trace[:n]], bool(n and trace[n - 1] < tol))
-    if echo:
-        for ln in rep.lines(0, "  Distance function time integration has reached steady state "):
-            print(ln)
-        print()
-        sys.stdout.flush()
-    _lib.check(rc)
-    return rep
+        rc = s.call("lsf_reinit_band", p, m, *args)
+    return _sweep_report(rc, done, trace, tol, 0, "  Distance function time integration has reached steady state ", echo)
 
 
 def narrowBand(nx: int, ny: int, nz: int, dx: float, phi, phiNB, phiSB) -> None:
     """SUBROUTINE narrowBand (subs.f90:178-207): phiNB = |phi| < 4.1 dx, phiSB = |phi| < 8.1 dx."""
-    lib = _lib.load()
-    if _is_torch(phi):
-        import torch
-
-        st = _stream_and_device(phi)
-        rc = lib.lsf_narrowband_device(_dev_ptr(phi, torch.float64, nx, ny, nz, "phi"),
-                                       _dev_ptr(phiNB, torch.int32, nx, ny, nz, "phiNB"),
-                                       _dev_ptr(phiSB, torch.int32, nx, ny, nz, "phiSB"), nx, ny, nz, float(dx), st)
-    else:
-        rc = lib.lsf_narrowband(_host_ptr(phi, np.float64, nx, ny, nz, "phi"),
-                                _host_ptr(phiNB, np.int32, nx, ny, nz, "phiNB"),
-                                _host_ptr(phiSB, np.int32, nx, ny, nz, "phiSB"), nx, ny, nz, float(dx))
-    _lib.check(rc)
+    s = Seam(phi, nx, ny, nz)
+    _lib.check(s.call("lsf_narrowband", s.field(phi, "phi"), s.field(phiNB, "phiNB", np.int32), s.field(phiSB, "phiSB", np.int32),
+                      nx, ny, nz, float(dx)))
 
 
 def minmaxFlow(phi, phiNB, phiSB, nx: int, ny: int, nz: int, iter: int, dx: float, h1: float, *,
@@ -279,34 +229,14 @@ def minmaxFlow(phi, phiNB, phiSB, nx: int, ny: int, nz: int, iter: int, dx: floa
     phi, phiNB, phiSB are updated in place; the masks come back as the host would hold them after
     the loop (refreshed only on the non-exit path, set3d.f90:448-460).
     """
-    lib = _lib.load()
     cap = max(int(iter), 1)
     trace = np.zeros(cap, dtype=np.float64)
     done = ctypes.c_int(0)
     mode = mode_word(order, "strict")  # min/max has a single (exact) arithmetic
-    if _is_torch(phi):
-        import torch
-
-        st = _stream_and_device(phi)
-        rc = lib.lsf_minmax_device(_dev_ptr(phi, torch.float64, nx, ny, nz, "phi"),
-                                   _dev_ptr(phiNB, torch.int32, nx, ny, nz, "phiNB"),
-                                   _dev_ptr(phiSB, torch.int32, nx, ny, nz, "phiSB"), nx, ny, nz, int(iter),
-                                   float(dx), float(h1), float(tol), mode, ctypes.byref(done), trace.ctypes.data,
-                                   cap, st)
-    else:
-        rc = lib.lsf_minmax(_host_ptr(phi, np.float64, nx, ny, nz, "phi"),
-                            _host_ptr(phiNB, np.int32, nx, ny, nz, "phiNB"),
-                            _host_ptr(phiSB, np.int32, nx, ny, nz, "phiSB"), nx, ny, nz, int(iter), float(dx),
-                            float(h1), float(tol), mode, ctypes.byref(done), trace.ctypes.data, cap)
-    n = done.value
-    rep = SweepReport(n, [float(v) for v in trace[:n]], bool(n and trace[n - 1] < tol))
-    if echo:
-        for ln in rep.lines(1, "  Min/max time integration has reached steady state "):
-            print(ln)
-        print()
-        sys.stdout.flush()
-    _lib.check(rc)
-    return rep
+    s = Seam(phi, nx, ny, nz)
+    rc = s.call("lsf_minmax", s.field(phi, "phi"), s.field(phiNB, "phiNB", np.int32), s.field(phiSB, "phiSB", np.int32), nx, ny, nz,
+                int(iter), float(dx), float(h1), float(tol), mode, ctypes.byref(done), trace.ctypes.data, cap)
+    return _sweep_report(rc, done, trace, tol, 1, "  Min/max time integration has reached steady state ", echo)
 
 
 def phi0Init(phi, nx: int, ny: int, nz: int, dx: float, xLo, minX, maxX, surfX, surfElem) -> None:
@@ -317,20 +247,12 @@ def phi0Init(phi, nx: int, ny: int, nz: int, dx: float, xLo, minX, maxX, surfX, 
     1-based, as stlRead returns them (subs.f90:17-121); xLo/minX/maxX as the host computes them
     (set3d.f90:94-157).  Bit-identical to the reference.
     """
-    lib = _lib.load()
     sX = np.asfortranarray(surfX, dtype=np.float64)
     sE = np.asfortranarray(surfElem, dtype=np.int32)
     lo, mn, mx = (np.ascontiguousarray(v, dtype=np.float64) for v in (xLo, minX, maxX))
-    args = (nx, ny, nz, float(dx), lo.ctypes.data, mn.ctypes.data, mx.ctypes.data, sX.ctypes.data, sX.shape[0],
-            sE.ctypes.data, sE.shape[0])
-    if _is_torch(phi):
-        import torch
-
-        st = _stream_and_device(phi)
-        rc = lib.lsf_phi0_device(_dev_ptr(phi, torch.float64, nx, ny, nz, "phi"), *args, st)
-    else:
-        rc = lib.lsf_phi0(_host_ptr(phi, np.float64, nx, ny, nz, "phi"), *args)
-    _lib.check(rc)
+    s = Seam(phi, nx, ny, nz)
+    _lib.check(s.call("lsf_phi0", s.field(phi, "phi"), nx, ny, nz, float(dx), lo.ctypes.data, mn.ctypes.data, mx.ctypes.data, sX.ctypes.data,
+                      sX.shape[0], sE.ctypes.data, sE.shape[0]))
 
 
 class MeshInfo(NamedTuple):
@@ -374,28 +296,16 @@ def meshDistance(phi, nx: int, ny: int, nz: int, dx: float, xLo, surfX, surfElem
     see meshCheck).  Returns the counts of the call.  The field is clamped, not a distance everywhere: reinit takes it as
     its start and needs far fewer sweeps than from phi0Init's smeared sign.
     """
-    lib = _lib.load()
     sX, sE = _surface(surfX, surfElem)
-    lo = np.ascontiguousarray(xLo, dtype=np.float64)
-    if lo.shape != (3,):
-        raise ValueError("xLo must hold 3 values")
-    width, dx = float(width), float(dx)
+    lo = _seam.xlo(xLo, finite=False)
+    width = float(width)
     if not (np.isfinite(width) and width >= 1.5):
         raise ValueError("width must be finite and >= 1.5 (cells)")
-    if not (np.isfinite(dx) and dx > 0.0):
-        raise ValueError("dx must be > 0")
+    dx = _seam.positive(dx, "dx must be > 0")
     info = np.zeros(_lib.LSF_MESH_INFO_LEN, dtype=np.int64)
-    args = (nx, ny, nz, dx, lo.ctypes.data, sX.ctypes.data, sX.shape[0], sE.ctypes.data, sE.shape[0], width,
-            0 if signed else _lib.LSF_MESH_UNSIGNED, info.ctypes.data)
-    if _is_torch(phi):
-        import torch
-
-        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        st = _stream_and_device(phi)
-        rc = lib.lsf_mesh_distance_device(p, *args, st)
-    else:
-        rc = lib.lsf_mesh_distance(_host_ptr(phi, np.float64, nx, ny, nz, "phi"), *args)
-    _lib.check(rc)
+    s = Seam(phi, nx, ny, nz)
+    _lib.check(s.call("lsf_mesh_distance", s.field(phi, "phi"), nx, ny, nz, dx, lo.ctypes.data, sX.ctypes.data, sX.shape[0], sE.ctypes.data,
+                      sE.shape[0], width, 0 if signed else _lib.LSF_MESH_UNSIGNED, info.ctypes.data))
     return MeshInfo(*(int(v) for v in info))
 
 
@@ -421,25 +331,13 @@ def distanceFill(phi, nx: int, ny: int, nz: int, dx: float, *, band: Optional[fl
     """
     if (band is None) == (mask is None):
         raise ValueError("give exactly one of band= (cells; freezes |phi| < band*dx) and mask= (int32; freezes mask == 1)")
-    lib = _lib.load()
     cap = max(int(max_rounds), 1)
     trace = np.zeros(cap, dtype=np.int64)
     done = ctypes.c_int(0)
     frozen = ctypes.c_int64(0)
-    tail = (nx, ny, nz, float(dx), 0.0 if band is None else float(band), int(max_rounds), ctypes.byref(done), trace.ctypes.data, cap,
-            ctypes.byref(frozen))
-    if _is_torch(phi):
-        import torch
-
-        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask") if mask is not None else None
-        st = _stream_and_device(phi)
-        rc = lib.lsf_distance_fill_device(p, m, *tail, st)
-    else:
-        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask") if mask is not None else None
-        rc = lib.lsf_distance_fill(p, m, *tail)
-    _lib.check(rc)
+    s = Seam(phi, nx, ny, nz)
+    _lib.check(s.call("lsf_distance_fill", s.field(phi, "phi"), s.optional(mask, "mask", np.int32), nx, ny, nz, float(dx),
+                      0.0 if band is None else float(band), int(max_rounds), ctypes.byref(done), trace.ctypes.data, cap, ctypes.byref(frozen)))
     n = done.value
     changed = [int(v) for v in trace[:n]]
     return FillReport(n, changed, int(frozen.value), bool(n and changed[-1] == 0))
@@ -468,31 +366,15 @@ def extendField(q, phi, nx: int, ny: int, nz: int, dx: float, *, band: Optional[
     """
     if (band is None) == (mask is None):
         raise ValueError("give exactly one of band= (cells; freezes |phi| < band*dx) and mask= (int32; freezes mask == 1)")
-    if _is_torch(q) != _is_torch(phi) or (mask is not None and _is_torch(mask) != _is_torch(q)):
-        raise TypeError("q, phi and mask must all be numpy arrays (host seam) or all be torch CUDA tensors (device seam)")
-    lib = _lib.load()
+    s = Seam(q, nx, ny, nz, "q, phi and mask", (phi,), (mask,), kinds=_EXTEND_KINDS, check_device=False)
     cap = max(int(max_rounds), 1)
     trace = np.zeros(cap, dtype=np.int64)
     done = ctypes.c_int(0)
     info = np.zeros(_lib.LSF_EXTEND_INFO_LEN, dtype=np.int64)
-    tail = (nx, ny, nz, float(dx), 0.0 if band is None else float(band), int(max_rounds), ctypes.byref(done), trace.ctypes.data, cap,
-            info.ctypes.data)
-    if _is_torch(q):
-        import torch
-
-        p = _dev_ptr(q, torch.float64, nx, ny, nz, "q")
-        f = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask") if mask is not None else None
-        if phi.device != q.device or (mask is not None and mask.device != q.device):
-            raise ValueError("q, phi and mask must live on one device")
-        st = _stream_and_device(q)
-        rc = lib.lsf_extend_field_device(p, f, m, *tail, st)
-    else:
-        p = _host_ptr(q, np.float64, nx, ny, nz, "q")
-        f = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask") if mask is not None else None
-        rc = lib.lsf_extend_field(p, f, m, *tail)
-    _lib.check(rc)
+    p, f, m = s.field(q, "q"), s.field(phi, "phi"), s.optional(mask, "mask", np.int32)
+    s.one_device()
+    _lib.check(s.call("lsf_extend_field", p, f, m, nx, ny, nz, float(dx), 0.0 if band is None else float(band), int(max_rounds),
+                      ctypes.byref(done), trace.ctypes.data, cap, info.ctypes.data))
     n = done.value
     changed = [int(v) for v in trace[:n]]
     return ExtendReport(n, changed, int(info[0]), int(info[1]), int(info[2]), bool(n and changed[-1] == 0))
@@ -530,17 +412,14 @@ def extendFieldBand(q, phi, mask, dx: float, known=None, band: Optional[float] =
         raise ValueError("mask (int32) must be a field of phi's shape")
     if (known is None) == (band is None):
         raise ValueError("give exactly one of known= (int32; freezes the list cells with known == 1) and band= (cells; freezes |phi| < band*dx)")
-    dev = _is_torch(q)
-    if any(_is_torch(a) != dev for a in (phi, mask) + (() if known is None else (known,))):
-        raise TypeError("q, phi, mask and known must all be numpy arrays (host seam) or all be torch CUDA tensors (device seam)")
-    if not dev and not isinstance(q, np.ndarray):
+    s = Seam(q, None, None, None, "q, phi, mask and known", (phi, mask), (known,), kinds=_EXTEND_KINDS, check_device=False)
+    if not s.dev and not isinstance(q, np.ndarray):
         raise TypeError("q must be a numpy array of float64 or a CUDA tensor of torch.float64")
-    if (q.dim() if dev else q.ndim) != 3:
+    if len(q.shape) != 3:
         raise ValueError("q must be a 3-D field: the grid size is taken from its shape")
-    nx, ny, nz = (int(s) - 1 for s in (tuple(q.shape)[::-1] if dev else q.shape))
-    dx = float(dx)
-    if not (dx > 0.0) or dx == float("inf"):
-        raise ValueError("dx must be finite and > 0")
+    nx, ny, nz = (int(n) - 1 for n in (tuple(q.shape)[::-1] if s.dev else q.shape))  # i is the unit-stride axis of both
+    s.nx, s.ny, s.nz = nx, ny, nz  # the grid is q's own, and its shape can be read only once the kinds are known to agree
+    dx = _seam.positive(dx)
     if band is not None and (not (float(band) > 0.0) or float(band) == float("inf")):
         raise ValueError("band must be finite and > 0")
     max_passes = int(max_passes)
@@ -548,33 +427,16 @@ def extendFieldBand(q, phi, mask, dx: float, known=None, band: Optional[float] =
         raise ValueError("max_passes must be >= 1")
     if trace_cap is not None and int(trace_cap) < 0:
         raise ValueError("trace_cap must be >= 0")
-    if dev:
-        import torch
-
-        p = _dev_ptr(q, torch.float64, nx, ny, nz, "q")
-        f = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-        k = _dev_ptr(known, torch.int32, nx, ny, nz, "known") if known is not None else None
-        if any(a.device != q.device for a in (phi, mask) + (() if known is None else (known,))):
-            raise ValueError("q, phi, mask and known must live on one device")
-    else:
-        p = _host_ptr(q, np.float64, nx, ny, nz, "q")
-        f = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-        k = _host_ptr(known, np.int32, nx, ny, nz, "known") if known is not None else None
+    p, f, m, k = s.field(q, "q"), s.field(phi, "phi"), s.field(mask, "mask", np.int32), s.optional(known, "known", np.int32)
+    s.one_device()
     if p == f:
         raise ValueError("q and phi must be different arrays")
-    lib = _lib.load()
     cap = min(max_passes, _EXTEND_BAND_TRACE)
     trace = np.zeros(cap, dtype=np.int64)
     done = ctypes.c_int(0)
     info = np.zeros(_lib.LSF_EXTEND_BAND_INFO_LEN, dtype=np.int64)
-    args = (p, f, m, k, nx, ny, nz, dx, 0.0 if band is None else float(band), max_passes, ctypes.byref(done), trace.ctypes.data, cap, info.ctypes.data)
-    if dev:
-        rc = lib.lsf_extend_field_band_device(*args, _stream_and_device(q))
-    else:
-        rc = lib.lsf_extend_field_band(*args)
-    _lib.check(rc)
+    _lib.check(s.call("lsf_extend_field_band", p, f, m, k, nx, ny, nz, dx, 0.0 if band is None else float(band), max_passes, ctypes.byref(done),
+                      trace.ctypes.data, cap, info.ctypes.data))
     n = done.value
     converged = n < max_passes or bool(0 < n <= cap and trace[n - 1] == 0)
     keep = min(n, cap if trace_cap is None else min(cap, int(trace_cap)))
@@ -602,49 +464,21 @@ def advectField(phi, nx: int, ny: int, nz: int, dx: float, dt: float, steps: int
     number is reported, not judged: keep it below 1.  Raises LsfNaNError when a step produced a NaN (phi holds that step; the
     exception carries the AdvectReport as `.report`).
     """
-    if scheme not in ("rk3", "euler"):
-        raise ValueError("scheme must be 'rk3' or 'euler'")
-    if arith not in ("strict", "fast"):
-        raise ValueError("arith must be 'strict' or 'fast'")
+    scheme, arith = _seam.named("scheme", scheme, _SCHEMES), _seam.named("arith", arith, _ARITHS)
     if velocity is None and speed is None:
         raise ValueError("give velocity=(u, v, w), speed=F, or both")
-    if velocity is not None:
-        if not isinstance(velocity, (tuple, list)) or len(velocity) != 3 or any(c is None for c in velocity):
-            raise ValueError("velocity must be a 3-tuple (u, v, w) of fields")
-    dev = _is_torch(phi)
-    inputs = [(n, f) for n, f in zip("uvw", velocity or ())] + ([("speed", speed)] if speed is not None else [])
-    if any(_is_torch(f) != dev for _, f in inputs):
-        raise TypeError("phi, velocity and speed must all be numpy arrays or all be CUDA tensors")
+    inputs = _transport_fields(velocity, speed)
+    s = Seam(phi, nx, ny, nz, "phi, velocity and speed", [f for _, f in inputs])
     cap = max(int(steps), 1)
     trace = np.zeros(cap, dtype=np.float64)
     done = ctypes.c_int(0)
     cfl = ctypes.c_double(0.0)
-    if dev:
-        import torch
-
-        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
-        if any(f.device != phi.device for _, f in inputs):
-            raise ValueError("phi, velocity and speed must live on one device")
-    else:
-        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
-    p = ptr(phi, "phi")
-    q = {n: ptr(f, n) for n, f in inputs}
-    lib = _lib.load()
-    tail = (q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps),
-            {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}[scheme], mode_word("jacobi", arith), ctypes.byref(done),
-            ctypes.byref(cfl), trace.ctypes.data, cap)
-    if dev:
-        rc = lib.lsf_advect_field_device(p, *tail, _stream_and_device(phi))
-    else:
-        rc = lib.lsf_advect_field(p, *tail)
+    p = s.field(phi, "phi")
+    q = {n: s.field(f, n) for n, f in inputs}
+    rc = s.call("lsf_advect_field", p, q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps), scheme,
+                LSF_ORDER_JACOBI | arith, ctypes.byref(done), ctypes.byref(cfl), trace.ctypes.data, cap)
     n = done.value
-    rep = AdvectReport(n, float(cfl.value), [float(x) for x in trace[:n]])
-    try:
-        _lib.check(rc)
-    except LsfNaNError as e:
-        e.report = rep  # the steps run, the NaN one included
-        raise
-    return rep
+    return _check_report(rc, AdvectReport(n, float(cfl.value), [float(x) for x in trace[:n]]))
 
 
 class AdvectBandReport(NamedTuple):
@@ -672,57 +506,28 @@ def advectFieldBand(phi, mask, nx: int, ny: int, nz: int, dx: float, dt: float, 
     list, and `margin` (compare it with a few dx) says when to rebuild the mask.  Raises LsfNaNError when a step produced a NaN (phi
     holds that step; the exception carries the AdvectBandReport as `.report`).
     """
-    if scheme not in ("rk3", "euler"):
-        raise ValueError("scheme must be 'rk3' or 'euler'")
-    if arith not in ("strict", "fast"):
-        raise ValueError("arith must be 'strict' or 'fast'")
+    scheme, arith = _seam.named("scheme", scheme, _SCHEMES), _seam.named("arith", arith, _ARITHS)
     if velocity is None and speed is None:
         raise ValueError("give velocity=(u, v, w), speed=F, or both")
-    if velocity is not None:
-        if not isinstance(velocity, (tuple, list)) or len(velocity) != 3 or any(c is None for c in velocity):
-            raise ValueError("velocity must be a 3-tuple (u, v, w) of fields")
+    inputs = _transport_fields(velocity, speed)
     if mask is None:
         raise ValueError("mask must be an int32 field of phi's shape")
-    dev = _is_torch(phi)
-    inputs = [(n, f) for n, f in zip("uvw", velocity or ())] + ([("speed", speed)] if speed is not None else [])
-    if any(_is_torch(f) != dev for _, f in inputs + [("mask", mask)]):
-        raise TypeError("phi, mask, velocity and speed must all be numpy arrays or all be CUDA tensors")
+    s = Seam(phi, nx, ny, nz, "phi, mask, velocity and speed", [f for _, f in inputs] + [mask])
     cap = max(int(steps), 1)
     trace = np.zeros(cap, dtype=np.float64)
     done = ctypes.c_int(0)
     cfl = ctypes.c_double(0.0)
     info = np.full(_lib.LSF_ADVECT_BAND_INFO_LEN, -1, dtype=np.int64)
     margin = ctypes.c_double(float("nan"))
-    if dev:
-        import torch
-
-        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
-        if any(f.device != phi.device for _, f in inputs + [("mask", mask)]):
-            raise ValueError("phi, mask, velocity and speed must live on one device")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-    else:
-        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-    p = ptr(phi, "phi")
-    q = {n: ptr(f, n) for n, f in inputs}
-    lib = _lib.load()
-    tail = (m, q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps),
-            {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}[scheme], mode_word("jacobi", arith), ctypes.byref(done),
-            ctypes.byref(cfl), trace.ctypes.data, cap, info.ctypes.data, ctypes.byref(margin))
-    if dev:
-        rc = lib.lsf_advect_field_band_device(p, *tail, _stream_and_device(phi))
-    else:
-        rc = lib.lsf_advect_field_band(p, *tail)
+    p, m = s.field(phi, "phi"), s.field(mask, "mask", np.int32)
+    q = {n: s.field(f, n) for n, f in inputs}
+    rc = s.call("lsf_advect_field_band", p, m, q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps),
+                scheme, LSF_ORDER_JACOBI | arith, ctypes.byref(done), ctypes.byref(cfl), trace.ctypes.data, cap, info.ctypes.data,
+                ctypes.byref(margin))
     n = done.value
     told = rc == _lib.LSF_OK  # info and margin are written on LSF_OK only
-    rep = AdvectBandReport(n, float(cfl.value), [float(x) for x in trace[:n]], *((int(v) for v in info) if told else (None, None, None)),
-                           float(margin.value) if told else None)
-    try:
-        _lib.check(rc)
-    except LsfNaNError as e:
-        e.report = rep  # the steps run, the NaN one included
-        raise
-    return rep
+    return _check_report(rc, AdvectBandReport(n, float(cfl.value), [float(x) for x in trace[:n]],
+                                              *((int(v) for v in info) if told else (None, None, None)), float(margin.value) if told else None))
 
 
 class EvolveBandReport(NamedTuple):
@@ -763,10 +568,7 @@ def evolveBand(phi, mask, nx: int, ny: int, nz: int, dx: float, dt: float, steps
 
 def _evolve_band(phi, mask, nx, ny, nz, dx, dt, steps, velocity, speed, scheme, arith, core, ring, reinit_sweeps, h, check_every, curv):
     """evolveBand (curv is None) and evolveBandCurv (curv = (curvature, clamp)): validation, the pointers, the call, the report"""
-    if scheme not in ("rk3", "euler"):
-        raise ValueError("scheme must be 'rk3' or 'euler'")
-    if arith not in ("strict", "fast"):
-        raise ValueError("arith must be 'strict' or 'fast'")
+    scheme, arith = _seam.named("scheme", scheme, _SCHEMES), _seam.named("arith", arith, _ARITHS)
     if curv is not None:
         bcurv, clamp = (float(x) for x in curv)
         if not (bcurv >= 0.0) or bcurv == float("inf"):
@@ -777,9 +579,7 @@ def _evolve_band(phi, mask, nx, ny, nz, dx, dt, steps, velocity, speed, scheme, 
             raise ValueError("give velocity=(u, v, w), speed=F, a curvature > 0, or several of them")
     elif velocity is None and speed is None:
         raise ValueError("give velocity=(u, v, w), speed=F, or both")
-    if velocity is not None:
-        if not isinstance(velocity, (tuple, list)) or len(velocity) != 3 or any(c is None for c in velocity):
-            raise ValueError("velocity must be a 3-tuple (u, v, w) of fields")
+    inputs = _transport_fields(velocity, speed)
     if mask is None:
         raise ValueError("mask must be an int32 field of phi's shape")
     if h is None:
@@ -794,52 +594,29 @@ def _evolve_band(phi, mask, nx, ny, nz, dx, dt, steps, velocity, speed, scheme, 
         raise ValueError("h must be finite and > 0")
     if int(check_every) != check_every or check_every < 1:
         raise ValueError("check_every must be an integer >= 1")
-    dev = _is_torch(phi)
-    inputs = [(n, f) for n, f in zip("uvw", velocity or ())] + ([("speed", speed)] if speed is not None else [])
-    if any(_is_torch(f) != dev for _, f in inputs + [("mask", mask)]):
-        raise TypeError("phi, mask, velocity and speed must all be numpy arrays or all be CUDA tensors")
+    s = Seam(phi, nx, ny, nz, "phi, mask, velocity and speed", [f for _, f in inputs] + [mask])
     cap = max(int(steps), 1)
     trace = np.zeros(cap, dtype=np.float64)
     done = ctypes.c_int(0)
     cfl = ctypes.c_double(0.0)
     info = np.full(_lib.LSF_EVOLVE_INFO_LEN, -1, dtype=np.int64)
     margin = ctypes.c_double(float("nan"))
-    if dev:
-        import torch
-
-        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
-        if any(f.device != phi.device for _, f in inputs + [("mask", mask)]):
-            raise ValueError("phi, mask, velocity and speed must live on one device")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-    else:
-        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-    p = ptr(phi, "phi")
-    q = {n: ptr(f, n) for n, f in inputs}
-    lib = _lib.load()
+    p, m = s.field(phi, "phi"), s.field(mask, "mask", np.int32)
+    q = {n: s.field(f, n) for n, f in inputs}
     diffusion = ctypes.c_double(0.0)
-    head = (p, m, q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps),
-            {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}[scheme], mode_word("jacobi", arith), float(core), int(ring),
-            int(reinit_sweeps), float(h), int(check_every))
-    tail = (trace.ctypes.data, cap, info.ctypes.data, ctypes.byref(margin)) + ((_stream_and_device(phi),) if dev else ())
+    head = (p, m, q.get("u"), q.get("v"), q.get("w"), q.get("speed"), nx, ny, nz, float(dx), float(dt), int(steps), scheme, LSF_ORDER_JACOBI | arith,
+            float(core), int(ring), int(reinit_sweeps), float(h), int(check_every))
+    tail = (trace.ctypes.data, cap, info.ctypes.data, ctypes.byref(margin))
     if curv is None:
-        rc = (lib.lsf_evolve_band_device if dev else lib.lsf_evolve_band)(*head, ctypes.byref(done), ctypes.byref(cfl), *tail)
+        rc = s.call("lsf_evolve_band", *head, ctypes.byref(done), ctypes.byref(cfl), *tail)
     else:
-        rc = (lib.lsf_evolve_band_curv_device if dev else lib.lsf_evolve_band_curv)(*head, bcurv, clamp, ctypes.byref(done), ctypes.byref(cfl),
-                                                                                    ctypes.byref(diffusion), *tail)
+        rc = s.call("lsf_evolve_band_curv", *head, bcurv, clamp, ctypes.byref(done), ctypes.byref(cfl), ctypes.byref(diffusion), *tail)
     n = done.value
     told = rc == _lib.LSF_OK  # info and margin are written on LSF_OK only
     rest = (*((int(v) for v in info) if told else (None,) * 6), float(margin.value) if told else None)
     if curv is None:
-        rep = EvolveBandReport(n, float(cfl.value), [float(x) for x in trace[:n]], *rest)
-    else:
-        rep = EvolveBandCurvReport(n, float(cfl.value), float(diffusion.value), [float(x) for x in trace[:n]], *rest)
-    try:
-        _lib.check(rc)
-    except LsfNaNError as e:
-        e.report = rep  # the steps run, the NaN one included
-        raise
-    return rep
+        return _check_report(rc, EvolveBandReport(n, float(cfl.value), [float(x) for x in trace[:n]], *rest))
+    return _check_report(rc, EvolveBandCurvReport(n, float(cfl.value), float(diffusion.value), [float(x) for x in trace[:n]], *rest))
 
 
 class EvolveBandCurvReport(NamedTuple):
@@ -897,34 +674,14 @@ def curvatureBand(phi, mask, nx: int, ny: int, nz: int, dx: float, kappa, *, gau
     """
     if mask is None or kappa is None:
         raise ValueError("mask (int32) and kappa (float64) must be fields of phi's shape")
-    dev = _is_torch(phi)
-    outs = [("kappa", kappa)] + [(n, a) for n, a in (("gauss", gauss), ("gmag", gmag)) if a is not None]
-    if any(_is_torch(a) != dev for _, a in outs + [("mask", mask)]):
-        raise TypeError("phi, mask, kappa, gauss and gmag must all be numpy arrays or all be CUDA tensors")
+    s = Seam(phi, nx, ny, nz, "phi, mask, kappa, gauss and gmag", (mask, kappa), (gauss, gmag))
     clamp = float(clamp)
     if not (clamp >= 0.0) or clamp == float("inf"):
         raise ValueError("clamp must be finite and >= 0 (0: no clamp)")
-    if dev:
-        import torch
-
-        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
-        if any(a.device != phi.device for _, a in outs + [("mask", mask)]):
-            raise ValueError("phi, mask, kappa, gauss and gmag must live on one device")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-    else:
-        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-    p = ptr(phi, "phi")
-    q = {n: ptr(a, n) for n, a in outs}
-    lib = _lib.load()
     info = np.zeros(_lib.LSF_CURV_INFO_LEN, dtype=np.int64)
     kmax = ctypes.c_double(0.0)
-    args = (p, m, q["kappa"], q.get("gauss"), q.get("gmag"), nx, ny, nz, float(dx), clamp, info.ctypes.data, ctypes.byref(kmax))
-    if dev:
-        rc = lib.lsf_curvature_band_device(*args, _stream_and_device(phi))
-    else:
-        rc = lib.lsf_curvature_band(*args)
-    _lib.check(rc)
+    _lib.check(s.call("lsf_curvature_band", s.field(phi, "phi"), s.field(mask, "mask", np.int32), s.field(kappa, "kappa"),
+                      s.optional(gauss, "gauss"), s.optional(gmag, "gmag"), nx, ny, nz, float(dx), clamp, info.ctypes.data, ctypes.byref(kmax)))
     return CurvatureReport(int(info[0]), int(info[1]), int(info[2]), float(kmax.value))
 
 
@@ -959,39 +716,12 @@ def measureBand(phi, mask, nx: int, ny: int, nz: int, dx: float, xLo, iso: float
     """
     if mask is None:
         raise ValueError("mask (int32) must be a field of phi's shape")
-    lo = np.ascontiguousarray(xLo, dtype=np.float64)
-    if lo.shape != (3,) or not np.all(np.isfinite(lo)):
-        raise ValueError("xLo must hold 3 finite values")
-    dx, iso = float(dx), float(iso)
-    if not (np.isfinite(dx) and dx > 0.0):
-        raise ValueError("dx must be finite and > 0")
-    if not np.isfinite(iso):
-        raise ValueError("iso must be finite")
-    dev = _is_torch(phi)
-    opt = [(n, a) for n, a in (("q", q), ("cell_area", cell_area)) if a is not None]
-    if any(_is_torch(a) != dev for _, a in opt + [("mask", mask)]):
-        raise TypeError("phi, mask, q and cell_area must all be numpy arrays or all be CUDA tensors")
-    if dev:
-        import torch
-
-        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
-        if any(a.device != phi.device for _, a in opt + [("mask", mask)]):
-            raise ValueError("phi, mask, q and cell_area must live on one device")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-    else:
-        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-    p = ptr(phi, "phi")
-    o = {n: ptr(a, n) for n, a in opt}
-    lib = _lib.load()
+    lo, dx, iso = _seam.xlo(xLo), _seam.positive(dx), _seam.finite_iso(iso)
+    s = Seam(phi, nx, ny, nz, "phi, mask, q and cell_area", (mask,), (q, cell_area))
     M = np.zeros(_lib.LSF_MEASURE_LEN, dtype=np.float64)
     info = np.zeros(_lib.LSF_MEASURE_INFO_LEN, dtype=np.int64)
-    args = (p, m, o.get("q"), o.get("cell_area"), nx, ny, nz, dx, lo.ctypes.data, iso, M.ctypes.data, info.ctypes.data)
-    if dev:
-        rc = lib.lsf_measure_band_device(*args, _stream_and_device(phi))
-    else:
-        rc = lib.lsf_measure_band(*args)
-    _lib.check(rc)
+    _lib.check(s.call("lsf_measure_band", s.field(phi, "phi"), s.field(mask, "mask", np.int32), s.optional(q, "q"),
+                      s.optional(cell_area, "cell_area"), nx, ny, nz, dx, lo.ctypes.data, iso, M.ctypes.data, info.ctypes.data))
     M = [float(v) for v in M]
     over = lambda num, den: tuple(v / den if den != 0.0 else float("nan") for v in num)
     return MeasureReport(M[0], M[1], over(M[2:5], M[1]), over(M[5:8], M[0]), M[8], *(int(v) for v in info))
@@ -1022,11 +752,7 @@ def cutCellsBand(phi, mask, nx: int, ny: int, nz: int, dx: float, iso: float = 0
     """
     if mask is None:
         raise ValueError("mask (int32) must be a field of phi's shape")
-    dx, iso = float(dx), float(iso)
-    if not (np.isfinite(dx) and dx > 0.0):
-        raise ValueError("dx must be finite and > 0")
-    if not np.isfinite(iso):
-        raise ValueError("iso must be finite")
+    dx, iso = _seam.positive(dx), _seam.finite_iso(iso)
     outs = [] if vof is None else [("vof", vof)]
     for name, group, parts in (("aperture", aperture, ("ax", "ay", "az")), ("area_vector", area_vector, ("bx", "by", "bz"))):
         if group is None:
@@ -1034,31 +760,13 @@ def cutCellsBand(phi, mask, nx: int, ny: int, nz: int, dx: float, iso: float = 0
         if not isinstance(group, (tuple, list)) or len(group) != 3 or any(a is None for a in group):
             raise ValueError(f"{name} must be a 3-tuple of fields of phi's shape")
         outs += list(zip(parts, group))
-    dev = _is_torch(phi)
-    if any(_is_torch(a) != dev for _, a in outs + [("mask", mask)]):
-        raise TypeError("phi, mask and the outputs must all be numpy arrays or all be CUDA tensors")
-    if dev:
-        import torch
-
-        ptr = lambda a, name: _dev_ptr(a, torch.float64, nx, ny, nz, name)
-        if any(a.device != phi.device for _, a in outs + [("mask", mask)]):
-            raise ValueError("phi, mask and the outputs must live on one device")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-    else:
-        ptr = lambda a, name: _host_ptr(a, np.float64, nx, ny, nz, name)
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-    p = ptr(phi, "phi")
-    o = {n: ptr(a, n) for n, a in outs}
-    lib = _lib.load()
+    s = Seam(phi, nx, ny, nz, "phi, mask and the outputs", [a for _, a in outs] + [mask])
+    p, m = s.field(phi, "phi"), s.field(mask, "mask", np.int32)
+    o = {n: s.field(a, n) for n, a in outs}
     tot = np.zeros(2, dtype=np.float64)  # volume, vof_min
     info = np.zeros(_lib.LSF_CUT_INFO_LEN, dtype=np.int64)
-    args = (p, m, nx, ny, nz, dx, iso, *(o.get(n) for n in ("vof", "ax", "ay", "az", "bx", "by", "bz")), tot.ctypes.data,
-            tot.ctypes.data + 8, info.ctypes.data)
-    if dev:
-        rc = lib.lsf_cut_cells_band_device(*args, _stream_and_device(phi))
-    else:
-        rc = lib.lsf_cut_cells_band(*args)
-    _lib.check(rc)
+    _lib.check(s.call("lsf_cut_cells_band", p, m, nx, ny, nz, dx, iso, *(o.get(n) for n in ("vof", "ax", "ay", "az", "bx", "by", "bz")),
+                      tot.ctypes.data, tot.ctypes.data + 8, info.ctypes.data))
     return CutCellsReport(float(tot[0]), float(tot[1]), *(int(v) for v in info))
 
 
@@ -1098,40 +806,18 @@ def labelBand(phi, mask, nx: int, ny: int, nz: int, label, *, iso: float = 0.0, 
         raise ValueError("mask and label (int32) must be fields of phi's shape")
     if side not in _LABEL_SIDES:
         raise ValueError('side must be "inside", "outside" or "both"')
-    iso, max_passes = float(iso), int(max_passes)
-    if not np.isfinite(iso):
-        raise ValueError("iso must be finite")
+    iso, max_passes = _seam.finite_iso(iso), int(max_passes)
     if max_passes < 1:
         raise ValueError("max_passes must be >= 1")
     cap = 1024 if comp_cap is None else int(comp_cap)
     if cap < 0:
         raise ValueError("comp_cap must be >= 0")
-    dev = _is_torch(phi)
-    if _is_torch(mask) != dev or _is_torch(label) != dev:
-        raise TypeError("phi, mask and label must all be numpy arrays or all be CUDA tensors")
-    if dev:
-        import torch
-
-        if mask.device != phi.device or label.device != phi.device:
-            raise ValueError("phi, mask and label must live on one device")
-        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        m = _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-        lab = _dev_ptr(label, torch.int32, nx, ny, nz, "label")
-    else:
-        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        m = _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-        lab = _host_ptr(label, np.int32, nx, ny, nz, "label")
-    lib = _lib.load()
+    s = Seam(phi, nx, ny, nz, "phi, mask and label", (mask, label))
     comp = np.zeros((cap, _lib.LSF_LABEL_COMP_LEN), dtype=np.int64)
     info = np.zeros(_lib.LSF_LABEL_INFO_LEN, dtype=np.int64)
     ncomp = ctypes.c_int64(0)
-    args = (p, m, lab, nx, ny, nz, iso, _LABEL_SIDES[side], max_passes, comp.ctypes.data if cap else None, cap, ctypes.byref(ncomp),
-            info.ctypes.data)
-    if dev:
-        rc = lib.lsf_label_band_device(*args, _stream_and_device(phi))
-    else:
-        rc = lib.lsf_label_band(*args)
-    _lib.check(rc)
+    _lib.check(s.call("lsf_label_band", s.field(phi, "phi"), s.field(mask, "mask", np.int32), s.field(label, "label", np.int32), nx, ny, nz, iso,
+                      _LABEL_SIDES[side], max_passes, comp.ctypes.data if cap else None, cap, ctypes.byref(ncomp), info.ctypes.data))
     n = int(ncomp.value)
     return LabelReport(n, comp[:min(n, cap)].copy(), int(info[4]), int(info[5]) == 0, tuple(int(v) for v in info))
 
@@ -1149,9 +835,6 @@ class SampleReport(NamedTuple):
     info: tuple
 
 
-_SAMPLE_ORDERS = {"linear": _lib.LSF_SAMPLE_LINEAR, "cubic": _lib.LSF_SAMPLE_CUBIC}
-
-
 def samplePoints(phi, nx: int, ny: int, nz: int, dx: float, xLo, pts, *, order: str = "cubic", mask=None, q=None, iso: float = 0.0,
                  iters: int = 0, tol: float = 1e-6, want_grad: bool = True) -> SampleReport:
     """The field at arbitrary points (include/lsf.h: lsf_sample_points): phi, its gradient, a second field q and, with iters >= 1, the
@@ -1164,66 +847,23 @@ def samplePoints(phi, nx: int, ny: int, nz: int, dx: float, xLo, pts, *, order: 
     Refused points hold NaN in every output.  phi, mask, q and pts are read only.  The grid point (i,j,k) is xLo + (i,j,k)*dx.
     Numpy in gives numpy out (host seam); CUDA tensors in give CUDA tensors out (device seam, on the tensor's current stream).
     """
-    lo = np.ascontiguousarray(xLo, dtype=np.float64)
-    if lo.shape != (3,) or not np.all(np.isfinite(lo)):
-        raise ValueError("xLo must hold 3 finite values")
-    dx, iso, tol, iters = float(dx), float(iso), float(tol), int(iters)
-    if not (np.isfinite(dx) and dx > 0.0):
-        raise ValueError("dx must be finite and > 0")
-    if not np.isfinite(iso):
-        raise ValueError("iso must be finite")
-    if order not in _SAMPLE_ORDERS:
-        raise ValueError("order must be 'linear' or 'cubic'")
+    lo, dx, iso, tol, iters = _seam.xlo(xLo), _seam.positive(dx), _seam.finite_iso(iso), float(tol), int(iters)
+    order = _seam.named("order", order, _SAMPLE_ORDERS)
     if iters < 0:
         raise ValueError("iters must be >= 0")
     if iters >= 1 and not (np.isfinite(tol) and tol >= 0.0):
         raise ValueError("tol must be finite and >= 0")
-    if min(int(nx), int(ny), int(nz)) < 1:
-        raise ValueError("nx, ny, nz must be >= 1")
-    dev = _is_torch(phi)
-    opt = [(n, a) for n, a in (("mask", mask), ("q", q)) if a is not None]
-    if any(_is_torch(a) != dev for _, a in opt + [("pts", pts)]):
-        raise TypeError("phi, mask, q and pts must all be numpy arrays or all be CUDA tensors")
-    if len(pts.shape) != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
-        raise ValueError("pts must have shape (npts, 3) with npts >= 1")
-    npts = int(pts.shape[0])
-    lib = _lib.load()
+    _seam.grid(nx, ny, nz)
+    s = Seam(phi, nx, ny, nz, "phi, mask, q and pts", (pts,), (mask, q))
+    npts = s.points(pts)
+    p, m, qq = s.field(phi, "phi"), s.optional(mask, "mask", np.int32), s.optional(q, "q")
     info = np.zeros(_lib.LSF_SAMPLE_INFO_LEN, dtype=np.int64)
-    if dev:
-        import torch
-
-        if any(a.device != phi.device for _, a in opt + [("pts", pts)]):
-            raise ValueError("phi, mask, q and pts must live on one device")
-        if not pts.is_cuda or pts.dtype != torch.float64 or not pts.t().is_contiguous():
-            raise TypeError("pts must be a float64 CUDA tensor of shape (npts, 3) in Fortran order (the transpose of a contiguous (3, npts))")
-        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        m = None if mask is None else _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-        qq = None if q is None else _dev_ptr(q, torch.float64, nx, ny, nz, "q")
-        vec = lambda: torch.empty((3, npts), dtype=torch.float64, device=phi.device).t()
-        val = torch.empty(npts, dtype=torch.float64, device=phi.device)
-        status = torch.empty(npts, dtype=torch.int32, device=phi.device)
-        grad = vec() if want_grad else None
-        qval = torch.empty(npts, dtype=torch.float64, device=phi.device) if q is not None else None
-        foot = vec() if iters >= 1 else None
-        ptr = lambda a: None if a is None else a.data_ptr()
-        rc = lib.lsf_sample_points_device(p, m, qq, nx, ny, nz, dx, lo.ctypes.data, pts.data_ptr(), npts, _SAMPLE_ORDERS[order], iso, iters, tol,
-                                          ptr(val), ptr(grad), ptr(qval), ptr(foot), ptr(status), info.ctypes.data, _stream_and_device(phi))
-    else:
-        if not isinstance(pts, np.ndarray) or pts.dtype != np.float64 or not pts.flags.f_contiguous:
-            raise TypeError("pts must be a Fortran-ordered float64 numpy array of shape (npts, 3)")
-        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        m = None if mask is None else _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-        qq = None if q is None else _host_ptr(q, np.float64, nx, ny, nz, "q")
-        vec = lambda: np.zeros((npts, 3), dtype=np.float64, order="F")
-        val = np.zeros(npts, dtype=np.float64)
-        status = np.zeros(npts, dtype=np.int32)
-        grad = vec() if want_grad else None
-        qval = np.zeros(npts, dtype=np.float64) if q is not None else None
-        foot = vec() if iters >= 1 else None
-        ptr = lambda a: None if a is None else a.ctypes.data
-        rc = lib.lsf_sample_points(p, m, qq, nx, ny, nz, dx, lo.ctypes.data, pts.ctypes.data, npts, _SAMPLE_ORDERS[order], iso, iters, tol,
-                                   ptr(val), ptr(grad), ptr(qval), ptr(foot), ptr(status), info.ctypes.data)
-    _lib.check(rc)
+    val, status = s.out(npts), s.out(npts, np.int32)
+    grad = s.out3(npts) if want_grad else None
+    qval = s.out(npts) if q is not None else None
+    foot = s.out3(npts) if iters >= 1 else None
+    _lib.check(s.call("lsf_sample_points", p, m, qq, nx, ny, nz, dx, lo.ctypes.data, s.ptr(pts), npts, order, iso, iters, tol, s.ptr(val),
+                      s.ptr(grad), s.ptr(qval), s.ptr(foot), s.ptr(status), info.ctypes.data))
     return SampleReport(val, grad, qval, foot, status, tuple(int(v) for v in info))
 
 
@@ -1254,17 +894,10 @@ def castRays(phi, nx: int, ny: int, nz: int, dx: float, xLo, org, dir, *, order:
     field, sampled at the hit.  A ray that is not HIT holds NaN in hit, grad and qval.  More than max_steps steps: status STEPS.
     Numpy in gives numpy out (host seam); CUDA tensors in give CUDA tensors out (device seam, on the tensor's current stream).
     """
-    lo = np.ascontiguousarray(xLo, dtype=np.float64)
-    if lo.shape != (3,) or not np.all(np.isfinite(lo)):
-        raise ValueError("xLo must hold 3 finite values")
-    dx, iso, tmin, tmax, safety, smin, smax, skip = (float(v) for v in (dx, iso, tmin, tmax, safety, smin, smax, skip))
+    lo, dx, iso = _seam.xlo(xLo), _seam.positive(dx), _seam.finite_iso(iso)
+    tmin, tmax, safety, smin, smax, skip = (float(v) for v in (tmin, tmax, safety, smin, smax, skip))
     refine, max_steps = int(refine), int(max_steps)
-    if not (np.isfinite(dx) and dx > 0.0):
-        raise ValueError("dx must be finite and > 0")
-    if not np.isfinite(iso):
-        raise ValueError("iso must be finite")
-    if order not in _SAMPLE_ORDERS:
-        raise ValueError("order must be 'linear' or 'cubic'")
+    order = _seam.named("order", order, _SAMPLE_ORDERS)
     if not (np.isfinite(tmin) and tmin >= 0.0 and np.isfinite(tmax) and tmax > tmin):
         raise ValueError("tmin must be finite and >= 0, tmax finite and > tmin")
     if not (0.0 < safety <= 1.0):
@@ -1275,56 +908,20 @@ def castRays(phi, nx: int, ny: int, nz: int, dx: float, xLo, org, dir, *, order:
         raise ValueError("skip must be finite and > 0")
     if refine < 0 or max_steps < 1:
         raise ValueError("refine must be >= 0 and max_steps >= 1")
-    if min(int(nx), int(ny), int(nz)) < 1:
-        raise ValueError("nx, ny, nz must be >= 1")
-    dev = _is_torch(phi)
-    opt = [(n, a) for n, a in (("mask", mask), ("q", q)) if a is not None]
-    rays = [("org", org), ("dir", dir)]
-    if any(_is_torch(a) != dev for _, a in opt + rays):
-        raise TypeError("phi, mask, q, org and dir must all be numpy arrays or all be CUDA tensors")
+    _seam.grid(nx, ny, nz)
+    s = Seam(phi, nx, ny, nz, "phi, mask, q, org and dir", (org, dir), (mask, q))
     if len(org.shape) != 2 or org.shape[1] != 3 or org.shape[0] < 1 or tuple(dir.shape) != tuple(org.shape):
         raise ValueError("org and dir must have one shape (nrays, 3) with nrays >= 1")
-    nrays = int(org.shape[0])
-    lib = _lib.load()
+    nrays = s.points(org, "org", "nrays")
+    s.points(dir, "dir", "nrays")
+    p, m, qq = s.field(phi, "phi"), s.optional(mask, "mask", np.int32), s.optional(q, "q")
     info = np.zeros(_lib.LSF_CAST_INFO_LEN, dtype=np.int64)
-    par = (nrays, _SAMPLE_ORDERS[order], iso, tmin, tmax, safety, smin, smax, skip, refine, max_steps)
-    if dev:
-        import torch
-
-        if any(a.device != phi.device for _, a in opt + rays):
-            raise ValueError("phi, mask, q, org and dir must live on one device")
-        for name, a in rays:
-            if not a.is_cuda or a.dtype != torch.float64 or not a.t().is_contiguous():
-                raise TypeError(f"{name} must be a float64 CUDA tensor of shape (nrays, 3) in Fortran order (the transpose of a contiguous (3, nrays))")
-        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        m = None if mask is None else _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-        qq = None if q is None else _dev_ptr(q, torch.float64, nx, ny, nz, "q")
-        vec = lambda: torch.empty((3, nrays), dtype=torch.float64, device=phi.device).t()
-        thit = torch.empty(nrays, dtype=torch.float64, device=phi.device)
-        status = torch.empty(nrays, dtype=torch.int32, device=phi.device)
-        hit = vec() if want_hit else None
-        grad = vec() if want_grad else None
-        qval = torch.empty(nrays, dtype=torch.float64, device=phi.device) if q is not None else None
-        ptr = lambda a: None if a is None else a.data_ptr()
-        rc = lib.lsf_cast_rays_device(p, m, qq, nx, ny, nz, dx, lo.ctypes.data, org.data_ptr(), dir.data_ptr(), *par, ptr(thit), ptr(hit),
-                                      ptr(grad), ptr(qval), ptr(status), info.ctypes.data, _stream_and_device(phi))
-    else:
-        for name, a in rays:
-            if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.f_contiguous:
-                raise TypeError(f"{name} must be a Fortran-ordered float64 numpy array of shape (nrays, 3)")
-        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        m = None if mask is None else _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-        qq = None if q is None else _host_ptr(q, np.float64, nx, ny, nz, "q")
-        vec = lambda: np.zeros((nrays, 3), dtype=np.float64, order="F")
-        thit = np.zeros(nrays, dtype=np.float64)
-        status = np.zeros(nrays, dtype=np.int32)
-        hit = vec() if want_hit else None
-        grad = vec() if want_grad else None
-        qval = np.zeros(nrays, dtype=np.float64) if q is not None else None
-        ptr = lambda a: None if a is None else a.ctypes.data
-        rc = lib.lsf_cast_rays(p, m, qq, nx, ny, nz, dx, lo.ctypes.data, org.ctypes.data, dir.ctypes.data, *par, ptr(thit), ptr(hit), ptr(grad),
-                               ptr(qval), ptr(status), info.ctypes.data)
-    _lib.check(rc)
+    thit, status = s.out(nrays), s.out(nrays, np.int32)
+    hit = s.out3(nrays) if want_hit else None
+    grad = s.out3(nrays) if want_grad else None
+    qval = s.out(nrays) if q is not None else None
+    _lib.check(s.call("lsf_cast_rays", p, m, qq, nx, ny, nz, dx, lo.ctypes.data, s.ptr(org), s.ptr(dir), nrays, order, iso, tmin, tmax, safety,
+                      smin, smax, skip, refine, max_steps, s.ptr(thit), s.ptr(hit), s.ptr(grad), s.ptr(qval), s.ptr(status), info.ctypes.data))
     return CastReport(thit, hit, grad, qval, status, tuple(int(v) for v in info))
 
 
@@ -1338,34 +935,6 @@ class AdvectPointsReport(NamedTuple):
     info: tuple
 
 
-_POINT_SCHEMES = {"rk3": _lib.LSF_ADVECT_RK3, "euler": _lib.LSF_ADVECT_EULER}
-
-
-def _points_common(nx, ny, nz, dx, xLo):
-    lo = np.ascontiguousarray(xLo, dtype=np.float64)
-    if lo.shape != (3,) or not np.all(np.isfinite(lo)):
-        raise ValueError("xLo must hold 3 finite values")
-    dx = float(dx)
-    if not (np.isfinite(dx) and dx > 0.0):
-        raise ValueError("dx must be finite and > 0")
-    if min(int(nx), int(ny), int(nz)) < 1:
-        raise ValueError("nx, ny, nz must be >= 1")
-    return lo, dx
-
-
-def _points_layout(pts, dev, name="pts"):
-    if len(pts.shape) != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
-        raise ValueError(f"{name} must have shape (npts, 3) with npts >= 1")
-    if dev:
-        import torch
-
-        if not pts.is_cuda or pts.dtype != torch.float64 or not pts.t().is_contiguous():
-            raise TypeError(f"{name} must be a float64 CUDA tensor of shape (npts, 3) in Fortran order (the transpose of a contiguous (3, npts))")
-    elif not isinstance(pts, np.ndarray) or pts.dtype != np.float64 or not pts.flags.f_contiguous:
-        raise TypeError(f"{name} must be a Fortran-ordered float64 numpy array of shape (npts, 3)")
-    return int(pts.shape[0])
-
-
 def advectPoints(pts, nx: int, ny: int, nz: int, dx: float, xLo, dt: float, steps: int, *, velocity=None, speed=None, phi=None, mask=None,
                  order: str = "cubic", scheme: str = "rk3") -> AdvectPointsReport:
     """Points carried through the fields that move phi (include/lsf.h: lsf_advect_points): x' = velocity(x) + speed(x) * grad phi(x) /
@@ -1377,14 +946,12 @@ def advectPoints(pts, nx: int, ny: int, nz: int, dx: float, xLo, dt: float, step
     the grid, walks off the mask or meets a flat phi keeps the position of its last completed step and says why in status.
     Numpy in gives numpy out (host seam); CUDA tensors in give CUDA tensors out (device seam, on the tensor's current stream).
     """
-    lo, dx = _points_common(nx, ny, nz, dx, xLo)
+    lo, dx = _seam.xlo(xLo), _seam.positive(dx)
+    _seam.grid(nx, ny, nz)
     dt, steps = float(dt), int(steps)
     if not np.isfinite(dt):
         raise ValueError("dt must be finite")
-    if order not in _SAMPLE_ORDERS:
-        raise ValueError("order must be 'linear' or 'cubic'")
-    if scheme not in _POINT_SCHEMES:
-        raise ValueError("scheme must be 'rk3' or 'euler'")
+    order, scheme = _seam.named("order", order, _SAMPLE_ORDERS), _seam.named("scheme", scheme, _SCHEMES)
     if not 1 <= steps <= _lib.LSF_ADVECT_POINTS_MAX_STEPS:
         raise ValueError(f"steps must be in 1..{_lib.LSF_ADVECT_POINTS_MAX_STEPS}")
     if velocity is not None and (len(velocity) != 3 or any(f is None for f in velocity)):
@@ -1393,32 +960,16 @@ def advectPoints(pts, nx: int, ny: int, nz: int, dx: float, xLo, dt: float, step
         raise ValueError("neither a velocity nor a speed is given")
     if (speed is None) != (phi is None):
         raise ValueError("speed and phi are given together")
-    dev = _is_torch(pts)
-    named = [(n, a) for n, a in (("u", None if velocity is None else velocity[0]), ("v", None if velocity is None else velocity[1]),
-                                 ("w", None if velocity is None else velocity[2]), ("phi", phi), ("speed", speed), ("mask", mask))]
-    if any(_is_torch(a) != dev for _, a in named if a is not None):
-        raise TypeError("pts and the fields must all be numpy arrays or all be CUDA tensors")
-    npts = _points_layout(pts, dev)
-    lib = _lib.load()
+    u, v, w = (None, None, None) if velocity is None else velocity
+    s = Seam(pts, nx, ny, nz, "pts and the fields", optional=(u, v, w, phi, speed, mask), check_device=False)
+    npts = s.points(pts)
+    s.one_device()
+    f = [s.optional(a, n) for n, a in (("u", u), ("v", v), ("w", w), ("phi", phi), ("speed", speed))] + [s.optional(mask, "mask", np.int32)]
     info = np.zeros(_lib.LSF_ADVECT_POINTS_INFO_LEN, dtype=np.int64)
     cfl = ctypes.c_double(0.0)
-    if dev:
-        import torch
-
-        if any(a.device != pts.device for _, a in named if a is not None):
-            raise ValueError("pts and the fields must live on one device")
-        f = [None if a is None else _dev_ptr(a, torch.int32 if n == "mask" else torch.float64, nx, ny, nz, n) for n, a in named]
-        out = pts.t().clone().t()
-        status = torch.empty(npts, dtype=torch.int32, device=pts.device)
-        rc = lib.lsf_advect_points_device(*f, nx, ny, nz, dx, lo.ctypes.data, out.data_ptr(), npts, _SAMPLE_ORDERS[order], _POINT_SCHEMES[scheme],
-                                          dt, steps, status.data_ptr(), ctypes.byref(cfl), info.ctypes.data, _stream_and_device(pts))
-    else:
-        f = [None if a is None else _host_ptr(a, np.int32 if n == "mask" else np.float64, nx, ny, nz, n) for n, a in named]
-        out = pts.copy(order="F")
-        status = np.zeros(npts, dtype=np.int32)
-        rc = lib.lsf_advect_points(*f, nx, ny, nz, dx, lo.ctypes.data, out.ctypes.data, npts, _SAMPLE_ORDERS[order], _POINT_SCHEMES[scheme], dt,
-                                   steps, status.ctypes.data, ctypes.byref(cfl), info.ctypes.data)
-    _lib.check(rc)
+    out, status = s.copy3(pts), s.out(npts, np.int32)
+    _lib.check(s.call("lsf_advect_points", *f, nx, ny, nz, dx, lo.ctypes.data, s.ptr(out), npts, order, scheme, dt, steps, s.ptr(status),
+                      ctypes.byref(cfl), info.ctypes.data))
     return AdvectPointsReport(out, status, float(cfl.value), tuple(int(v) for v in info))
 
 
@@ -1440,40 +991,21 @@ def correctField(phi, nx: int, ny: int, nz: int, dx: float, xLo, pts, rad, *, ma
     off the list are left out (status OFFBAND).  The result does not depend on the order of the particles.  Numpy in: host seam; CUDA
     tensors in: device seam, on the tensor's current stream.
     """
-    lo, dx = _points_common(nx, ny, nz, dx, xLo)
+    lo, dx = _seam.xlo(xLo), _seam.positive(dx)
+    _seam.grid(nx, ny, nz)
     slack = float(slack)
     if not (np.isfinite(slack) and slack >= 0.0):
         raise ValueError("slack must be finite and >= 0")
-    dev = _is_torch(phi)
-    if any(_is_torch(a) != dev for a in (pts, rad) + (() if mask is None else (mask,))):
-        raise TypeError("phi, mask, pts and rad must all be numpy arrays or all be CUDA tensors")
-    npts = _points_layout(pts, dev)
-    if tuple(rad.shape) != (npts,):
-        raise ValueError("rad must have shape (npts,)")
-    lib = _lib.load()
+    s = Seam(phi, nx, ny, nz, "phi, mask, pts and rad", (pts, rad), (mask,), check_device=False)
+    npts = s.points(pts)
+    s.one_device()
+    s.vector(rad, npts, "rad")
+    p, m = s.field(phi, "phi"), s.optional(mask, "mask", np.int32)
     info = np.zeros(_lib.LSF_CORRECT_INFO_LEN, dtype=np.int64)
     change = ctypes.c_double(0.0)
-    if dev:
-        import torch
-
-        if any(a.device != phi.device for a in (pts, rad) + (() if mask is None else (mask,))):
-            raise ValueError("phi, mask, pts and rad must live on one device")
-        if rad.dtype != torch.float64 or not rad.is_contiguous():
-            raise TypeError("rad must be a contiguous float64 CUDA tensor")
-        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        m = None if mask is None else _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-        status = torch.empty(npts, dtype=torch.int32, device=phi.device)
-        rc = lib.lsf_correct_field_device(p, m, nx, ny, nz, dx, lo.ctypes.data, pts.data_ptr(), rad.data_ptr(), npts, slack, status.data_ptr(),
-                                          ctypes.byref(change), info.ctypes.data, _stream_and_device(phi))
-    else:
-        if not isinstance(rad, np.ndarray) or rad.dtype != np.float64 or not rad.flags.c_contiguous:
-            raise TypeError("rad must be a contiguous float64 numpy array")
-        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        m = None if mask is None else _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-        status = np.zeros(npts, dtype=np.int32)
-        rc = lib.lsf_correct_field(p, m, nx, ny, nz, dx, lo.ctypes.data, pts.ctypes.data, rad.ctypes.data, npts, slack, status.ctypes.data,
-                                   ctypes.byref(change), info.ctypes.data)
-    _lib.check(rc)
+    status = s.out(npts, np.int32)
+    _lib.check(s.call("lsf_correct_field", p, m, nx, ny, nz, dx, lo.ctypes.data, s.ptr(pts), s.ptr(rad), npts, slack, s.ptr(status),
+                      ctypes.byref(change), info.ctypes.data))
     return CorrectReport(status, float(change.value), tuple(int(v) for v in info))
 
 
@@ -1486,7 +1018,8 @@ def seedParticles(phi, nx: int, ny: int, nz: int, dx: float, xLo, *, mask=None, 
     samplePoints(order="linear"); the points with rmin * dx <= |val| <= band * dx are kept and rad = sign(val) * clip(|val|, rmin * dx,
     rmax * dx).  phi and mask are numpy arrays of shape (nx+1, ny+1, nz+1) in Fortran order.
     """
-    lo, dx = _points_common(nx, ny, nz, dx, xLo)
+    lo, dx = _seam.xlo(xLo), _seam.positive(dx)
+    _seam.grid(nx, ny, nz)
     f = np.asarray(phi)
     if f.shape != (nx + 1, ny + 1, nz + 1):
         raise ValueError("phi must be a numpy array of shape (nx+1, ny+1, nz+1)")
@@ -1537,11 +1070,11 @@ def reseedParticles(phi, nx: int, ny: int, nz: int, dx: float, xLo, pts=None, ra
     are reported (info[11], info[12]) and left alone.  Numpy in gives numpy out (host seam); CUDA tensors in give CUDA tensors out
     (device seam, on the tensor's current stream).
     """
-    lo, dx = _points_common(nx, ny, nz, dx, xLo)
+    lo, dx = _seam.xlo(xLo), _seam.positive(dx)
+    _seam.grid(nx, ny, nz)
     per_cell, iters, seed = int(per_cell), int(iters), int(seed)
     rmin, rmax, band, tol = float(rmin), float(rmax), float(band), float(tol)
-    if order not in _SAMPLE_ORDERS:
-        raise ValueError("order must be 'linear' or 'cubic'")
+    order = _seam.named("order", order, _SAMPLE_ORDERS)
     if not 1 <= per_cell <= _lib.LSF_RESEED_MAX_PER_CELL:
         raise ValueError(f"per_cell must be in 1..{_lib.LSF_RESEED_MAX_PER_CELL}")
     if not 1 <= iters <= _lib.LSF_RESEED_MAX_ITERS:
@@ -1554,54 +1087,23 @@ def reseedParticles(phi, nx: int, ny: int, nz: int, dx: float, xLo, pts=None, ra
         raise ValueError("pts and rad are given together")
     if pts is not None and pts.shape[0] == 0:
         pts = rad = None
-    dev = _is_torch(phi)
-    others = tuple(a for a in (pts, rad, mask) if a is not None)
-    if any(_is_torch(a) != dev for a in others):
-        raise TypeError("phi, mask, pts and rad must all be numpy arrays or all be CUDA tensors")
+    s = Seam(phi, nx, ny, nz, "phi, mask, pts and rad", optional=(pts, rad, mask), check_device=False)
     npts = 0
     if pts is not None:
-        npts = _points_layout(pts, dev)
-        if tuple(rad.shape) != (npts,):
-            raise ValueError("rad must have shape (npts,)")
-    lib = _lib.load()
+        npts = s.points(pts)
+    s.one_device()
+    if pts is not None:
+        s.vector(rad, npts, "rad")
+    p, m = s.field(phi, "phi"), s.optional(mask, "mask", np.int32)
     info = np.zeros(_lib.LSF_RESEED_INFO_LEN, dtype=np.int64)
     nout = ctypes.c_int(0)
     useed = ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF)
-    if dev:
-        import torch
-
-        if any(a.device != phi.device for a in others):
-            raise ValueError("phi, mask, pts and rad must live on one device")
-        if rad is not None and (rad.dtype != torch.float64 or not rad.is_contiguous()):
-            raise TypeError("rad must be a contiguous float64 CUDA tensor")
-        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        m = None if mask is None else _dev_ptr(mask, torch.int32, nx, ny, nz, "mask")
-        status = torch.empty(npts, dtype=torch.int32, device=phi.device)
-        st = _stream_and_device(phi)
-        _lib.check(lib.lsf_reseed_points_device(p, m, nx, ny, nz, dx, lo.ctypes.data, pts.data_ptr() if npts else None,
-                                                rad.data_ptr() if npts else None, npts, per_cell, rmin, rmax, band, _SAMPLE_ORDERS[order], iters,
-                                                tol, useed, status.data_ptr() if npts else None, ctypes.byref(nout), info.ctypes.data, st))
-        n = nout.value
-        # (n,3) in Fortran order: the transpose of a contiguous (3,n)
-        out = torch.empty((3, n), dtype=torch.float64, device=phi.device)
-        orad = torch.empty(n, dtype=torch.float64, device=phi.device)
-        src = torch.empty(n, dtype=torch.int32, device=phi.device)
-        _lib.check(lib.lsf_reseed_get_device(out.data_ptr() if n else None, orad.data_ptr() if n else None, src.data_ptr() if n else None, st))
-        out = out.t()
-    else:
-        if rad is not None and (not isinstance(rad, np.ndarray) or rad.dtype != np.float64 or not rad.flags.c_contiguous):
-            raise TypeError("rad must be a contiguous float64 numpy array")
-        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        m = None if mask is None else _host_ptr(mask, np.int32, nx, ny, nz, "mask")
-        status = np.zeros(npts, dtype=np.int32)
-        _lib.check(lib.lsf_reseed_points(p, m, nx, ny, nz, dx, lo.ctypes.data, pts.ctypes.data if npts else None, rad.ctypes.data if npts else None,
-                                         npts, per_cell, rmin, rmax, band, _SAMPLE_ORDERS[order], iters, tol, useed,
-                                         status.ctypes.data if npts else None, ctypes.byref(nout), info.ctypes.data))
-        n = nout.value
-        out = np.zeros((n, 3), dtype=np.float64, order="F")
-        orad = np.zeros(n, dtype=np.float64)
-        src = np.zeros(n, dtype=np.int32)
-        _lib.check(lib.lsf_reseed_get(out.ctypes.data if n else None, orad.ctypes.data if n else None, src.ctypes.data if n else None))
+    status = s.out(npts, np.int32)
+    _lib.check(s.call("lsf_reseed_points", p, m, nx, ny, nz, dx, lo.ctypes.data, s.ptr(pts), s.ptr(rad), npts, per_cell, rmin, rmax, band, order,
+                      iters, tol, useed, s.ptr(status) if npts else None, ctypes.byref(nout), info.ctypes.data))
+    n = nout.value
+    out, orad, src = s.out3(n), s.out(n), s.out(n, np.int32)
+    _lib.check(s.call("lsf_reseed_get", *((s.ptr(out), s.ptr(orad), s.ptr(src)) if n else (None, None, None))))
     return ReseedReport(out, orad, src, status, tuple(int(v) for v in info))
 
 
@@ -1623,48 +1125,22 @@ def extractSurface(phi, nx: int, ny: int, nz: int, dx: float, xLo, *, iso: float
     tensor's current stream.  Triangle normals point towards phi >= iso; the numbering is a function of the field alone.  A level set
     that reaches the walls of the grid gives an open mesh; an empty one gives arrays with 0 rows.
     """
-    lo = np.ascontiguousarray(xLo, dtype=np.float64)
-    if lo.shape != (3,):
-        raise ValueError("xLo must hold 3 values")
-    dx, iso = float(dx), float(iso)
-    if not (np.isfinite(dx) and dx > 0.0):
-        raise ValueError("dx must be finite and > 0")
-    if not np.isfinite(iso):
-        raise ValueError("iso must be finite")
-    if min(int(nx), int(ny), int(nz)) < 1:
-        raise ValueError("nx, ny, nz must be >= 1")
-    dev = _is_torch(phi)
+    lo, dx, iso = _seam.xlo(xLo, finite=False), _seam.positive(dx), _seam.finite_iso(iso)
+    _seam.grid(nx, ny, nz)
+    s = Seam(phi, nx, ny, nz)
     nn, nt = ctypes.c_int(0), ctypes.c_int(0)
     info = np.zeros(_lib.LSF_SURF_INFO_LEN, dtype=np.int64)
-    if dev:
-        import torch
-
-        p = _dev_ptr(phi, torch.float64, nx, ny, nz, "phi")
-        lib = _lib.load()
-        st = _stream_and_device(phi)
-        _lib.check(lib.lsf_extract_surface_device(p, nx, ny, nz, dx, lo.ctypes.data, iso, ctypes.byref(nn), ctypes.byref(nt), info.ctypes.data, st))
-        # (n,3) in Fortran order: the transpose of a contiguous (3,n)
-        sX = torch.empty((3, nn.value), dtype=torch.float64, device=phi.device)
-        sE = torch.empty((3, nt.value), dtype=torch.int32, device=phi.device)
-        _lib.check(lib.lsf_extract_get_device(sX.data_ptr() if nn.value else None, sE.data_ptr() if nt.value else None, st))
-        sX, sE = sX.t(), sE.t()
-    else:
-        p = _host_ptr(phi, np.float64, nx, ny, nz, "phi")
-        lib = _lib.load()
-        _lib.check(lib.lsf_extract_surface(p, nx, ny, nz, dx, lo.ctypes.data, iso, ctypes.byref(nn), ctypes.byref(nt), info.ctypes.data))
-        sX = np.zeros((nn.value, 3), dtype=np.float64, order="F")
-        sE = np.zeros((nt.value, 3), dtype=np.int32, order="F")
-        _lib.check(lib.lsf_extract_get(sX.ctypes.data if nn.value else None, sE.ctypes.data if nt.value else None))
+    _lib.check(s.call("lsf_extract_surface", s.field(phi, "phi"), nx, ny, nz, dx, lo.ctypes.data, iso, ctypes.byref(nn), ctypes.byref(nt),
+                      info.ctypes.data))
+    sX, sE = s.out3(nn.value), s.out3(nt.value, np.int32)
+    _lib.check(s.call("lsf_extract_get", s.ptr(sX) if nn.value else None, s.ptr(sE) if nt.value else None))
     return sX, sE, SurfaceInfo(*(int(v) for v in info))
 
 
 def stlWrite(path, surfX, surfElem) -> None:
     """Binary STL from nodes + 1-based connectivity (include/lsf.h: lsf_stl_write): vertices rounded to float32, unit normals
     computed from the rounded vertices.  Host code only: no device is needed.  CUDA tensors are copied to the host first."""
-    if _is_torch(surfX):
-        surfX = surfX.cpu().numpy()
-    if _is_torch(surfElem):
-        surfElem = surfElem.cpu().numpy()
+    surfX, surfElem = (a.cpu().numpy() if _seam.is_torch(a) else a for a in (surfX, surfElem))
     sX, sE = _surface(surfX, surfElem)
     _lib.check(_lib.load().lsf_stl_write(os.fsencode(path), sX.ctypes.data, sX.shape[0], sE.ctypes.data, sE.shape[0]))
 
@@ -1676,23 +1152,13 @@ def advectNodes(phi, phiSB, nx: int, ny: int, nz: int, dx: float, xLo, surfXX, i
     return (this is what the host writes to the .s3d file, set3d.f90:606-608).  phi / phiSB as for minmaxFlow.
     Bit-identical to the reference (including subs.f90:346's repeated j+1 neighbour).
     """
-    lib = _lib.load()
     if not (isinstance(surfXX, np.ndarray) and surfXX.dtype == np.float64 and surfXX.ndim == 2
             and surfXX.shape[1] == 3 and surfXX.flags.f_contiguous and surfXX.flags.writeable):
         raise ValueError("surfXX must be a writeable Fortran-ordered float64 array of shape (nSurfNode, 3)")
     lo = np.ascontiguousarray(xLo, dtype=np.float64)
-    if _is_torch(phi):
-        import torch
-
-        st = _stream_and_device(phi)
-        rc = lib.lsf_advect_nodes_device(_dev_ptr(phi, torch.float64, nx, ny, nz, "phi"),
-                                         _dev_ptr(phiSB, torch.int32, nx, ny, nz, "phiSB"), nx, ny, nz, float(dx),
-                                         lo.ctypes.data, surfXX.ctypes.data, surfXX.shape[0], int(iter), st)
-    else:
-        rc = lib.lsf_advect_nodes(_host_ptr(phi, np.float64, nx, ny, nz, "phi"),
-                                  _host_ptr(phiSB, np.int32, nx, ny, nz, "phiSB"), nx, ny, nz, float(dx),
-                                  lo.ctypes.data, surfXX.ctypes.data, surfXX.shape[0], int(iter))
-    _lib.check(rc)
+    s = Seam(phi, nx, ny, nz)
+    _lib.check(s.call("lsf_advect_nodes", s.field(phi, "phi"), s.field(phiSB, "phiSB", np.int32), nx, ny, nz, float(dx), lo.ctypes.data,
+                      surfXX.ctypes.data, surfXX.shape[0], int(iter)))
 
 
 TRANSPORTS = {"peer": _lib.LSF_TRANSPORT_PEER, "rccl": _lib.LSF_TRANSPORT_RCCL, "mock": _lib.LSF_TRANSPORT_MOCK}
@@ -1726,17 +1192,14 @@ def reinit_multi(phi, nx: int, ny: int, nz: int, iter: int, dx: float, h: float,
     devs = (ctypes.c_int * len(devices))(*[int(d) for d in devices])
     dm = (ctypes.c_int * 3)(*[int(d) for d in dims]) if dims is not None else None
     f32 = isinstance(phi, np.ndarray) and phi.dtype == np.float32
-    p = _host_ptr(phi, np.float32 if f32 else np.float64, nx, ny, nz, "phi")
+    p = _seam.host_field(phi, "phi", np.float32 if f32 else np.float64, nx, ny, nz)  # a host call: the devices are named, not implied
     fn = lib.lsf_reinit_multi_f32 if f32 else lib.lsf_reinit_multi
     try:
         rc = fn(p, nx, ny, nz, int(iter), float(dx), float(h), float(tol), mode, devs, len(devices), dm, ctypes.byref(done),
                 trace.ctypes.data, cap)
     finally:
         lib.lsf_multi_defaults(old_ce.value, old_tr.value)
-    n = done.value
-    rep = SweepReport(n, [float(v) for v in trace[:n]], bool(n and trace[n - 1] < tol))
-    _lib.check(rc)
-    return rep
+    return _sweep_report(rc, done, trace, tol, 0, "", False)
 
 
 def peer_selftest(dev_a: int, dev_b: int) -> int:
