@@ -194,7 +194,7 @@ __device__ __forceinline__ double godunov_strict(double phic, double a, double b
     return __builtin_sqrt(gX + gY + gZ);
 }
 
-template <bool STRICT>
+template <bool STRICT, bool SK = false>
 __device__ __forceinline__ void axis_pair(const double q[7], bool weno_ok, bool yquirk, double dx, double floor2,
                                           double& dm, double& dp);
 template <bool STRICT>
@@ -255,9 +255,21 @@ __device__ __forceinline__ double rcp_nr(double x)
 //    m2 = (q0 q1)^2, D = n0 + 6 n1 + 3 m2 (one reciprocal per side), and the correction term is
 //        PW = 1/3 w0 (a-2b+c) + 1/6 (w2 - 1/2) (b-2c+d) = r (n0/3 Sa + m2/2 S0) - S0/12,   r = 1/D,
 //    so the weights themselves are never formed.
+//
+// SK (the three-lane march of lsf_skew.hpp only): the multipliers -3, 3 and 6 come from scalar register pairs.  As literals
+// they force the two-address v_fmac_f64 (VOP3 takes no literal on gfx950), and where the addend stays live -- t0p, t0m, the inner
+// FMA of Dp and Dm -- the compiler copies it first: three v_mov_b64 per marching step.  An empty asm statement pins each constant
+// to scalar registers and the same FMAs become three-address v_fma_f64 without a copy.  The same operations on the same values.
+template <bool SK = false>
 __device__ __forceinline__ void weno_axis_fast(const double q[7], double floor2, bool yquirk, double& dm,
                                                double& dp)
 {
+    double km3 = -3.0, k3 = 3.0, k6 = 6.0;
+    if constexpr (SK) {
+        asm volatile("" : "+s"(km3));
+        asm volatile("" : "+s"(k3));
+        asm volatile("" : "+s"(k6));
+    }
     // first differences d_k = q[k+1]-q[k]  (p_k * dx)
     const double d0 = q[1] - q[0], d1 = q[2] - q[1], d2 = q[3] - q[2];
     const double d3 = q[4] - q[3], d4 = q[5] - q[4], d5 = q[6] - q[5];
@@ -265,8 +277,8 @@ __device__ __forceinline__ void weno_axis_fast(const double q[7], double floor2,
     const double am = d1 - d0, bm = d2 - d1, cp = d3 - d2, bp = d4 - d3, ap = d5 - d4;
     // the four distinct differences of second differences and the six linear forms of the indicators
     const double e_ab = ap - bp, e_bc = bp - cp, e_cm = cp - bm, e_mm = am - bm;
-    const double t0p = __builtin_fma(-3.0, bp, ap), t1p = bp + cp, t2p = __builtin_fma(3.0, cp, -bm);
-    const double t0m = __builtin_fma(-3.0, bm, am), t1m = bm + cp, t2m = __builtin_fma(3.0, cp, -bp);
+    const double t0p = __builtin_fma(km3, bp, ap), t1p = bp + cp, t2p = __builtin_fma(k3, cp, -bm);
+    const double t0m = __builtin_fma(km3, bm, am), t1m = bm + cp, t2m = __builtin_fma(k3, cp, -bp);
 
     // eps = 1e-6 max(p^2) + 1e-99 (subs.f90:533-534), in unscaled units and times 1/3 like the IS below (floor2 is the
     // floor divided by 13: times 13/3 here); max of squares = square of the max magnitude (|x| is a free modifier)
@@ -299,8 +311,8 @@ __device__ __forceinline__ void weno_axis_fast(const double q[7], double floor2,
     const double t12m = q1m * q2m, t02m = q0m * q2m, t01m = q0m * q1m;
     const double n0p = t12p * t12p, n1p = t02p * t02p, m2p = t01p * t01p;
     const double n0m = t12m * t12m, n1m = t02m * t02m, m2m = t01m * t01m;
-    const double Dp = __builtin_fma(3.0, m2p, __builtin_fma(6.0, n1p, n0p));
-    const double Dm = __builtin_fma(3.0, m2m, __builtin_fma(6.0, n1m, n0m));
+    const double Dp = __builtin_fma(k3, m2p, __builtin_fma(k6, n1p, n0p));
+    const double Dm = __builtin_fma(k3, m2m, __builtin_fma(k6, n1m, n0m));
     const double R = rcp_nr(__builtin_fmax(Dp * Dm, 1e-300));
     const double rp = Dm * R, rm = Dp * R;
     const double Sap = e_ab - e_bc; // ap - 2bp + cp
@@ -404,7 +416,8 @@ __device__ __forceinline__ double cell_update(const double qx[7], const double q
 // one cell are computed by three lanes of a quad).  Same expressions as cell_update_* above.
 // ---------------------------------------------------------------------------------------------
 // one-sided derivatives along one axis: STRICT -> true values (a,b); FAST -> values * dx
-template <bool STRICT>
+// SK: see weno_axis_fast (FAST only; nothing in the STRICT arithmetic changes with it)
+template <bool STRICT, bool SK>
 __device__ __forceinline__ void axis_pair(const double q[7], bool weno_ok, bool yquirk, double dx, double floor2,
                                           double& dm, double& dp)
 {
@@ -419,7 +432,7 @@ __device__ __forceinline__ void axis_pair(const double q[7], bool weno_ok, bool 
         }
     } else {
         if (weno_ok) {
-            weno_axis_fast(q, floor2, yquirk, dm, dp);
+            weno_axis_fast<SK>(q, floor2, yquirk, dm, dp);
         } else {
             dm = q[3] - q[2];
             dp = q[4] - q[3];
@@ -471,7 +484,7 @@ __device__ __forceinline__ double axis_term(const double q[7], bool weno_ok, boo
 {
     double dm, dp;
     if (weno_ok) {
-        axis_pair<STRICT>(q, true, yquirk, dx, floor2, dm, dp);
+        axis_pair<STRICT, true>(q, true, yquirk, dx, floor2, dm, dp);
         return axis_godunov_sel<STRICT>(q[3], dm, dp);
     }
     axis_pair<STRICT>(q, false, yquirk, dx, floor2, dm, dp);

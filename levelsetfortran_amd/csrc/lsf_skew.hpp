@@ -227,6 +227,34 @@ struct SkShared {
     double wsum[T::W];
 };
 
+// Step masks of a lane (skew_tile): bit t is set for the marching steps lo_t <= t < hi_t of the TA <= 32 a tile has.
+__host__ __device__ constexpr unsigned sk_step_mask(int lo_t, int hi_t, int ta)
+{
+    lo_t = lo_t > 0 ? lo_t : 0, lo_t = lo_t < ta ? lo_t : ta; // min(max(lo_t, 0), ta): the device's min and max are no constant expressions
+    hi_t = hi_t > lo_t ? hi_t : lo_t, hi_t = hi_t < ta ? hi_t : ta;
+    return (unsigned)(((1ull << hi_t) - 1ull) & ~((1ull << lo_t) - 1ull));
+}
+// The same mask with step 0 in bit 31 (three lanes per cell): the march doubles it once per step, and the carry of that one
+// addition (v_add_co_u32) is the step's lane mask -- no shift, no AND, no compare.
+__host__ __device__ constexpr unsigned sk_step_mask_rev(unsigned m) { return __builtin_bitreverse32(m); }
+// sixteen doublings of the reversed mask hand out the bits of the mask itself, step 0 first (all 0 <= lo <= hi <= 16)
+constexpr bool sk_carry_chain_ok()
+{
+    for (int lo = 0; lo <= 16; ++lo)
+        for (int hi = lo; hi <= 16; ++hi) {
+            const unsigned m = sk_step_mask(lo, hi, 16);
+            unsigned r = sk_step_mask_rev(m);
+            for (int t = 0; t < 16; ++t) {
+                const bool carry = (r >> 31) != 0u; // what __builtin_add_overflow(r, r, &r) returns
+                r += r;
+                if (carry != (((m >> t) & 1u) != 0u)) return false;
+            }
+            if (r != 0u) return false;
+        }
+    return true;
+}
+static_assert(sk_carry_chain_ok(), "the carries of the reversed step mask are the bits of the step mask, in order");
+
 // The LDS offsets of a lane's stencil at step 0 (skew_tile).  Functions, not lambdas of skew_tile: captured by reference inside the
 // loaders' lambdas the arrays went to scratch memory.
 // Three lanes per cell: index of the stencil value mm - 3 along the lane's axis.
@@ -435,10 +463,7 @@ __device__ __forceinline__ bool skew_tile(SkShared<SkTile<TA, WY, WZ, BY>>& sm, 
     const int fx0 = X0 - bc - cc;
     double acc = 0.0;
     // per-lane bit t: the cell of step t exists (0 <= fx0 + t < nxi) / takes the WENO branch (3 < gi < nx - 4)
-    auto step_mask = [](int lo_t, int hi_t) { // bits lo_t .. hi_t - 1 of 16
-        lo_t = min(max(lo_t, 0), TA), hi_t = min(max(hi_t, lo_t), TA);
-        return (unsigned)(((1ull << hi_t) - 1ull) & ~((1ull << lo_t) - 1ull));
-    };
+    auto step_mask = [](int lo_t, int hi_t) { return sk_step_mask(lo_t, hi_t, TA); }; // bits lo_t .. hi_t - 1 of 16
     const unsigned act_bits = row_ok ? step_mask(-fx0, nxi - fx0) : 0u;
     // 3 < gi < nx - 4 with gi = 1 + fx (si > 0: 2 < fx < nx - 5) or gi = nx - 1 - fx (si < 0: 3 < fx < nx - 4)
     const unsigned weno_bits = yz_weno ? step_mask((si > 0 ? 3 : 4) - fx0, (si > 0 ? nx - 5 : nx - 4) - fx0) : 0u;
@@ -457,6 +482,15 @@ __device__ __forceinline__ bool skew_tile(SkShared<SkTile<TA, WY, WZ, BY>>& sm, 
         yquirk = axis == a.quirk_axis;
         row_core = T::core_at(cc * NYT + bc) + 3;
         sk_lane_offsets3<T>(axis, si, sj, sk, deep, pre, bc, cc, nj, nk, off);
+    }
+    // three lanes per cell: the two step masks with step 0 in bit 31, `axis == 0` (only the x lane of a cell runs the tail of
+    // the update) folded into the first; the march shifts them out by one addition per step (sk_step_mask_rev)
+    [[maybe_unused]] unsigned act_rev = 0u, weno_rev = 0u;
+    if constexpr (BY == 5) {
+        static_assert(TA <= 32, "one bit per marching step");
+        act_rev = axis == 0 ? sk_step_mask_rev(act_bits) : 0u;
+        weno_rev = sk_step_mask_rev(weno_bits);
+        asm volatile("" : "+v"(act_rev), "+v"(weno_rev)); // formed here, in front of the loads, not inside the first marching step
     }
     // Wide path: a deep tile (full, every row of its image an interior row) whose image also stays inside the grid along the
     // march axis -- entries 0 .. 22 of every row are interior cells -- needs no clamp, no interior test and no choice between
@@ -642,14 +676,14 @@ __device__ __forceinline__ bool skew_tile(SkShared<SkTile<TA, WY, WZ, BY>>& sm, 
 #pragma unroll
             for (int t = 0; t < TA; ++t) {
                 LSF_SK_MID(t);
-                const bool active = (bool)((act_bits >> t) & 1u) && axis == 0;
+                const bool active = __builtin_add_overflow(act_rev, act_rev, &act_rev); // bit t of act_bits, x lane only
                 double q[7];
 #pragma unroll
                 for (int mm = 0; mm < 7; ++mm) q[mm] = lds[off[mm] + t];
                 // phiS of step t at the x lane: its own third, or the y / z lane's (row_shl:1, row_shl:2 -- in front of the branch
                 // on `active`: a lane that is switched off cannot be a source)
                 const double pS = t < NPS ? ps[t] : (t < 2 * NPS ? dpp_mov<0x101>(ps[t - NPS]) : dpp_mov<0x102>(ps[t - 2 * NPS]));
-                const bool weno_ok = (bool)((weno_bits >> t) & 1u);
+                const bool weno_ok = __builtin_add_overflow(weno_rev, weno_rev, &weno_rev); // bit t of weno_bits
                 const double gg = axis_term<STRICT>(q, weno_ok, yquirk, dx, floor2);
                 const double gX = gg, gY = dpp_mov<0x101>(gg), gZ = dpp_mov<0x102>(gg); // row_shl:1, row_shl:2
                 if (active) { // only the x lane of a cell needs the tail (|grad|, sign, Euler step)

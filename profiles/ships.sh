@@ -19,7 +19,8 @@ for CFG in "$@"; do
     # requests of the L2s to the fabric BY SIZE (FETCH_SIZE counts a request as 64 bytes whatever its size)
     [ $P = RDREQ ] && C="TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum"
     [ $P = WRREQ ] && C="TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum"
-    rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$D/$P" -- python3 bench.py --size $N --steps $K --warmup $K --arith $A --mode $M --no-cpu-baseline --no-secondary > "$D.$P.json" 2> "$D.$P.log"
+    # (a pass that fails ends the script: nothing more is started on a device that may have faulted)
+    timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$D/$P" -- python3 bench.py --size $N --steps $K --warmup $K --arith $A --mode $M --no-cpu-baseline --no-secondary > "$D.$P.json" 2> "$D.$P.log" || { echo "$CFG $P failed ($?)" >&2; tail -20 "$D.$P.log" >&2; exit 1; }
     echo "$CFG $P done" >&2
   done
   echo "$N $A $M $((2 * K))" >> "$OUT/configs.txt"
