@@ -3,21 +3,17 @@
 //
 // One lane per point, in the caller's order (k_advect_points, AP_BLOCK lanes per block, one block per AP_BLOCK consecutive points).
 // The loop over the steps runs inside the kernel; the stages of a step are one loop whose body holds the one inlined sample
-// (ap_rhs): sp_locate of lsf_sample_points.hpp, the joint stencil rule, the band rule with its loads side by side (cr_in_band of
-// lsf_cast_rays.hpp), sp_stencil -- unchanged -- for the value and gradient of phi with the value of speed, and ap_stencil3, the
-// value-only contraction of u, v and w under one set of weights, which repeats the operations of sp_stencil's value so that each
-// component equals val of tests/sample_ref.py bit for bit.  Everything is evaluated as the header writes it, left to right, without
-// contraction: the result is the numpy statement's (tests/points_ref.py) bit for bit.
+// (ap_rhs): pt_sample of lsf_point_stencil.hpp -- locate, the joint stencil rule, the band rule -- with ap_eval on the admitted
+// stencil: sp_stencil for the value and gradient of phi with the value of speed, and pt_values3 for u, v and w under one set of
+// weights, so that each component equals val of tests/sample_ref.py bit for bit.  Everything is evaluated as the header writes it,
+// left to right, without contraction: the result is the numpy statement's (tests/points_ref.py) bit for bit.
 //
 // Bounded.  The step loop runs at most nsteps <= LSF_ADVECT_POINTS_MAX_STEPS trips of at most 3 stages; a point that fails leaves
 // it.  No lane waits for another block; no value of a field, NaN included, can keep a lane.
 //
-// Bounds.  The INSIDE test of sp_locate, made in double BEFORE any conversion to an integer, is the only thing between a wild
-// position and an out-of-bounds load: it is the first thing ap_rhs does for every position of every stage, and a position that fails
-// it (NaN or inf born of a non-finite field value included) returns before an index exists.  Behind it sp_stencil's own argument
-// holds: corners i0, i0 + 1 in 0..n, cubic only where 1 <= i0 <= n - 2.  u, v, w and speed are fields of the size of phi and are
-// read at sp_stencil's offsets only.  Loads and stores of pts and status go to the lane's own entries t, t + npts, t + 2 npts
-// (64-bit) of arrays of 3 npts and npts entries.  Lanes with t >= npts touch no memory.
+// Bounds: "Bounds" of lsf_point_stencil.hpp, for every position of every stage.  u, v, w and speed are fields of the size of phi.
+// Loads and stores of pts and status go to the lane's own entries t, t + npts, t + 2 npts (64-bit) of arrays of 3 npts and npts
+// entries.  Lanes with t >= npts touch no memory.
 //
 // The report: per block the six counts of info and the bit pattern of the block's cfl (the per-lane integers through wave_usum_each,
 // the cfl through wave_umax_x and block_umax, whose barrier also publishes the counts), finished by the host in block order.
@@ -28,8 +24,7 @@
 
 #include "../../include/lsf.h"
 #include "lsf_block_reduce.hpp"
-#include "lsf_cast_rays.hpp"
-#include "lsf_sample_points.hpp"
+#include "lsf_point_stencil.hpp"
 
 namespace lsf {
 
@@ -40,49 +35,16 @@ struct ApFields {
     const double *u, *v, *w, *speed;
 };
 
-// The values of three fields on the K^3 stencil whose lowest point is lo, under one set of weights: sp_stencil's value, three times.
-template <bool CUBIC>
-__device__ __forceinline__ void ap_stencil3(const SpGrid& G, const ApFields& F, const int (&lo)[3], const double (&t)[3], double (&U)[3])
-{
-#pragma clang fp contract(off)
-    constexpr int K = CUBIC ? 4 : 2;
-    const long rs = (long)G.nx + 1, ps = rs * ((long)G.ny + 1);
-    const long base = (long)lo[0] + rs * (long)lo[1] + ps * (long)lo[2];
-    double wx[K], wy[K], wz[K], dd[K];
-    sp_weights<CUBIC>(t[0], wx, dd);
-    sp_weights<CUBIC>(t[1], wy, dd);
-    sp_weights<CUBIC>(t[2], wz, dd);
-    const double* __restrict__ f[3] = {F.u + base, F.v + base, F.w + base};
-    double p[3][K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) {
-        double r[3][K];
-#pragma unroll
-        for (int b = 0; b < K; ++b)
-#pragma unroll
-            for (int m = 0; m < 3; ++m) {
-                double a[K];
-#pragma unroll
-                for (int i = 0; i < K; ++i) a[i] = f[m][i + rs * b + ps * c];
-                r[m][b] = sp_dot<K>(wx, a);
-            }
-#pragma unroll
-        for (int m = 0; m < 3; ++m) p[m][c] = sp_dot<K>(wy, r[m]);
-    }
-#pragma unroll
-    for (int m = 0; m < 3; ++m) U[m] = sp_dot<K>(wz, p[m]);
-}
-
 // K on an admitted stencil: LSF_POINTS_OK or LSF_POINTS_FLAT
 template <bool CUBIC, bool HAS_VEL, bool HAS_SPEED>
 __device__ __forceinline__ int ap_eval(const SpGrid& G, const ApFields& F, const int (&lo)[3], const double (&t)[3], double (&k)[3])
 {
 #pragma clang fp contract(off)
     double U[3] = {0., 0., 0.};
-    if constexpr (HAS_VEL) ap_stencil3<CUBIC>(G, F, lo, t, U);
+    if constexpr (HAS_VEL) pt_values3<CUBIC>(G, F.u, F.v, F.w, lo, t, U);
     if constexpr (HAS_SPEED) {
         SpSample s;
-        sp_stencil<CUBIC, true, false>(G, F.speed, lo, t, s);
+        sp_stencil<CUBIC, true>(G, F.speed, lo, t, s);
         const double m = (s.g0 * s.g0 + s.g1 * s.g1) + s.g2 * s.g2;
         if (m == 0.0) return LSF_POINTS_FLAT;
         const double nrm = __builtin_sqrt(m);
@@ -95,37 +57,20 @@ __device__ __forceinline__ int ap_eval(const SpGrid& G, const ApFields& F, const
     return LSF_POINTS_OK;
 }
 
-// One sample of the right-hand side at (x, y, z): LSF_POINTS_OK, _OUTSIDE, _OFFBAND or _FLAT; k and linear are written on OK only.
+// One sample of the right-hand side at (x, y, z): LSF_POINTS_OK, _OUTSIDE, _OFFBAND or _FLAT; k is written on OK only, linear on OK and on FLAT.
 template <bool CUBIC, bool HAS_VEL, bool HAS_SPEED, bool HAS_MASK>
 __device__ __forceinline__ int ap_rhs(const SpGrid& G, const ApFields& F, double x, double y, double z, double (&k)[3], bool& linear)
 {
-    int i0[3];
-    double t[3];
-    // The INSIDE test comes first: nothing below may run for a position that fails it (see "Bounds" above).
-    if (!sp_locate(x, G.x0, G.dx, G.nx, i0[0], t[0]) || !sp_locate(y, G.y0, G.dx, G.ny, i0[1], t[1]) ||
-        !sp_locate(z, G.z0, G.dx, G.nz, i0[2], t[2]))
-        return LSF_POINTS_OUTSIDE;
-    if constexpr (CUBIC) {
-        // the joint rule: cubic only where 1 <= i0 <= n - 2 on all three axes, so that i0 - 1 >= 0 and i0 + 2 <= n
-        if (i0[0] >= 1 && i0[0] <= G.nx - 2 && i0[1] >= 1 && i0[1] <= G.ny - 2 && i0[2] >= 1 && i0[2] <= G.nz - 2) {
-            const int lo[3] = {i0[0] - 1, i0[1] - 1, i0[2] - 1};
-            if constexpr (HAS_MASK)
-                if (!cr_in_band<4>(G, lo)) return LSF_POINTS_OFFBAND;
-            linear = false;
-            return ap_eval<true, HAS_VEL, HAS_SPEED>(G, F, lo, t, k);
-        }
-    }
-    if constexpr (HAS_MASK)
-        if (!cr_in_band<2>(G, i0)) return LSF_POINTS_OFFBAND;
-    linear = true;
-    return ap_eval<false, HAS_VEL, HAS_SPEED>(G, F, i0, t, k);
+    return pt_sample<CUBIC, HAS_MASK, false>(G, x, y, z, linear, [&](auto cubic, const int(&lo)[3], const double(&t)[3]) __attribute__((always_inline)) {
+        return ap_eval<decltype(cubic)::value, HAS_VEL, HAS_SPEED>(G, F, lo, t, k);
+    });
 }
 
 __device__ __forceinline__ bool ap_inside(const SpGrid& G, double x, double y, double z)
 {
     int i;
     double t;
-    return sp_locate(x, G.x0, G.dx, G.nx, i, t) && sp_locate(y, G.y0, G.dx, G.ny, i, t) && sp_locate(z, G.z0, G.dx, G.nz, i, t);
+    return pt_locate<false>(x, G.x0, G.dx, G.nx, i, t) && pt_locate<false>(y, G.y0, G.dx, G.ny, i, t) && pt_locate<false>(z, G.z0, G.dx, G.nz, i, t);
 }
 
 // Point t of block blockIdx.x.  pts: (npts, 3) in Fortran order, in and out.  status may be NULL.  part: AP_NPART words per block.
@@ -153,7 +98,6 @@ __global__ __launch_bounds__(AP_BLOCK) void k_advect_points(SpGrid G, ApFields F
                 for (int sg = 0; sg < nstage; ++sg) {
                     double k[3];
                     bool lin = false;
-                    // the position passes the INSIDE test of ap_rhs before anything is loaded for it
                     why = ap_rhs<CUBIC, HAS_VEL, HAS_SPEED, HAS_MASK>(G, F, y0, y1, y2, k, lin);
                     if (why != LSF_POINTS_OK) break;
                     if (CUBIC && lin) ++nfall;

@@ -36,6 +36,7 @@
 #include "lsf_extract_surface.hpp"
 #include "lsf_measure_band.hpp"
 #include "lsf_cut_cells_band.hpp"
+#include "lsf_point_stencil.hpp"
 #include "lsf_sample_points.hpp"
 #include "lsf_cast_rays.hpp"
 #include "lsf_advect_points.hpp"
@@ -754,6 +755,7 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_measure_band.hpp"
 #include "lsf_host_cut_cells_band.hpp"
 
+#include "lsf_host_point_launch.hpp"
 #include "lsf_host_sample_points.hpp"
 #include "lsf_host_cast_rays.hpp"
 #include "lsf_host_points.hpp"

@@ -1,4 +1,4 @@
-// lsf_block_reduce.hpp -- the order-free reductions of the band kernels: integer sums, and maxima and minima of bit patterns.
+// lsf_block_reduce.hpp -- the order-free reductions of the band and point kernels: integer sums, and maxima and minima of bit patterns.
 //
 // Whatever order the operands meet in, the result is the same, so none of these reaches a statement: a kernel may use them for a
 // count, or for the largest or smallest of non-negative doubles taken as their bit patterns (as unsigned integers these order like
@@ -26,6 +26,9 @@ __device__ __forceinline__ T wave_usum(T v)
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+
+// the number of lanes of the wave whose flag is set, in every lane: one ballot and one population count, both scalar
+__device__ __forceinline__ unsigned long long wave_count(bool f) { return (unsigned long long)__popcll(__ballot(f)); }
 
 // butterfly maximum over the 64 lanes, the lane exchanges of wave_sum_x (lsf_kernels.hpp): no LDS round trips
 __device__ __forceinline__ unsigned long long wave_umax_x(unsigned long long v)
@@ -88,13 +91,15 @@ __device__ __forceinline__ T block_usum(T v, int tid)
     return v;
 }
 
-// the block's sums of N per-lane counters, written by thread 0 to out[0 .. N)
-template <int NW, typename T, int N>
+// the block's sums of N per-lane counters, written by thread 0 to out[0 .. N).  PER_WAVE: v already holds the wave's totals
+// (wave_count, wave_usum) and only the waves are added.
+template <int NW, bool PER_WAVE = false, typename T, int N>
 __device__ __forceinline__ void block_usum_out(T (&v)[N], int tid, T* out)
 {
     __shared__ T red[NW][N];
+    if constexpr (!PER_WAVE)
 #pragma unroll
-    for (int m = 0; m < N; ++m) v[m] = wave_usum(v[m]);
+        for (int m = 0; m < N; ++m) v[m] = wave_usum(v[m]);
     if ((tid & 63) == 0)
 #pragma unroll
         for (int m = 0; m < N; ++m) red[tid >> 6][m] = v[m];

@@ -5,9 +5,9 @@
 //   k_cf_init     plus = minus = key(phi) at every point of the list (with a mask) or of the grid, key the order-preserving 64-bit
 //                 transform b ^ (b >> 63 ? ~0 : 1 << 63) of the bit pattern b: unsigned comparison of keys is the total order of the
 //                 doubles, -0.0 below +0.0.
-//   k_cf_scatter  one lane per particle, in the caller's order: classifies it (radius, sp_locate, the band rule on the 8 corners of
-//                 its cell by cr_in_band, the LINEAR value by sp_stencil, unchanged, read from phi itself -- phi is not written
-//                 until the merge, so that IS the field as it was on entry) and, for an escaped particle, offers cand = s (r - d) to
+//   k_cf_scatter  one lane per particle, in the caller's order: classifies it (radius, pt_locate, the band rule on the 8 corners of
+//                 its cell by pt_in_band, the LINEAR value by sp_stencil -- all of lsf_point_stencil.hpp -- read from phi itself: phi
+//                 is not written until the merge, so that IS the field as it was on entry) and, for an escaped particle, offers cand = s (r - d) to
 //                 the 8 corners: atomicMax on plus for s > 0, atomicMin on minus otherwise, on unsigned long long, each filtered by
 //                 a plain read first (a stale value only lets a useless atomic through).  Maxima and minima of integers: the result
 //                 is a function of the set of particles, not of their order.  No floating-point atomic, no CAS loop.
@@ -15,9 +15,9 @@
 //                 of such points and the largest fabs(new - old) as a bit pattern, per block, then one atomicAdd and one atomicMax of
 //                 integers per block that has something to report.
 //
-// Bounds.  A particle reaches k_cf_scatter's loads only behind the INSIDE test of sp_locate, made in double BEFORE any conversion
-// to an integer; behind it 0 <= i0 <= n - 1 on each axis and the 8 corners i0, i0 + 1 lie in 0..n: they are the points whose mask
-// and phi are read and whose keys are offered to, at 64-bit offsets below (nx+1)(ny+1)(nz+1), the size of both key fields.  Under a
+// Bounds.  A particle reaches k_cf_scatter's loads only behind pt_locate ("Bounds" of lsf_point_stencil.hpp): the 8 corners
+// i0, i0 + 1 are the points whose mask and phi are read and whose keys are offered to, at 64-bit offsets below
+// (nx+1)(ny+1)(nz+1), the size of both key fields.  Under a
 // mask an escaped particle's 8 corners are all in the list (interior points with mask == 1), so every key it touches was set by
 // k_cf_init.  A list entry is an interior point index below the number of points (lsf_band_cell.hpp).  Lanes with t >= npts, or
 // e beyond the list or the grid, touch no memory.  No loop waits for another block; every loop has 8 trips.
@@ -27,8 +27,7 @@
 
 #include "../../include/lsf.h"
 #include "lsf_block_reduce.hpp"
-#include "lsf_cast_rays.hpp"
-#include "lsf_sample_points.hpp"
+#include "lsf_point_stencil.hpp"
 
 namespace lsf {
 
@@ -74,14 +73,14 @@ __global__ __launch_bounds__(CF_BLOCK) void k_cf_scatter(SpGrid G, const double*
         if (!__builtin_isfinite(ra) || ra == 0.0)
             st = LSF_CORRECT_BADRADIUS;
         // The INSIDE test comes first: nothing below may run for a particle that fails it (see "Bounds" above).
-        else if (!sp_locate(x[0], G.x0, G.dx, G.nx, i0[0], tt[0]) || !sp_locate(x[1], G.y0, G.dx, G.ny, i0[1], tt[1]) ||
-                 !sp_locate(x[2], G.z0, G.dx, G.nz, i0[2], tt[2]))
+        else if (!pt_locate<false>(x[0], G.x0, G.dx, G.nx, i0[0], tt[0]) || !pt_locate<false>(x[1], G.y0, G.dx, G.ny, i0[1], tt[1]) ||
+                 !pt_locate<false>(x[2], G.z0, G.dx, G.nz, i0[2], tt[2]))
             st = LSF_CORRECT_OUTSIDE;
-        else if (HAS_MASK && !cr_in_band<2>(G, i0))
+        else if (HAS_MASK && !pt_in_band<2>(G, i0))
             st = LSF_CORRECT_OFFBAND;
         else {
             SpSample o;
-            sp_stencil<false, false, false>(G, nullptr, i0, tt, o);
+            sp_stencil<false, false>(G, nullptr, i0, tt, o);
             const double r = __builtin_fabs(ra), s = ra > 0.0 ? 1. : -1.;
             if (!__builtin_isfinite(o.v))
                 st = LSF_CORRECT_NONFINITE;

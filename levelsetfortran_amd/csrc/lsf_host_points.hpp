@@ -10,43 +10,22 @@ int advect_points_core(const double* d_u, const double* d_v, const double* d_w, 
                        int32_t* d_status, double* cfl, int64_t* info, hipStream_t st)
 {
     int rc;
-    Ctx& c = ctx();
-    const int nblocks = (int)(((size_t)npts + AP_BLOCK - 1) / AP_BLOCK);
-    if ((rc = ws(c.slot[S_PART], (size_t)nblocks * AP_NPART * sizeof(unsigned long long)))) return rc;
-    unsigned long long* part = (unsigned long long*)c.slot[S_PART].p;
+    PointPlan pp;
+    if ((rc = point_plan(pp, (size_t)npts, AP_BLOCK, AP_NPART))) return rc;
     const SpGrid G{d_phi, d_mask, nx, ny, nz, dx, xLo[0], xLo[1], xLo[2]};
     const ApFields F{d_u, d_v, d_w, d_speed};
     const int euler = scheme == LSF_ADVECT_EULER;
-    const dim3 grid((unsigned)nblocks), blk(AP_BLOCK);
-#define LSF_AP_CALL(CU, HV, HS, HM) \
-    hipLaunchKernelGGL((k_advect_points<CU, HV, HS, HM>), grid, blk, 0, st, G, F, d_pts, npts, euler, dt, nsteps, d_status, part)
-#define LSF_AP_GROUPS(CU, HM)                            \
-    do {                                                 \
-        if (d_u && d_speed) LSF_AP_CALL(CU, true, true, HM); \
-        else if (d_u) LSF_AP_CALL(CU, true, false, HM);  \
-        else LSF_AP_CALL(CU, false, true, HM);           \
-    } while (0)
-    switch ((order == LSF_SAMPLE_CUBIC ? 2 : 0) | (d_mask ? 1 : 0)) {
-    case 0: LSF_AP_GROUPS(false, false); break;
-    case 1: LSF_AP_GROUPS(false, true); break;
-    case 2: LSF_AP_GROUPS(true, false); break;
-    default: LSF_AP_GROUPS(true, true); break;
-    }
-#undef LSF_AP_GROUPS
-#undef LSF_AP_CALL
+    with_flags(
+        [&](auto CU, auto HV, auto HS, auto HM) {
+            if constexpr (decltype(HV)::value || decltype(HS)::value) // (advect_points_args_ok refuses a call with neither)
+                hipLaunchKernelGGL((k_advect_points<decltype(CU)::value, decltype(HV)::value, decltype(HS)::value, decltype(HM)::value>),
+                                   dim3((unsigned)pp.nblocks), dim3(AP_BLOCK), 0, st, G, F, d_pts, npts, euler, dt, nsteps, d_status, pp.part);
+        },
+        order == LSF_SAMPLE_CUBIC, d_u != nullptr, d_speed != nullptr, d_mask != nullptr);
     HIPCHK(hipGetLastError());
-    std::vector<unsigned long long> h((size_t)nblocks * AP_NPART);
-    HIPCHK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    unsigned long long tot[AP_NPART] = {0, 0, 0, 0, 0, 0, 0};
-    for (int b = 0; b < nblocks; ++b) { // block order: integer sums and a maximum of bit patterns
-        const unsigned long long* p = &h[(size_t)b * AP_NPART];
-        for (int m = 0; m < LSF_ADVECT_POINTS_INFO_LEN; ++m) tot[m] += p[m];
-        tot[LSF_ADVECT_POINTS_INFO_LEN] = std::max(tot[LSF_ADVECT_POINTS_INFO_LEN], p[LSF_ADVECT_POINTS_INFO_LEN]);
-    }
+    unsigned long long tot[AP_NPART]; // the counts of info, then the largest cfl of a block as a bit pattern
+    if ((rc = block_counts_finish(pp.part, pp.nblocks, AP_NPART, tot, info, st, true))) return rc;
     if (cfl) std::memcpy(cfl, &tot[LSF_ADVECT_POINTS_INFO_LEN], sizeof(double));
-    if (info)
-        for (int m = 0; m < LSF_ADVECT_POINTS_INFO_LEN; ++m) info[m] = (int64_t)tot[m];
     if (getenv("LSF_TRACE"))
         fprintf(stderr, "[lsf] points: %d points, %d steps asked, %llu ok, %llu outside, %llu off the band, %llu flat; %llu steps made, %llu linear fallbacks\n",
                 npts, nsteps, tot[0], tot[1], tot[2], tot[3], tot[4], tot[5]);
@@ -73,16 +52,16 @@ int correct_field_core(double* d_phi, const int32_t* d_mask, int nx, int ny, int
             L = bl.L;
         }
     }
-    const int nblocks = (int)(((size_t)npts + CF_BLOCK - 1) / CF_BLOCK);
+    PointPlan pp;
     if ((rc = ws(c.slot[S_CF_PLUS], n * sizeof(unsigned long long)))) return rc;
     if ((rc = ws(c.slot[S_CF_MINUS], n * sizeof(unsigned long long)))) return rc;
     if ((rc = ws(c.slot[S_CF_CTL], 2 * sizeof(unsigned long long)))) return rc;
-    if ((rc = ws(c.slot[S_PART], (size_t)nblocks * CF_NPART * sizeof(unsigned long long)))) return rc;
+    if ((rc = point_plan(pp, (size_t)npts, CF_BLOCK, CF_NPART))) return rc;
     unsigned long long *plus = (unsigned long long*)c.slot[S_CF_PLUS].p, *minus = (unsigned long long*)c.slot[S_CF_MINUS].p;
-    unsigned long long *ctl = (unsigned long long*)c.slot[S_CF_CTL].p, *part = (unsigned long long*)c.slot[S_PART].p;
+    unsigned long long *ctl = (unsigned long long*)c.slot[S_CF_CTL].p, *part = pp.part;
     HIPCHK(hipMemsetAsync(ctl, 0, 2 * sizeof(unsigned long long), st));
     const SpGrid G{d_phi, d_mask, nx, ny, nz, dx, xLo[0], xLo[1], xLo[2]};
-    const dim3 blk(CF_BLOCK), gw((unsigned)((nwork + CF_BLOCK - 1) / CF_BLOCK)), gp((unsigned)nblocks);
+    const dim3 blk(CF_BLOCK), gw((unsigned)((nwork + CF_BLOCK - 1) / CF_BLOCK)), gp((unsigned)pp.nblocks);
     if (nwork) {
         if (d_mask)
             hipLaunchKernelGGL((k_cf_init<true>), gw, blk, 0, st, (const double*)d_phi, L, nwork, plus, minus);
@@ -104,7 +83,7 @@ int correct_field_core(double* d_phi, const int32_t* d_mask, int nx, int ny, int
     unsigned long long hctl[2];
     HIPCHK(hipMemcpyAsync(hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
     unsigned long long tot[CF_NPART];
-    if ((rc = block_counts_finish(part, nblocks, CF_NPART, tot, nullptr, st))) return rc; // (lsf_host_sample_points.hpp; synchronises)
+    if ((rc = block_counts_finish(part, pp.nblocks, CF_NPART, tot, nullptr, st))) return rc; // (synchronises)
     if (change) std::memcpy(change, &hctl[1], sizeof(double));
     if (info) {
         for (int m = 0; m < CF_NPART; ++m) info[m] = (int64_t)tot[m];

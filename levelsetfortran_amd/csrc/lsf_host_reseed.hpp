@@ -45,7 +45,8 @@ int reseed_core(const double* d_phi, const int32_t* d_mask, int nx, int ny, int 
     if ((rc = ws(c.slot[S_RS_OLD], std::max(np, (size_t)1) * (sizeof(double) + sizeof(uint32_t) + sizeof(int32_t))))) return rc;
     if ((rc = ws(c.slot[S_RS_SCAN], (tilesK + tilesC + 2) * (sizeof(uint2) + sizeof(ulonglong2))))) return rc;
     if ((rc = ws(c.slot[S_RS_CTL], RS_CTL_LEN * sizeof(unsigned long long)))) return rc;
-    if ((rc = ws(c.slot[S_PART], std::max(tilesK, (size_t)1) * RS_NPART * sizeof(unsigned long long)))) return rc;
+    PointPlan pp;
+    if ((rc = point_plan(pp, np, RS_BLOCK, RS_NPART))) return rc; // (pp.nblocks == tilesK)
     int* count = (int*)c.slot[S_RS_COUNT].p;
     uint32_t* rankC = (uint32_t*)c.slot[S_RS_RANK].p;
     double* radn = (double*)c.slot[S_RS_OLD].p;
@@ -55,7 +56,7 @@ int reseed_core(const double* d_phi, const int32_t* d_mask, int nx, int ny, int 
     ulonglong2* offC = offK + tilesK + 1;
     uint2* sumsK = (uint2*)(offC + tilesC + 1);
     uint2* sumsC = sumsK + tilesK + 1;
-    unsigned long long *ctl = (unsigned long long*)c.slot[S_RS_CTL].p, *part = (unsigned long long*)c.slot[S_PART].p;
+    unsigned long long *ctl = (unsigned long long*)c.slot[S_RS_CTL].p, *part = pp.part;
     HIPCHK(hipMemsetAsync(ctl, 0, RS_CTL_LEN * sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(count, 0, n * sizeof(int), st));
     const SpGrid G{d_phi, d_mask, nx, ny, nz, dx, xLo[0], xLo[1], xLo[2]};
@@ -80,7 +81,7 @@ int reseed_core(const double* d_phi, const int32_t* d_mask, int nx, int ny, int 
     HIPCHK(hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
     unsigned long long tot[RS_NPART] = {0, 0, 0, 0, 0, 0, 0};
     if (np) {
-        if ((rc = block_counts_finish(part, (int)tilesK, RS_NPART, tot, nullptr, st))) return rc; // (lsf_host_sample_points.hpp; synchronises)
+        if ((rc = block_counts_finish(part, pp.nblocks, RS_NPART, tot, nullptr, st))) return rc; // (synchronises)
     } else
         HIPCHK(hipStreamSynchronize(st));
     const unsigned long long ncand = h[RS_NCAND], nkept = h[RS_NKEPT];
@@ -99,15 +100,12 @@ int reseed_core(const double* d_phi, const int32_t* d_mask, int nx, int ny, int 
         uint2* sumsA = (uint2*)(crad + ncand);
         rankA = (uint32_t*)(sumsA + tilesA + 1);
         const dim3 ga((unsigned)tilesA);
-#define LSF_RS_CALL(CU, HM) \
-    hipLaunchKernelGGL((k_rs_candidates<CU, HM>), ga, blk, 0, st, G, P, L, nwork, (const uint32_t*)rankC, (const ulonglong2*)offC, ncand, cpts, crad, rankA, sumsA, ctl)
-        switch ((order == LSF_SAMPLE_CUBIC ? 2 : 0) | (d_mask ? 1 : 0)) {
-        case 0: LSF_RS_CALL(false, false); break;
-        case 1: LSF_RS_CALL(false, true); break;
-        case 2: LSF_RS_CALL(true, false); break;
-        default: LSF_RS_CALL(true, true); break;
-        }
-#undef LSF_RS_CALL
+        with_flags(
+            [&](auto CU, auto HM) {
+                hipLaunchKernelGGL((k_rs_candidates<decltype(CU)::value, decltype(HM)::value>), ga, blk, 0, st, G, P, L, nwork, (const uint32_t*)rankC,
+                                   (const ulonglong2*)offC, ncand, cpts, crad, rankA, sumsA, ctl);
+            },
+            order == LSF_SAMPLE_CUBIC, d_mask != nullptr);
         hipLaunchKernelGGL(k_extract_scan, dim3(1), dim3(XS_SCAN_T), 0, st, (const uint2*)sumsA, (long)tilesA, offA, ctl + RS_NACC);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, st));

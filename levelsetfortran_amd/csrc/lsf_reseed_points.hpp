@@ -3,8 +3,9 @@
 // target level, and return one compacted set: lsf_reseed_points (include/lsf.h).
 //
 // Plain launches in stream order, no block waits for another:
-//   k_rs_classify    one lane per old marker, in the caller's order: radius, sp_locate, the band rule on the 8 corners of its cell
-//                    (cr_in_band), the LINEAR value (sp_stencil, unchanged).  Writes status, the refreshed radius, the keep flag
+//   k_rs_classify    one lane per old marker, in the caller's order: radius, pt_locate, the band rule on the 8 corners of its cell
+//                    (pt_in_band), the LINEAR value (sp_stencil; all of lsf_point_stencil.hpp).  Writes status, the refreshed
+//                    radius, the keep flag
 //                    with the marker's exclusive rank inside its block (xs_block_scan of lsf_extract_surface.hpp, reused), the
 //                    block's kept total, and adds 1 to the int32 count of the marker's cell: integer atomics, order-free.
 //   k_rs_cells       one lane per cell in memory order -- the points of the grid or, under a mask, the entries of the BandList in
@@ -18,7 +19,8 @@
 //                    most blocks of a maskless grid without a candidate and the others with anything from 1 to 256 * per_cell;
 //                    the search keeps every wave full of candidates whatever the shape of the band.  Then the four draws
 //                    (splitmix64, exact integer arithmetic), the first sample in the caller's order (sp_sample), the attraction --
-//                    the foot iteration of k_sample_points with the candidate's goal as iso, at most `iters` moves -- the LINEAR
+//                    the foot iteration of lsf_sample_points (pt_foot) with the candidate's goal as iso, at most `iters` moves -- the
+//                    LINEAR
 //                    sample at the end and the acceptance.  Stores position, radius (0 for a rejected candidate) and the accept
 //                    flag with its rank.
 //   k_rs_emit_kept, k_rs_emit_new   the kept markers in the caller's order with src = 1-based input position, then the accepted
@@ -26,11 +28,11 @@
 // Everything is evaluated as the header writes it, left to right, without contraction, so the result is the numpy statement's
 // (tests/reseed_ref.py) bit for bit; the counts are integers and no order of execution reaches them.
 //
-// Bounds.  An old marker reaches loads only behind the INSIDE test of sp_locate, made in double BEFORE any integer exists; behind it
-// 0 <= i0 <= n - 1 and the 8 corners lie in 0..n, and the cell's lower corner p = i0 + ... is below the number of points, the size
-// of count.  k_rs_cells forms a cell only where i < nx, j < ny, k < nz, so its 8 corners exist; a list entry is an interior point.
+// Bounds.  An old marker reaches loads only behind pt_locate ("Bounds" of lsf_point_stencil.hpp); behind it the 8 corners exist
+// and the cell's lower corner p = i0 + ... is below the number of points, the size of count.  k_rs_cells forms a cell only where
+// i < nx, j < ny, k < nz, so its 8 corners exist; a list entry is an interior point.
 // A candidate exists only for g < ncand, the total of the needs, so both searches end on a cell with need > 0 (below); its position
-// and every moved position pass sp_sample's INSIDE test before anything is loaded for them.  Slots: a kept marker writes slot
+// and every moved position pass sp_sample's locate before anything is loaded for them.  Slots: a kept marker writes slot
 // offK + rank < nkept, a new one nkept + offA + rank < nout, each into arrays of nout and 3 nout entries.  Lanes beyond npts, the
 // cells or ncand touch no memory.  Every loop is bounded: the searches by 32 and 8 trips, the attraction by iters <= 64.
 #pragma once
@@ -39,9 +41,8 @@
 
 #include "../../include/lsf.h"
 #include "lsf_block_reduce.hpp"
-#include "lsf_cast_rays.hpp"
 #include "lsf_extract_surface.hpp"
-#include "lsf_sample_points.hpp"
+#include "lsf_point_stencil.hpp"
 
 namespace lsf {
 
@@ -91,14 +92,14 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rs_classify(SpGrid G, RsParams P, 
         if (!__builtin_isfinite(ra) || ra == 0.0)
             st = LSF_RESEED_BADRADIUS;
         // The INSIDE test comes first: nothing below may run for a marker that fails it (see "Bounds" above).
-        else if (!sp_locate(pts[t], G.x0, G.dx, G.nx, i0[0], tt[0]) || !sp_locate(pts[t + N], G.y0, G.dx, G.ny, i0[1], tt[1]) ||
-                 !sp_locate(pts[t + 2 * N], G.z0, G.dx, G.nz, i0[2], tt[2]))
+        else if (!pt_locate<false>(pts[t], G.x0, G.dx, G.nx, i0[0], tt[0]) || !pt_locate<false>(pts[t + N], G.y0, G.dx, G.ny, i0[1], tt[1]) ||
+                 !pt_locate<false>(pts[t + 2 * N], G.z0, G.dx, G.nz, i0[2], tt[2]))
             st = LSF_RESEED_OUTSIDE;
-        else if (HAS_MASK && !cr_in_band<2>(G, i0))
+        else if (HAS_MASK && !pt_in_band<2>(G, i0))
             st = LSF_RESEED_OFFBAND;
         else {
             SpSample o;
-            sp_stencil<false, false, false>(G, nullptr, i0, tt, o);
+            sp_stencil<false, false>(G, nullptr, i0, tt, o);
             if (!__builtin_isfinite(o.v))
                 st = LSF_RESEED_NONFINITE;
             else if (__builtin_fabs(o.v) > P.band_dx)
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rs_cells(SpGrid G, RsParams P, con
             bool ok = true;
             if constexpr (LIST) {
                 const int lo[3] = {i, j, k};
-                ok = cr_in_band<2>(G, lo);
+                ok = pt_in_band<2>(G, lo);
             }
             if (ok) {
                 const double* __restrict__ f = G.phi + p;
@@ -217,32 +218,12 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rs_candidates(SpGrid G, RsParams P
         const double x0 = G.x0 + ((double)ci + u0) * G.dx, x1 = G.y0 + ((double)cj + u1) * G.dx, x2 = G.z0 + ((double)ck + u2) * G.dx;
         double y0 = x0, y1 = x1, y2 = x2, rd = 0.0;
         SpSample s;
-        // every position passes the INSIDE test of sp_sample before anything is loaded for it
         int st = sp_sample<CUBIC, false, HAS_MASK>(G, nullptr, x0, x1, x2, s);
         if (st == LSF_SAMPLE_OK && !__builtin_isfinite(s.v)) st = -1;
         if (st == LSF_SAMPLE_OK) {
             const double sg = s.v < 0.0 ? -1. : 1.;
             const double goal = sg * ((P.rmin + (P.band - P.rmin) * u3) * G.dx);
-            st = LSF_SAMPLE_NOT_CONVERGED;
-            for (int it = 0;; ++it) { // the loop of k_sample_points: `iters` moves, and one more sample for the test after the last
-                const double e_ = s.v - goal;
-                if (!(__builtin_fabs(e_) > P.tol_dx)) {
-                    st = LSF_SAMPLE_OK;
-                    break;
-                }
-                if (it == P.iters) break;
-                const double m = (s.g0 * s.g0 + s.g1 * s.g1) + s.g2 * s.g2;
-                if (m == 0.0) {
-                    st = LSF_SAMPLE_FLAT;
-                    break;
-                }
-                y0 = y0 - (e_ * s.g0) / m, y1 = y1 - (e_ * s.g1) / m, y2 = y2 - (e_ * s.g2) / m;
-                const int s2 = sp_sample<CUBIC, false, HAS_MASK>(G, nullptr, y0, y1, y2, s);
-                if (s2 != LSF_SAMPLE_OK) {
-                    st = s2;
-                    break;
-                }
-            }
+            st = pt_foot<CUBIC, HAS_MASK>(G, goal, P.iters, P.tol_dx, s, y0, y1, y2);
             if (st == LSF_SAMPLE_OK) {
                 SpSample l;
                 const int s3 = sp_sample<false, false, HAS_MASK>(G, nullptr, y0, y1, y2, l);

@@ -246,6 +246,30 @@ def special_points(shape, dx, lo):
     return np.array(pts), np.array(want, np.int32)
 
 
+def ring_points(phi, mask, dx, lo):
+    """(points, status of a cubic sample under the mask): a handful of points in cells whose eight corners are all on the list while a
+    point of the outer ring of their 4 x 4 x 4 stencil is not -- OFFBAND by the ring alone -- and, beside each, a point in a
+    neighbouring cell whose whole stencil is on the list.  The cells come from the mask itself: a hole next to the lower corner of
+    the interior (mask[1, 1, 1] != 1) gives one.  Asserts that the statement reports at least one point of each kind."""
+    shape, lo = phi.shape, np.asarray(lo, dtype=np.float64)
+    listed = np.zeros(shape, bool)
+    listed[1:-1, 1:-1, 1:-1] = mask[1:-1, 1:-1, 1:-1] == 1
+    pts = []
+    for i in range(2, shape[0] - 3):
+        for j in range(2, shape[1] - 3):
+            for k in range(2, shape[2] - 3):  # the cubic stencil is taken and lies in the interior: the mask's values decide
+                corners, stencil = listed[i:i + 2, j:j + 2, k:k + 2].all(), listed[i - 1:i + 3, j - 1:j + 3, k - 1:k + 3].all()
+                if corners and not stencil:
+                    pts.extend(lo + (np.array([i, j, k]) + f) * dx for f in ((0.5, 0.5, 0.5), (0.0, 0.25, 0.875), (0.75, 0.125, 0.0)))
+                    pts.extend(lo + (np.array([i + a, j + b, k + c]) + 0.5) * dx for a, b, c in ((1, 0, 0), (0, 1, 0), (0, 0, 1)))
+    pts = np.asfortranarray(np.array(pts))
+    want = sample_points(phi, dx, lo, pts, order=CUBIC, mask=mask)
+    ring_only = want.status == OFFBAND
+    assert ring_only.any() and (want.status == OK).any(), want.info
+    assert np.array_equal(sample_points(phi, dx, lo, pts[ring_only], order=LINEAR, mask=mask).status, np.zeros(ring_only.sum(), np.int32))
+    return pts, want
+
+
 def node_value_bound(phi, dx, xLo, X):
     """How far from iso the LINEAR sample at each node of lsf_extract_surface may lie, derived and not measured: (bound per node,
     whether the node lies on an edge along a grid axis).

@@ -357,6 +357,9 @@ def _mirror(flags):
     from levelsetfortran_amd import _lib
 
     lib = _lib.load()
+    # no twin of an earlier test may be left: a fresh array can get the address of a freed one (the all-zero mask of the test before),
+    # and under TRUST a current twin of that address would be taken for it
+    _lib.check(lib.lsf_release_workspace())
     try:
         _lib.check(lib.lsf_mirror(flags))
         yield lib

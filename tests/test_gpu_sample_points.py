@@ -298,6 +298,26 @@ def test_status_cases(lsf, name, seam):
     _assert_equal(_home(seam, outs, npts), info, want, name)
 
 
+@pytest.mark.parametrize("seam", ["host", "device"])
+def test_offband_by_the_outer_ring_alone(lsf, seam):
+    """cubic under the mask, in cells whose eight corners are on the list while a point of the outer ring of the 4 x 4 x 4 stencil
+    is not (the hole at (1, 1, 1)), and in their neighbours: the corners pass the band rule, the ring decides"""
+    from levelsetfortran_amd import _lib
+
+    lib = _lib.load()
+    phi, mask, q = _fields()
+    pts, want = S.ring_points(phi, mask, DX, LO)  # (asserts that both kinds of point are there)
+    npts = len(pts)
+    for hasq, iters in ((False, 0), (True, ITERS)):
+        w = S.sample_points(phi, DX, LO, pts, order=S.CUBIC, mask=mask, q=q if hasq else None, iso=ISO, iters=iters, tol=TOL)
+        assert np.array_equal(w.status == S.OFFBAND, want.status == S.OFFBAND)
+        mk = _dev if seam == "device" else (lambda a: np.array(a.ravel(order="F")))
+        outs = _fresh_outs(seam, npts, [k for k in OUTS if (k != "qval" or hasq) and (k != "foot" or iters)])
+        rc, info, msg = _raw(lib, seam, mk(phi), mk(mask), mk(q) if hasq else None, N, DX, LO, mk(pts), npts, S.CUBIC, ISO, iters, TOL, outs)
+        assert rc == 0, msg
+        _assert_equal(_home(seam, outs, npts), info, w, f"outer ring, q {hasq}, iters {iters}")
+
+
 # ---------------------------------------------------------------------------------- 4: the Python name
 @pytest.mark.parametrize("seam", ["host", "device"])
 def test_python_report(lsf, seam):
