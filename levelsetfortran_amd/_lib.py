@@ -192,11 +192,21 @@ DEVICE_TWINS = ("lsf_minmax", "lsf_narrowband", "lsf_phi0", "lsf_mesh_distance",
 for _name in DEVICE_TWINS:
     SIGNATURES[_name + "_device"] = (SIGNATURES[_name][0], SIGNATURES[_name][1] + [c_void_p])
 
+# include/lsf_redistance.h: the second public header and its table, bound by load() after the first.  Both seams are written out;
+# Seam.call finds them by name.
+LSF_REDISTANCE_INFO_LEN = 9
+_REDISTANCE_BAND = [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_double, c_int, POINTER(c_int), c_void_p, c_int,
+                    POINTER(c_double), c_void_p]
+SIGNATURES_REDISTANCE = {
+    "lsf_redistance_band": (c_int, _REDISTANCE_BAND),
+    "lsf_redistance_band_device": (c_int, _REDISTANCE_BAND + [c_void_p]),
+}
+
 _lib = None
 
 
 def load() -> ctypes.CDLL:
-    """Load liblsf_hip.so and bind every symbol of include/lsf.h.  Raises if it is not built."""
+    """Load liblsf_hip.so and bind every symbol of include/lsf.h and include/lsf_redistance.h.  Raises if it is not built."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -213,10 +223,11 @@ def load() -> ctypes.CDLL:
         except ImportError:  # host-only use (lsf_stl_read, the ABI checks): nothing to keep consistent
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
-            fn.restype = res
-            fn.argtypes = args
+        for table in (SIGNATURES, SIGNATURES_REDISTANCE):
+            for name, (res, args) in table.items():
+                fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
+                fn.restype = res
+                fn.argtypes = args
         _lib = lib
     return _lib
 

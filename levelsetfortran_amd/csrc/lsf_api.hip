@@ -43,6 +43,7 @@
 #include "lsf_correct_field.hpp"
 #include "lsf_reseed_points.hpp"
 #include "lsf_label_band.hpp"
+#include "lsf_redistance_band.hpp"
 
 using namespace lsf;
 
@@ -199,7 +200,7 @@ struct BatchPlan {
     int nslots = 0;
 };
 
-enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_CR_Q, S_CR_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_AP_IO, S_CF_IO, S_CF_PLUS, S_CF_MINUS, S_CF_CTL, S_CC_VOF, S_CC_AX, S_CC_AY, S_CC_AZ, S_CC_BX, S_CC_BY, S_CC_BZ, S_RS_COUNT, S_RS_RANK, S_RS_OLD, S_RS_SCAN, S_RS_CTL, S_RS_CAND, S_RS_IO, S_NSLOTS };
+enum Slot { S_PONG, S_PHIS, S_PART, S_CTL, S_TRACE, S_HPHI, S_HNB, S_HSB, S_CEN, S_VTX, S_BFLAG, S_CHG, S_BACKUP, S_PART2, S_PLANECNT, S_DBG, S_COLSUM, S_ORDER, S_GRAD, S_NODES, S_STAMP, S_PONG2, S_PONG3, S_PONG4, S_SNAP, S_MB_CNT, S_MB_L, S_MB_NB6, S_MB_AOLD, S_MB_A0, S_MB_BAND, S_MB_KEY, S_MB_TMP, S_RB_PHIS, S_MD_REC, S_MD_BOX, S_MD_CHUNK, S_MD_CNT, S_DF_WORDS, S_DF_CNT, S_AF_U, S_AF_V, S_AF_W, S_AF_F, S_XS_MASK, S_XS_BYTE, S_XS_NOFF, S_XS_TOFF, S_XS_SUMS, S_XS_TILEOFF, S_XS_CTL, S_EXT_WORDS, S_EXT_CNT, S_EXT_Q, S_EVB_MASK, S_CV_KAPPA, S_CV_GAUSS, S_CV_GMAG, S_XB_NB, S_XB_WT, S_XB_NV, S_XB_FLAG, S_XB_CNT, S_XB_KNOWN, S_MS_Q, S_MS_CELL, S_MS_CTL, S_SP_Q, S_SP_IO, S_CR_Q, S_CR_IO, S_LB_LABEL, S_LB_CNT, S_LB_ROOTS, S_LB_ROWS, S_AP_IO, S_CF_IO, S_CF_PLUS, S_CF_MINUS, S_CF_CTL, S_CC_VOF, S_CC_AX, S_CC_AY, S_CC_AZ, S_CC_BX, S_CC_BY, S_CC_BZ, S_RS_COUNT, S_RS_RANK, S_RS_OLD, S_RS_SCAN, S_RS_CTL, S_RS_CAND, S_RS_IO, S_RD_VAL, S_RD_FLAG, S_RD_CNT, S_NSLOTS };
 
 // partial sums of the box calls issued on one stream; `deferred`: between lsf_sumsq_begin and lsf_sumsq_end the calls
 // append their partials instead of reducing them one by one
@@ -470,6 +471,7 @@ BcWhole bc_whole(int nx, int ny, int nz)
 #include "lsf_host_args.hpp"
 #include "lsf_host_args_points.hpp"
 #include "lsf_host_args_cut.hpp"
+#include "lsf_host_args_redistance.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // One fp64 Jacobi sweep over the cells [lo, hi) of a box: picks the kernel and its launch geometry.
@@ -762,6 +764,7 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 #include "lsf_host_reseed.hpp"
 
 #include "lsf_host_label_band.hpp"
+#include "lsf_host_redistance_band.hpp"
 
 int box_ok(const lsf_box* b, const int lo[3], const int hi[3])
 {
@@ -1755,6 +1758,35 @@ int lsf_extend_field_band(double* q, const double* phi, const int32_t* mask, con
         return rc;
     HIPCHK(hipMemcpy(q, d_q, n * sizeof(double), hipMemcpyDeviceToHost));
     return LSF_OK;
+}
+
+int lsf_redistance_band_device(double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, double near, int iters, double tol,
+                               int max_passes, int* passes_done, int64_t* changed_trace, int trace_cap, double* change,
+                               int64_t info[LSF_REDISTANCE_INFO_LEN], void* stream)
+{
+    Trace trace_("lsf_redistance_band_device");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = redistance_band_args_ok(d_phi, d_mask, nx, ny, nz, dx, near, iters, tol, max_passes, trace_cap))) return rc;
+    return redistance_band_core(d_phi, d_mask, nx, ny, nz, dx, near, iters, tol, max_passes, passes_done, changed_trace, trace_cap, change, info,
+                                (hipStream_t)stream);
+}
+
+int lsf_redistance_band(double* phi, const int32_t* mask, int nx, int ny, int nz, double dx, double near, int iters, double tol, int max_passes,
+                        int* passes_done, int64_t* changed_trace, int trace_cap, double* change, int64_t info[LSF_REDISTANCE_INFO_LEN])
+{
+    Trace trace_("lsf_redistance_band");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = redistance_band_args_ok(phi, mask, nx, ny, nz, dx, near, iters, tol, max_passes, trace_cap))) return rc;
+    Ctx& c = ctx();
+    const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
+    const int32_t* d_mask;
+    if ((rc = twin_in(c, c.twin_phi, S_HPHI, phi, n * sizeof(double)))) return rc; // in and out, as lsf_reinit_band takes its field
+    if ((rc = mask_in(c, mask, n, &d_mask))) return rc;
+    rc = redistance_band_core((double*)c.slot[S_HPHI].p, d_mask, nx, ny, nz, dx, near, iters, tol, max_passes, passes_done, changed_trace, trace_cap,
+                              change, info, nullptr);
+    return phi_home(c, phi, n * sizeof(double), rc, true); // every LSF_ERR_INVALID is decided before phi is written: the twin stays
 }
 
 int lsf_extract_surface_device(const double* d_phi, int nx, int ny, int nz, double dx, const double xLo[3], double iso, int* nSurfNode,

@@ -60,6 +60,9 @@
 !   extendFieldBand(q,phi,mask,nx,ny,nz,dx,band)         no reference counterpart: extendField on the cells with mask == 1
 !                                                        only, by Jacobi passes over the list: q carried off the list cells
 !                                                        with |phi| < band*dx (include/lsf.h: lsf_extend_field_band)
+!   redistanceBand(phi,mask,nx,ny,nz,dx,near)            no reference counterpart: the distance property restored on the cells
+!                                                        with mask == 1 from closest points, without pseudo-time sweeps
+!                                                        (include/lsf_redistance.h: lsf_redistance_band)
 !   extractSurface(phi,nx,ny,nz,dx,xLo,iso,surfX,nSurfNode,surfElem,nSurfElem)
 !                                                        no reference counterpart: the level set phi = iso as a triangle mesh,
 !                                                        marching tetrahedra (include/lsf.h: lsf_extract_surface)
@@ -105,6 +108,9 @@
 !                               !   (ncclSend / ncclRecv over xGMI; needs a distinct device per block)
 !     check_every = 8           ! sweeps between two looks of the host at the RMS of a block-decomposed run (1..64;
 !                               !   the stop sweep, the field and the printed residuals do not depend on it)
+!     redist_iters = 8          ! redistanceBand: Newton steps of the foot iteration at most,
+!     redist_tol = 1e-9         !   its tolerance |phi(foot)| <= tol*dx,
+!     redist_passes = 64        !   and the cap of the Jacobi passes of its fill (include/lsf_redistance.h)
 !     resident = 2              ! 0: every seam copies its arrays in and out (default of the C ABI)
 !                               ! 1: skip the host-to-device copy of an array the last seam left on the device
 !                               ! 2: (default here) ... and leave results on the device until the host needs them:
@@ -140,6 +146,7 @@ PUBLIC :: reseedPoints
 PUBLIC :: reseedGet
 PUBLIC :: labelBand
 PUBLIC :: extendFieldBand
+PUBLIC :: redistanceBand
 PUBLIC :: extractSurface, stlWrite
 PUBLIC :: writeVti, snapshotPhi, sumSqDiff, syncHost, syncHostInt, forgetHost, stlRead
 
@@ -154,6 +161,8 @@ INTEGER, SAVE :: nml_reinit_iter = -1, nml_minmax_iter = -1, nml_reinit2_iter = 
 CHARACTER(LEN=16), SAVE :: nml_order = ' ', nml_arith = ' ', nml_transport = ' '
 INTEGER, SAVE :: nml_check_every = 8
 INTEGER, SAVE :: nml_resident = -1, nml_slabs = 0
+INTEGER, SAVE :: nml_redist_iters = 8, nml_redist_passes = 64
+REAL, SAVE :: nml_redist_tol = 1.0e-9
 INTEGER(c_int), SAVE :: nml_devices(16) = -1
 LOGICAL, SAVE :: mirror_set = .FALSE.
 
@@ -393,6 +402,20 @@ INTERFACE
       INTEGER(c_int64_t), INTENT(OUT) :: info(8)
       INTEGER(c_int) :: rc
    END FUNCTION lsf_label_band
+   ! int lsf_redistance_band(double*,const int32_t*,int,int,int,double,double,int,double,int,int*,int64_t*,int,double*,int64_t[9])
+   FUNCTION lsf_redistance_band(phi,mask,nx,ny,nz,dx,near,iters,tol,max_passes,passes_done,changed_trace,trace_cap,change,info) &
+            BIND(C,NAME='lsf_redistance_band') RESULT(rc)
+      IMPORT :: c_int, c_double, c_int64_t
+      REAL(c_double), INTENT(INOUT) :: phi(*)
+      INTEGER(c_int), INTENT(IN) :: mask(*)
+      INTEGER(c_int), VALUE :: nx,ny,nz,iters,max_passes,trace_cap
+      REAL(c_double), VALUE :: dx,near,tol
+      INTEGER(c_int), INTENT(OUT) :: passes_done
+      INTEGER(c_int64_t), INTENT(OUT) :: changed_trace(*)
+      REAL(c_double), INTENT(OUT) :: change
+      INTEGER(c_int64_t), INTENT(OUT) :: info(9)
+      INTEGER(c_int) :: rc
+   END FUNCTION lsf_redistance_band
    ! int lsf_sample_points(const double*,const int32_t*,const double*,int,int,int,double,const double[3],const double*,int,int,
    !                       double,int,double,double*,double*,double*,double*,int32_t*,int64_t[6])
    FUNCTION lsf_sample_points(phi,mask,q,nx,ny,nz,dx,xLo,pts,npts,order,iso,iters,tol,val,grad,qval,foot,status,info) &
@@ -618,12 +641,14 @@ END FUNCTION lsf_mode
 ! &lsf_inputs: from the file named by the second command-line argument, else ./lsf.nml
 !*************************************************************************************!
 SUBROUTINE lsf_load_inputs()
-REAL :: dx
+REAL :: dx,redist_tol
 INTEGER :: dd,dd_lo(3),dd_hi(3),reinit_iter,minmax_iter,reinit2_iter,ios,u,resident,devices(16),check_every,slabs
+INTEGER :: redist_iters,redist_passes
 CHARACTER(LEN=16) :: order,arith,transport
 CHARACTER(LEN=1024) :: path
 LOGICAL :: there
-NAMELIST /lsf_inputs/ dx,dd,dd_lo,dd_hi,reinit_iter,minmax_iter,reinit2_iter,order,arith,resident,devices,transport,check_every,slabs
+NAMELIST /lsf_inputs/ dx,dd,dd_lo,dd_hi,reinit_iter,minmax_iter,reinit2_iter,order,arith,resident,devices,transport,check_every,slabs, &
+                      redist_iters,redist_tol,redist_passes
 IF (nml_loaded) RETURN
 nml_loaded = .TRUE.
 path = ' '
@@ -641,6 +666,7 @@ dx = nml_dx; dd = nml_dd; dd_lo = nml_dd_lo; dd_hi = nml_dd_hi
 reinit_iter = nml_reinit_iter; minmax_iter = nml_minmax_iter; reinit2_iter = nml_reinit2_iter
 order = nml_order; arith = nml_arith; resident = nml_resident; devices = nml_devices
 transport = nml_transport; check_every = nml_check_every; slabs = nml_slabs
+redist_iters = nml_redist_iters; redist_tol = nml_redist_tol; redist_passes = nml_redist_passes
 u = 47
 OPEN(UNIT=u,FILE=TRIM(path),STATUS='old',ACTION='read',IOSTAT=ios)
 IF (ios == 0) READ(u,NML=lsf_inputs,IOSTAT=ios)
@@ -653,6 +679,7 @@ nml_dx = dx; nml_dd = dd; nml_dd_lo = dd_lo; nml_dd_hi = dd_hi
 nml_reinit_iter = reinit_iter; nml_minmax_iter = minmax_iter; nml_reinit2_iter = reinit2_iter
 nml_order = order; nml_arith = arith; nml_resident = resident; nml_devices = devices
 nml_transport = transport; nml_check_every = check_every; nml_slabs = slabs
+nml_redist_iters = redist_iters; nml_redist_tol = redist_tol; nml_redist_passes = redist_passes
 PRINT*, " Run parameters read from ",TRIM(path)
 END SUBROUTINE lsf_load_inputs
 
@@ -965,6 +992,42 @@ PRINT*, " Extend field on the band: ",info(1)," list cells, ",info(2)," frozen, 
 PRINT*
 
 END SUBROUTINE extendFieldBand
+
+!*************************************************************************************!
+! The distance property restored on the cells with mask == 1 from closest points
+! (include/lsf_redistance.h: lsf_redistance_band; no reference counterpart): a list cell
+! whose foot on the interpolant's zero level set is found closer than near*dx takes that
+! distance with the sign it had; the other list cells are filled from those by Jacobi
+! passes of distanceFill's visit over the list.  Nothing outside the list is read or
+! written, no cell changes sign, and list cells that no frozen cell reaches keep their
+! value and are counted.  iters, tol and the cap of the passes come from &lsf_inputs
+! (redist_iters = 8, redist_tol = 1e-9, redist_passes = 64).  Prints the counts, the
+! passes run, the visits the last one lowered (0: converged) and the largest change.
+!*************************************************************************************!
+SUBROUTINE redistanceBand(phi,mask,nx,ny,nz,dx,near)
+
+INTEGER,INTENT(IN) :: nx,ny,nz
+REAL,INTENT(IN) :: dx,near
+REAL,DIMENSION(0:nx,0:ny,0:nz),INTENT(INOUT) :: phi
+INTEGER,DIMENSION(0:nx,0:ny,0:nz),INTENT(IN) :: mask
+INTEGER(c_int64_t), ALLOCATABLE :: trace(:)
+INTEGER(c_int64_t) :: info(9)
+INTEGER(c_int) :: rc,done
+REAL(c_double) :: change
+
+CALL lsf_load_inputs()
+CALL lsf_set_mirror()
+ALLOCATE(trace(MAX(nml_redist_passes,1)))
+rc = lsf_redistance_band(phi,mask,nx,ny,nz,dx,near,nml_redist_iters,nml_redist_tol,nml_redist_passes,done,trace, &
+                         MAX(nml_redist_passes,1),change,info)
+IF (rc /= LSF_OK) CALL lsf_fail('lsf_redistance_band',rc)
+PRINT*, " Redistance on the band: list cells, frozen, filled, unreached ",info(1),info(2),info(3),info(4)
+PRINT*, " Redistance on the band: feet off the band, outside, flat, not converged, beyond near ",info(5),info(6),info(7),info(8),info(9)
+PRINT*, " Redistance on the band: ",done," passes, last pass lowered ",trace(done),", largest change ",change
+PRINT*
+DEALLOCATE(trace)
+
+END SUBROUTINE redistanceBand
 
 !*************************************************************************************!
 ! Transport of the level set by a velocity field, phi_t + u.grad(phi) = 0 (include/lsf.h:

@@ -59,6 +59,10 @@ and a quantity known on that band carried to the rest of the grid constant along
 
   extendField(q, phi, nx, ny, nz, dx, band=... | mask=...)      include/lsf.h: lsf_extend_field
 
+and the distance property restored on the cells of a mask from closest points, without pseudo-time sweeps:
+
+  redistanceBand(phi, mask, nx, ny, nz, dx, near=2.5, ...)      include/lsf_redistance.h: lsf_redistance_band
+
 Fields are updated IN PLACE like the INTENT(INOUT) dummies of the reference.  A field is either
   * a numpy float64 array, Fortran-ordered with shape (nx+1, ny+1, nz+1) (or 1-D of that size):
     the host seam -- the library copies it to HBM and back (lsf_reinit / lsf_minmax), or
@@ -82,7 +86,7 @@ from . import _lib, _seam
 from ._lib import LSF_ARITH_FAST, LSF_ARITH_STRICT, LSF_ORDER_GS, LSF_ORDER_JACOBI, LsfError, LsfNaNError
 from ._seam import Seam
 
-__all__ = ["cutCellsBand", "CutCellsReport", "advectPoints","AdvectPointsReport", "correctField", "CorrectReport", "seedParticles", "reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "castRays", "CastReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
+__all__ = ["cutCellsBand", "CutCellsReport", "advectPoints","AdvectPointsReport", "correctField", "CorrectReport", "seedParticles", "reinit", "reinitBand", "narrowBand", "minmaxFlow", "phi0Init", "meshDistance", "meshCheck", "MeshInfo", "distanceFill", "FillReport", "extendField", "ExtendReport", "extendFieldBand", "ExtendBandReport", "redistanceBand", "RedistanceReport", "advectField", "AdvectReport", "advectFieldBand", "AdvectBandReport", "evolveBand", "EvolveBandReport", "evolveBandCurv", "EvolveBandCurvReport", "curvatureBand", "CurvatureReport", "extractSurface", "SurfaceInfo", "measureBand", "MeasureReport", "samplePoints", "SampleReport", "castRays", "CastReport", "stlWrite", "advectNodes", "SweepReport", "mode_word", "LsfError", "LsfNaNError", "peer_selftest"]
 
 REINIT_TOL = 1.0e-5  # subs.f90:915
 MINMAX_TOL = 1.0e-7  # set3d.f90:448
@@ -441,6 +445,66 @@ def extendFieldBand(q, phi, mask, dx: float, known=None, band: Optional[float] =
     converged = n < max_passes or bool(0 < n <= cap and trace[n - 1] == 0)
     keep = min(n, cap if trace_cap is None else min(cap, int(trace_cap)))
     return q, ExtendBandReport(n, converged, [int(v) for v in trace[:keep]], int(info[0]), int(info[1]), int(info[2]), int(info[3]))
+
+
+class RedistanceReport(NamedTuple):
+    """What lsf_redistance_band reports (include/lsf_redistance.h): Jacobi passes of the fill, whether the last one lowered nothing,
+    the visits that lowered a value in each pass, the largest |new - old| over the written cells, and the nine counts of info:
+    list cells, the frozen, filled and unreached ones among them, and the feet by status (offband, outside, flat, not_converged;
+    far = found, but not closer than near*dx).  frozen + offband + outside + flat + not_converged + far == cells ==
+    frozen + filled + unreached."""
+    passes: int
+    converged: bool
+    trace: List[int]
+    change: float
+    cells: int
+    frozen: int
+    filled: int
+    unreached: int
+    offband: int
+    outside: int
+    flat: int
+    not_converged: int
+    far: int
+
+
+def redistanceBand(phi, mask, nx: int, ny: int, nz: int, dx: float, near: float = 2.5, iters: int = 8, tol: float = 1e-9,
+                   max_passes: int = 64) -> RedistanceReport:
+    """Redistances the list of `mask` from closest points, without pseudo-time sweeps (include/lsf_redistance.h:
+    lsf_redistance_band); `phi` is updated in place, `mask` is read only.
+
+    phi: float64, numpy Fortran-ordered (nx+1, ny+1, nz+1) or a torch CUDA tensor (nz+1, ny+1, nx+1); mask: int32, same layout and
+    kind.  The list is the interior points with mask == 1, as in reinitBand.  A list cell whose foot on the cubic interpolant's zero
+    level set is found (at most `iters` Newton steps to |phi| <= tol*dx) closer than near*dx takes that distance with the sign it
+    had; the other list cells are filled from those by Jacobi passes of distanceFill's visit until a pass lowers nothing or
+    max_passes is reached (then converged is False).  No cell changes the answer of (phi < 0); list cells no frozen cell reaches keep
+    their value and are counted in `unreached`; points outside the list are neither read nor written.  near: 2 to 3 cells -- far
+    from the surface the foot of a field that is not a distance is not the closest point.
+    """
+    dx = _seam.positive(dx)
+    near = float(near)
+    if not (np.isfinite(near) and near > 0.0):
+        raise ValueError("near must be finite and > 0")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError("iters must be >= 1")
+    tol = float(tol)
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError("tol must be finite and >= 0")
+    max_passes = int(max_passes)
+    if max_passes < 1:
+        raise ValueError("max_passes must be >= 1")
+    s = Seam(phi, nx, ny, nz)
+    p, m = s.field(phi, "phi"), s.field(mask, "mask", np.int32)
+    cap = min(max_passes, _EXTEND_BAND_TRACE)  # passes whose counts the Python layer keeps at most
+    trace = np.zeros(cap, dtype=np.int64)
+    done, change = ctypes.c_int(0), ctypes.c_double(0.0)
+    info = np.zeros(_lib.LSF_REDISTANCE_INFO_LEN, dtype=np.int64)
+    _lib.check(s.call("lsf_redistance_band", p, m, nx, ny, nz, dx, near, iters, tol, max_passes, ctypes.byref(done), trace.ctypes.data, cap,
+                      ctypes.byref(change), info.ctypes.data))
+    n = done.value
+    converged = n < max_passes or bool(0 < n <= cap and trace[n - 1] == 0)
+    return RedistanceReport(n, converged, [int(v) for v in trace[:min(n, cap)]], change.value, *(int(v) for v in info))
 
 
 class AdvectReport(NamedTuple):

@@ -1,0 +1,98 @@
+"""The inputs of the GPU tests of lsf_redistance_band (tests/test_gpu_redistance_band.py) with what the statement
+(tests/redistance_ref.py) makes of them; tests/test_redistance_band_cpu.py checks on the CPU that every case reaches the path it is
+named after.
+
+The field is the two-sphere field of fields.two_sphere_phi0 -- the smeared sign s = d / sqrt(d^2 + dx^2) of the distance d to two
+spheres, far from a distance: |grad s| is 1/dx on the surface and falls to nothing within a few cells -- times a positive
+distortion g.  The mask is |d| < width*dx with d recovered from s: a band of that width in cells around the surface.  (A mask
+|s g| < width*dx of the smeared field itself is thinner than one cell: no cubic stencil fits into it, and the call is refused with "no
+frozen cell".)
+
+case -> (phi, mask, dx, keywords of the call); all arrays read-only and Fortran-ordered.
+"""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+import redistance_ref as R
+from advect_band_ref import list_of
+from levelsetfortran_amd import fields
+
+DEFAULTS = dict(near=2.5, iters=8, tol=1e-9, max_passes=64)
+CASES = ("baseline", "asymmetric", "cut", "walls", "zeros", "cap1", "cap3", "one_iteration", "flat", "values")
+
+
+def _two_spheres(npts, ranges=None, whole=None):
+    """(s * g, d, dx) on npts points, or on the index block `ranges` of the `whole` grid"""
+    s, dx = fields.two_sphere_phi0(whole or npts, ranges=ranges)
+    x, y, z, _ = fields.grid_axes(whole or npts)
+    if ranges is not None:
+        x, y, z = (a[r[0]:r[1]] for a, r in zip((x, y, z), ranges))
+    x, y, z = np.meshgrid(x, y, z, indexing="ij")
+    g = 1.0 + 0.3 * x + 0.2 * y * y + 0.25 * np.sin(3.0 * z)
+    assert g.min() > 0.25
+    d = s * dx / np.sqrt(1.0 - s * s)
+    return np.asfortranarray(s * g), d, dx
+
+
+def _band(d, dx, width):
+    return np.asfortranarray((np.abs(d) < width * dx).astype(np.int32))
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(case):
+    kw = dict(DEFAULTS)
+    if case == "asymmetric":  # (70, 21, 45) points of a 70^3 grid: a transposed stride cannot pass
+        phi, d, dx = _two_spheres(None, ranges=((0, 70), (25, 46), (12, 57)), whole=(70, 70, 70))
+        mask = _band(d, dx, 4.1)
+    elif case == "walls":  # the surface within two cells of the lower x wall and of the upper z wall; 1s on the wall points themselves
+        phi, d, dx = _two_spheres(None, ranges=((2, 24), (1, 22), (0, 16)), whole=(24, 24, 24))
+        mask = _band(d, dx, 4.1)
+    elif case in ("flat", "zeros"):  # dx = 1/8: the cell points are located exactly, t = 0
+        phi, d, dx = _two_spheres((25, 21, 19))
+        assert dx == 0.125
+        mask = _band(d, dx, 4.1)
+        if case == "flat":  # a plateau inside the list, clear of the surface: the gradient of the interpolant is exactly 0
+            phi[9:15, 8:14, 1:7] = 0.375
+            mask[8:16, 7:15, 1:8] = 1
+        else:  # exactly 0.0 and -0.0 on the list points nearest to the surface
+            lst = list_of(mask)
+            order = np.argsort(np.where(lst, np.abs(phi), np.inf), axis=None)[:12]
+            at = np.unravel_index(order, phi.shape)
+            phi[tuple(a[0::2] for a in at)] = 0.0
+            phi[tuple(a[1::2] for a in at)] = -0.0
+    else:
+        phi, d, dx = _two_spheres((24, 21, 19))
+        mask = _band(d, dx, 4.1)
+        if case == "cut":  # the mask ends in the middle of the first sphere, and holds a block no frozen cell reaches
+            mask[6:, :, :] = np.where(mask[6:, :, :] == 1, 0, mask[6:, :, :])
+            mask[18:22, 2:6, 13:17] = 1
+        elif case == "values":  # 0, 7, -1, and 1s on all six walls
+            near = mask == 1
+            mask[~near & (d > 6 * dx)] = 7  # not 1: not in the list
+            mask[~near & (d > 9 * dx)] = -1
+            for a in range(3):
+                sl = [slice(None)] * 3
+                for side in (0, -1):
+                    sl[a] = side
+                    mask[tuple(sl)] = 1
+        elif case == "cap1":
+            kw["max_passes"] = 1
+        elif case == "cap3":
+            kw["max_passes"] = 3
+        elif case == "one_iteration":
+            kw["iters"], kw["tol"] = 1, 1e-2  # one Newton step reaches the looser tolerance from some cells and not from others
+    phi, mask = np.asfortranarray(phi), np.asfortranarray(mask)
+    for a in (phi, mask):
+        a.setflags(write=False)
+    return phi, mask, float(dx), kw
+
+
+@functools.lru_cache(maxsize=None)
+def want(case):
+    phi, mask, dx, kw = inputs(case)
+    r = R.redistance_band(phi, mask, dx, **kw)
+    r.field.setflags(write=False)
+    return r
