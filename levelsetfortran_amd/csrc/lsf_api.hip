@@ -732,6 +732,7 @@ int reinit_f32_core(float* d_phi, const float* d_phiS_in, int nx, int ny, int nz
 
 #include "lsf_host_gs.hpp"
 
+#include "lsf_host_band.hpp"
 #include "lsf_host_minmax.hpp"
 
 #include "lsf_host_reinit_band.hpp"

@@ -1,6 +1,6 @@
-// lsf_host_advect_band.hpp -- host side of lsf_advect_field_band (kernels and design: lsf_advect_band.hpp): validation, the list, the
-// scan of the inputs at list cells, the edge pass, the steps (one plain launch per stage over the list) and the closing pass.
-// Included by lsf_api.hip inside its anonymous namespace.
+// lsf_host_advect_band.hpp -- host side of lsf_advect_field_band (kernels and design: lsf_advect_band.hpp): validation, the list
+// (lsf_host_band.hpp), the scan of the inputs at list cells, the edge pass, the steps (one plain launch per stage over the list) and
+// the closing pass.  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
 
 // one stage launch over the list: the instance for the arithmetic and the terms present
@@ -28,7 +28,7 @@ int advect_band_core(double* d_phi, const int32_t* d_mask, const double* d_u, co
     const bool strict = (mode & LSF_ARITH_STRICT) != 0, rk3 = scheme == LSF_ADVECT_RK3;
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
     BandList bl;
-    if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, dx, st))) return rc;
+    if ((rc = band_list_build(bl, d_mask, nx, ny, nz, dx, true, st))) return rc;
     const int nL = bl.nL, nchunks = bl.nchunks;
     if (nL <= 0) { // empty list: nothing to do, nothing written
         if (steps_done) *steps_done = 0;
@@ -37,8 +37,6 @@ int advect_band_core(double* d_phi, const int32_t* d_mask, const double* d_u, co
         if (margin) *margin = HUGE_VAL;
         return LSF_OK;
     }
-    // (a grid whose brick keys do not fit 32 bits keeps the memory order: only the locality of a chunk depends on the order)
-    if ((rc = band_list_sort(bl, bl.keys_fit(), st))) return rc;
     const int* L = bl.L;
     const int nb = std::min(ADV_SCAN_BLOCKS, cdiv(nL, 256)); // blocks of the scan and of the closing pass
     if ((rc = ws(c.slot[S_PART2], (size_t)nb * 24))) return rc;

@@ -1,6 +1,6 @@
 // lsf_host_cut_cells_band.hpp -- host side of lsf_cut_cells_band (kernel and design: lsf_cut_cells_band.hpp; argument checks:
 // lsf_host_args_cut.hpp): the list, the control words, the two launches over it and the finish of the per-block partials in block
-// order.  Included by lsf_api.hip inside its anonymous namespace.
+// order (the list, the flags and the counts through lsf_host_band.hpp).  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
 
 // the arguments have passed cut_cells_args_ok.  volume, vof_min and info are written on LSF_OK only.  Returns after the stream is
@@ -12,7 +12,7 @@ int cut_cells_core(const double* d_phi, const int32_t* d_mask, int nx, int ny, i
     int rc;
     Ctx& c = ctx();
     BandList bl;
-    if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, dx, st))) return rc;
+    if ((rc = band_list_build(bl, d_mask, nx, ny, nz, dx, true, st))) return rc;
     const int nL = bl.nL, nchunks = bl.nchunks;
     if (nL <= 0) { // empty list: nothing written
         if (volume) *volume = 0.0;
@@ -20,9 +20,6 @@ int cut_cells_core(const double* d_phi, const int32_t* d_mask, int nx, int ny, i
         if (info) info[0] = info[1] = info[2] = info[3] = info[4] = 0;
         return LSF_OK;
     }
-    // (a grid whose brick keys do not fit 32 bits keeps the memory order: the order of the sum is then that one, still a function of
-    // the mask alone)
-    if ((rc = band_list_sort(bl, bl.keys_fit(), st))) return rc;
     // per block one fp64 partial and one 64-bit key (S_PART), four counts (S_PART2)
     if ((rc = ws(c.slot[S_PART], (size_t)nchunks * 2 * sizeof(double)))) return rc;
     if ((rc = ws(c.slot[S_PART2], (size_t)nchunks * CC_NCNT * sizeof(unsigned long long)))) return rc;
@@ -35,39 +32,29 @@ int cut_cells_core(const double* d_phi, const int32_t* d_mask, int nx, int ny, i
     const dim3 grid((unsigned)nchunks), blk(MB_CH);
     // the validation pass of lsf_measure_band comes first; the cell pass leaves at once, before its stores, when it counted anything
     hipLaunchKernelGGL((k_measure_check<false>), grid, blk, 0, st, d_phi, (const double*)nullptr, (const int*)bl.L, nL, nx, ny, iso, ctl);
-#define LSF_CC_CALL(HV, HA, HB) \
-    hipLaunchKernelGGL((k_cut_cells_band<HV, HA, HB>), grid, blk, 0, st, d_phi, d_mask, d_vof, d_ax, d_ay, d_az, d_bx, d_by, d_bz, (const int*)bl.L, \
-                       nL, nx, ny, nz, iso, (const unsigned long long*)ctl, part, key, cnt)
-    switch ((d_vof ? 4 : 0) | (d_ax ? 2 : 0) | (d_bx ? 1 : 0)) {
-    case 0: LSF_CC_CALL(false, false, false); break;
-    case 1: LSF_CC_CALL(false, false, true); break;
-    case 2: LSF_CC_CALL(false, true, false); break;
-    case 3: LSF_CC_CALL(false, true, true); break;
-    case 4: LSF_CC_CALL(true, false, false); break;
-    case 5: LSF_CC_CALL(true, false, true); break;
-    case 6: LSF_CC_CALL(true, true, false); break;
-    default: LSF_CC_CALL(true, true, true); break;
-    }
-#undef LSF_CC_CALL
+    with_flags(
+        [&](auto HV, auto HA, auto HB) {
+            hipLaunchKernelGGL((k_cut_cells_band<decltype(HV)::value, decltype(HA)::value, decltype(HB)::value>), grid, blk, 0, st, d_phi, d_mask,
+                               d_vof, d_ax, d_ay, d_az, d_bx, d_by, d_bz, (const int*)bl.L, nL, nx, ny, nz, iso, (const unsigned long long*)ctl, part,
+                               key, cnt);
+        },
+        d_vof != nullptr, d_ax != nullptr, d_bx != nullptr);
     HIPCHK(hipGetLastError());
-    unsigned long long bad[MS_CTL_LEN];
+    unsigned long long bad[MS_CTL_LEN], n[CC_NCNT];
     std::vector<double> hp((size_t)nchunks * 2);
-    std::vector<unsigned long long> hc((size_t)nchunks * CC_NCNT);
     HIPCHK(hipMemcpyAsync(bad, ctl, sizeof bad, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hc.data(), cnt, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = block_counts_finish(cnt, nchunks, CC_NCNT, n, nullptr, st))) return rc; // (the third copy; synchronises)
     if (bad[MS_BAD_F])
         return fail(LSF_ERR_INVALID, "lsf_cut_cells_band: " + std::to_string(bad[MS_BAD_F]) +
                                          " crossed edge(s) of listed cells with a non-finite phi - iso on an endpoint");
     double tot = 0.0;
-    unsigned long long kmin = 0x7ff0000000000000ull, n[CC_NCNT] = {0, 0, 0, 0};
+    unsigned long long kmin = 0x7ff0000000000000ull;
     for (int b = 0; b < nchunks; ++b) { // block order
         unsigned long long k;
         memcpy(&k, &hp[(size_t)nchunks + b], sizeof k);
         tot = tot + hp[b];
         kmin = k < kmin ? k : kmin;
-        for (int m = 0; m < CC_NCNT; ++m) n[m] += hc[(size_t)b * CC_NCNT + m];
     }
     if (getenv("LSF_TRACE"))
         fprintf(stderr, "[lsf] cut cells on the band: %d list cells (%.2f %% of the grid), %d chunks, %llu cut, %llu full, %llu open, %llu clamped\n",

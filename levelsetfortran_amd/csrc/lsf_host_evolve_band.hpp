@@ -1,6 +1,6 @@
 // lsf_host_evolve_band.hpp -- host side of lsf_evolve_band and lsf_evolve_band_curv (kernels and design: lsf_evolve_band.hpp; the
 // stage with the curvature term: lsf_evolve_band_curv.hpp; lsf_evolve_band is bcurv = clamp = 0; argument checks: lsf_host_args.hpp): the scan of the
-// inputs over all points, the first list, the steps (stages and sweeps enqueued on the resident list), the checks (one 64-byte
+// inputs over all points, the first list (lsf_host_band.hpp), the steps (stages and sweeps enqueued on the resident list), the checks (one 64-byte
 // record read per check) and the rebuilds.  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
 
@@ -38,7 +38,7 @@ int evolve_band_core(double* d_phi, int32_t* d_mask, const double* d_u, const do
     const size_t n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
     const double core_dx = core * dx, far = (core + (double)ring) * dx;
     BandList bl;
-    if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, dx, st))) return rc;
+    if ((rc = band_list_build(bl, d_mask, nx, ny, nz, dx, true, st))) return rc;
     if (bl.nL <= 0) { // empty list: the mask is normalised (all 0), nothing else is written
         HIPCHK(hipMemsetAsync(d_mask, 0, n * sizeof(int32_t), st));
         HIPCHK(hipStreamSynchronize(st));
@@ -50,7 +50,6 @@ int evolve_band_core(double* d_phi, int32_t* d_mask, const double* d_u, const do
         if (margin) *margin = HUGE_VAL;
         return LSF_OK;
     }
-    if ((rc = band_list_sort(bl, bl.keys_fit(), st))) return rc;
     // the stage buffers are not the staging of the list build (S_PONG): a rebuild stages a list while they hold the field
     if ((rc = ws(c.slot[S_PONG2], n * sizeof(double)))) return rc;
     if (rk3 && (rc = ws(c.slot[S_PONG3], n * sizeof(double)))) return rc;
@@ -113,9 +112,8 @@ int evolve_band_core(double* d_phi, int32_t* d_mask, const double* d_u, const do
         hipLaunchKernelGGL(k_evb_dilate, gl, b256, 0, st, (const double*)d_phi, L, nL, nx, ny, nz, core_dx, ring, scratch);
         hipLaunchKernelGGL(k_evb_leave, gl, b256, 0, st, L, nL, (const double*)d_phi, w1, w2, (const int32_t*)scratch, d_mask);
         BandList nw;
-        if ((r = band_list_count<true>(nw, nullptr, scratch, nx, ny, nz, dx, st))) return r; // (waits: the old list is no longer in use)
+        if ((r = band_list_build(nw, scratch, nx, ny, nz, dx, true, st))) return r; // (waits: the old list is no longer in use)
         if (nw.nL <= 0) return fail(LSF_ERR_HIP, "lsf_evolve_band: a rebuild found no core cell"); // (cannot be: the margin cell is one)
-        if ((r = band_list_sort(nw, nw.keys_fit(), st))) return r;
         bl = nw;
         if ((r = adopt())) return r;
         const dim3 gn((unsigned)nchunks);
@@ -155,12 +153,12 @@ int evolve_band_core(double* d_phi, int32_t* d_mask, const double* d_u, const do
                 hipLaunchKernelGGL(k_rb_gather, gl, b256, 0, st, L, (const double*)cur, nL, ps);
                 for (int q = 0; q < reinit_sweeps; ++q) { // (the sums of squares go to the partials of the stages: written, never read)
                     double* other = cur == d_phi ? w1 : d_phi;
-                    if (strict)
-                        hipLaunchKernelGGL((k_reinit_band<true>), gl, b256, 0, st, (const double*)cur, other, (const double*)ps, L, nL, nx, ny, nz, dx, h,
-                                           (double*)part, ctl);
-                    else
-                        hipLaunchKernelGGL((k_reinit_band<false>), gl, b256, 0, st, (const double*)cur, other, (const double*)ps, L, nL, nx, ny, nz, dx, h,
-                                           (double*)part, ctl);
+                    with_flags(
+                        [&](auto S) {
+                            hipLaunchKernelGGL((k_reinit_band<decltype(S)::value>), gl, b256, 0, st, (const double*)cur, other, (const double*)ps, L, nL,
+                                               nx, ny, nz, dx, h, (double*)part, ctl);
+                        },
+                        strict);
                     cur = other;
                 }
             }

@@ -1,6 +1,6 @@
 // lsf_host_extend_band.hpp -- host side of lsf_extend_field_band (kernels and design: lsf_extend_band.hpp; argument checks: lsf_host_args.hpp): the list, the
-// plan pass with its error counts, the Jacobi passes enqueued CHECK_EVERY at a time, and the final count.  Included by lsf_api.hip
-// inside its anonymous namespace.
+// plan pass with its error counts, the Jacobi passes enqueued CHECK_EVERY at a time, and the final count (the list, the pass driver and
+// the finish of the counts: lsf_host_band.hpp).  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
 
 // the arguments have passed extend_band_args_ok.  passes_done, changed_trace and info are written on LSF_OK only, q after every error
@@ -11,11 +11,9 @@ int extend_band_core(double* d_q, const double* d_phi, const int32_t* d_mask, co
     int rc;
     Ctx& c = ctx();
     BandList bl;
-    if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, dx, st))) return rc;
+    if ((rc = band_list_build(bl, d_mask, nx, ny, nz, dx, true, st))) return rc;
     const int nL = bl.nL, nchunks = bl.nchunks;
     if (nL <= 0) return fail(LSF_ERR_INVALID, "lsf_extend_field_band: the list is empty (no interior point with mask == 1)");
-    // (a grid whose brick keys do not fit 32 bits keeps the memory order: only the locality of a chunk depends on the order)
-    if ((rc = band_list_sort(bl, bl.keys_fit(), st))) return rc;
     const int* L = bl.L;
     if ((rc = ws(c.slot[S_XB_NB], (size_t)nL * 3 * sizeof(int)))) return rc;
     if ((rc = ws(c.slot[S_XB_WT], (size_t)nL * 3 * sizeof(double)))) return rc;
@@ -36,12 +34,9 @@ int extend_band_core(double* d_q, const double* d_phi, const int32_t* d_mask, co
     // the plan: read-only on the caller's arrays; its counts decide the errors
     hipLaunchKernelGGL(k_extb_plan, grid, blk, 0, st, (const double*)d_q, d_phi, d_mask, d_known, L, nL, nx, ny, nz, far, nb, wt, fz, part);
     HIPCHK(hipGetLastError());
-    std::vector<unsigned long long> h((size_t)nchunks * EXTB_NPART);
-    HIPCHK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    unsigned long long nfrozen = 0, nbadq = 0, nbadphi = 0;
-    for (int b = 0; b < nchunks; ++b) // integer counts: no order in the result
-        nfrozen += h[(size_t)b * EXTB_NPART], nbadq += h[(size_t)b * EXTB_NPART + 1], nbadphi += h[(size_t)b * EXTB_NPART + 2];
+    unsigned long long plan[EXTB_NPART];
+    if ((rc = block_counts_finish(part, nchunks, EXTB_NPART, plan, nullptr, st))) return rc;
+    const unsigned long long nfrozen = plan[0], nbadq = plan[1], nbadphi = plan[2];
     if (nbadphi)
         return fail(LSF_ERR_INVALID, "lsf_extend_field_band: " + std::to_string(nbadphi) +
                                          " list cell(s) see a non-finite phi at themselves or at one of their six neighbours");
@@ -54,38 +49,23 @@ int extend_band_core(double* d_q, const double* d_phi, const int32_t* d_mask, co
     // the passes, a batch enqueued ahead of the device; the kernels behind a pass that changed nothing return at once, and the host
     // reads the counts of the batch -- which are the trace -- once
     std::vector<int64_t> trace;
-    unsigned long long hc[CHECK_EVERY];
-    bool stopped = false;
-    while (!stopped && (int)trace.size() < max_passes) {
-        const int batch = std::min(CHECK_EVERY, max_passes - (int)trace.size());
-        HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)batch * sizeof(unsigned long long), st));
-        for (int p = 0; p < batch; ++p) {
-            hipLaunchKernelGGL(k_extb_compute, grid, blk, 0, st, (const double*)d_q, L, (const int*)nb, (const double*)wt, (const unsigned char*)fz, nL,
-                               nv, chg, (const unsigned long long*)d_cnt, p);
-            hipLaunchKernelGGL(k_extb_commit, grid, blk, 0, st, d_q, L, (const double*)nv, (const unsigned char*)chg, nL, d_cnt, p);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hc, d_cnt, (size_t)batch * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int p = 0; p < batch && !stopped; ++p) {
-            trace.push_back((int64_t)hc[p]);
-            stopped = hc[p] == 0; // that pass is counted
-        }
-    }
+    rc = band_passes(trace, d_cnt, max_passes, 0, st, [&](int p) {
+        hipLaunchKernelGGL(k_extb_compute, grid, blk, 0, st, (const double*)d_q, L, (const int*)nb, (const double*)wt, (const unsigned char*)fz, nL, nv,
+                           chg, (const unsigned long long*)d_cnt, p);
+        hipLaunchKernelGGL(k_extb_commit, grid, blk, 0, st, d_q, L, (const double*)nv, (const unsigned char*)chg, nL, d_cnt, p);
+    });
+    if (rc) return rc;
 
     hipLaunchKernelGGL(k_extb_count, grid, blk, 0, st, (const double*)d_q, L, (const unsigned char*)fz, nL, part);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h.data(), part, (size_t)nchunks * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    unsigned long long nreached = 0, nunreached = 0;
-    for (int b = 0; b < nchunks; ++b) nreached += h[(size_t)b * 2], nunreached += h[(size_t)b * 2 + 1];
+    unsigned long long reach[2]; // reached, unreached
+    if ((rc = block_counts_finish(part, nchunks, 2, reach, nullptr, st))) return rc;
+    const unsigned long long nreached = reach[0], nunreached = reach[1];
     if (getenv("LSF_TRACE"))
         fprintf(stderr, "[lsf] extend on the band: %d list cells (%.2f %% of the grid), %d chunks, %llu frozen, %d pass(es), last count %lld, "
                         "%llu unreached\n",
                 nL, 100.0 * nL / (double)bl.n, nchunks, nfrozen, (int)trace.size(), (long long)trace.back(), nunreached);
-    if (passes_done) *passes_done = (int)trace.size();
-    if (changed_trace)
-        for (int p = 0; p < (int)trace.size() && p < trace_cap; ++p) changed_trace[p] = trace[p];
+    passes_report(trace, passes_done, changed_trace, trace_cap);
     if (info) info[0] = nL, info[1] = (int64_t)nfrozen, info[2] = (int64_t)nreached, info[3] = (int64_t)nunreached;
     return LSF_OK;
 }

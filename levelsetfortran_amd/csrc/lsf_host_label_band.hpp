@@ -1,6 +1,6 @@
 // lsf_host_label_band.hpp -- host side of lsf_label_band (kernels and design: lsf_label_band.hpp; argument checks: lsf_host_args.hpp): the list, the check
-// launch with its error counts, the link / flatten passes enqueued CHECK_EVERY at a time, and the table of components.  Included by
-// lsf_api.hip inside its anonymous namespace.
+// launch with its error counts, the link / flatten passes enqueued CHECK_EVERY at a time, and the table of components (the list, the
+// pass driver and the finish of the counts: lsf_host_band.hpp).  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
 
 // the arguments have passed label_band_args_ok.  comp, ncomp and info are host arrays and are written on LSF_OK only, d_label after every
@@ -11,7 +11,7 @@ int label_band_core(const double* d_phi, const int32_t* d_mask, int32_t* d_label
     int rc;
     Ctx& c = ctx();
     BandList bl;
-    if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, 1.0, st))) return rc;
+    if ((rc = band_list_build(bl, d_mask, nx, ny, nz, 1.0, true, st))) return rc;
     const int nL = bl.nL, nchunks = bl.nchunks;
     if (nL <= 0) { // empty list: nothing to do, nothing written
         if (info)
@@ -19,8 +19,6 @@ int label_band_core(const double* d_phi, const int32_t* d_mask, int32_t* d_label
         if (ncomp) *ncomp = 0;
         return LSF_OK;
     }
-    // (a grid whose brick keys do not fit 32 bits keeps the memory order: only the locality of a chunk depends on the order)
-    if ((rc = band_list_sort(bl, bl.keys_fit(), st))) return rc;
     const int* L = bl.L;
     int* label = (int*)d_label;
     constexpr int NPART = LB_NCHECK > LB_NROOTS ? LB_NCHECK : LB_NROOTS;
@@ -35,12 +33,9 @@ int label_band_core(const double* d_phi, const int32_t* d_mask, int32_t* d_label
     // the check: read-only on the caller's arrays; its counts decide the errors
     hipLaunchKernelGGL(k_label_check, grid, blk, 0, st, d_phi, L, nL, iso, part);
     HIPCHK(hipGetLastError());
-    std::vector<unsigned long long> h((size_t)nchunks * NPART);
-    HIPCHK(hipMemcpyAsync(h.data(), part, (size_t)nchunks * LB_NCHECK * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    unsigned long long nbad = 0, nin = 0, nout = 0;
-    for (int b = 0; b < nchunks; ++b) // integer counts: no order in the result
-        nbad += h[(size_t)b * LB_NCHECK], nin += h[(size_t)b * LB_NCHECK + 1], nout += h[(size_t)b * LB_NCHECK + 2];
+    unsigned long long chk[LB_NCHECK];
+    if ((rc = block_counts_finish(part, nchunks, LB_NCHECK, chk, nullptr, st))) return rc;
+    const unsigned long long nbad = chk[0], nin = chk[1], nout = chk[2];
     if (nbad) return fail(LSF_ERR_INVALID, "lsf_label_band: " + std::to_string(nbad) + " list cell(s) hold a non-finite phi - iso");
     const unsigned long long nlabelled = side == LSF_LABEL_BOTH ? nin + nout : side == LSF_LABEL_INSIDE ? nin : nout;
 
@@ -48,35 +43,28 @@ int label_band_core(const double* d_phi, const int32_t* d_mask, int32_t* d_label
     hipLaunchKernelGGL(k_label_init, grid, blk, 0, st, d_phi, L, nL, iso, side, label);
     // the passes, a batch enqueued ahead of the device; the kernels behind a pass that linked nothing return at once, and the host
     // reads the counts of the batch and the chase flag once
-    int passes = 0;
-    unsigned long long last = 0, hc[CHECK_EVERY + 1];
-    bool stopped = false;
-    while (!stopped && passes < max_passes) {
-        const int batch = std::min(CHECK_EVERY, max_passes - passes);
-        HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)batch * sizeof(unsigned long long), st));
-        for (int p = 0; p < batch; ++p) {
+    std::vector<int64_t> trace;
+    rc = band_passes(
+        trace, d_cnt, max_passes, CHECK_EVERY + 1, st,
+        [&](int p) {
             hipLaunchKernelGGL(k_label_link, grid, blk, 0, st, d_phi, d_mask, L, nL, nx, ny, nz, iso, label, d_cnt, p, d_flag);
             hipLaunchKernelGGL(k_label_flatten, grid, blk, 0, st, L, nL, label, (const unsigned long long*)d_cnt, p, d_flag);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hc, d_cnt, (CHECK_EVERY + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if ((int)hc[CHECK_EVERY] != 0)
+        },
+        [](const unsigned long long* hc) {
+            if ((int)hc[CHECK_EVERY] == 0) return (int)LSF_OK;
             return fail(LSF_ERR_HIP, "lsf_label_band: a chase met a word that is no forest word, or ran beyond the number of list cells "
                                      "(label was written by someone else during the call?)");
-        for (int p = 0; p < batch && !stopped; ++p) {
-            ++passes, last = hc[p];
-            stopped = hc[p] == 0; // that pass is counted
-        }
-    }
+        });
+    if (rc) return rc;
+    const int passes = (int)trace.size();
+    const unsigned long long last = (unsigned long long)trace.back(); // (max_passes >= 1: there is one)
 
     // the roots of each class
     hipLaunchKernelGGL(k_label_roots, grid, blk, 0, st, d_phi, L, nL, iso, (const int*)label, part);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h.data(), part, (size_t)nchunks * LB_NROOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    unsigned long long rin = 0, rout = 0;
-    for (int b = 0; b < nchunks; ++b) rin += h[(size_t)b * LB_NROOTS], rout += h[(size_t)b * LB_NROOTS + 1];
+    unsigned long long roots_of[LB_NROOTS];
+    if ((rc = block_counts_finish(part, nchunks, LB_NROOTS, roots_of, nullptr, st))) return rc;
+    const unsigned long long rin = roots_of[0], rout = roots_of[1];
     const size_t nc = (size_t)(rin + rout);
     const int rows = (int)std::min(nc, (size_t)comp_cap);
     std::vector<int64_t> table((size_t)rows * LB_ROW);

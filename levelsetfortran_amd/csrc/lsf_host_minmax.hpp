@@ -1,5 +1,6 @@
 // lsf_host_minmax.hpp -- host side of narrowBand (subs.f90:178-207) and of the min/max flow (set3d.f90:394-462): the exact fixed-point
-// executor, the tile-wavefront fallback and the Jacobi ordering.  Included by lsf_api.hip inside its anonymous namespace.
+// executor, the tile-wavefront fallback and the Jacobi ordering, and the executor on the band, whose list is built by the two phases of
+// lsf_host_band.hpp with a decision between them.  Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
 
 int narrowband_core(const double* d_phi, int32_t* d_nb, int32_t* d_sb, size_t n, double dx, hipStream_t st)
@@ -146,71 +147,6 @@ int minmax_core_impl(double* d_phi, int32_t* d_nb, int32_t* d_sb, int nx, int ny
     if (bufs[nit & 1] != d_phi)
         HIPCHK(hipMemcpyAsync(d_phi, bufs[nit & 1], n * sizeof(double), hipMemcpyDeviceToDevice, st));
     return stop.verdict(rms_trace, trace_cap, iters_done, "RMS became NaN (the reference STOPs here, set3d.f90:458)");
-}
-
-// The list of cells a band executor works on (the min/max flow below, lsf_host_reinit_band.hpp), built once per call in two phases with
-// the caller's decision between them.  Staging: the first n ints of S_PONG -- asked for at n doubles, the size at which the dense min/max
-// executors and the reinit on the band want their second field, so that no call frees and allocates the buffer a second time.
-struct BandList {
-    int nL = 0, nchunks = 0;       // cells (after band_list_count), chunks of MB_CH cells
-    int* L = nullptr;              // S_MB_L: point indices, sorted by brick key or in memory order (after band_list_sort)
-    const unsigned* key = nullptr; // S_MB_KEY: the sorted brick keys; NULL for a list in memory order
-    size_t n = 0;                  // points of the grid
-    long nblk = 0;                 // blocks of the scan
-    int nx = 0, ny = 0, nz = 0, nbx = 0, nby = 0; // ... bricks along x, y
-    int *staging = nullptr, *counts = nullptr, *offsets = nullptr;
-    // brick keys are 32-bit: beyond that a list can only stay in memory order
-    bool keys_fit() const { return (double)nbx * nby * cdiv(nz + 1, 4) * 256.0 <= 4.0e9; }
-};
-// phase 1: the cells per scan block and their number.  MASK_ONLY: the cells of the caller's mask; otherwise the cells that can ever be
-// in the band of phi (k_mb_collect).  Waits for the device.
-template <bool MASK_ONLY>
-int band_list_count(BandList& bl, const double* d_phi, const int32_t* d_mask, int nx, int ny, int nz, double dx, hipStream_t st)
-{
-    int rc;
-    Ctx& c = ctx();
-    bl.n = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-    bl.nx = nx, bl.ny = ny, bl.nz = nz, bl.nbx = cdiv(nx + 1, 8), bl.nby = cdiv(ny + 1, 8);
-    bl.nblk = (long)((bl.n + MB_SCAN - 1) / MB_SCAN);
-    if ((rc = ws(c.slot[S_PONG], bl.n * sizeof(double)))) return rc;
-    if ((rc = ws(c.slot[S_MB_CNT], (size_t)(2 * bl.nblk + 8) * sizeof(int)))) return rc;
-    bl.staging = (int*)c.slot[S_PONG].p, bl.counts = (int*)c.slot[S_MB_CNT].p;
-    bl.offsets = bl.counts + ((bl.nblk + 3) & ~3L); // 16-byte aligned like counts (k_mb_offsets moves vectors)
-    hipLaunchKernelGGL(k_mb_collect<MASK_ONLY>, dim3((unsigned)bl.nblk), dim3(256), 0, st, MASK_ONLY ? nullptr : d_phi, d_mask, nx, ny, nz, dx,
-                       bl.staging, bl.counts);
-    hipLaunchKernelGGL(k_mb_offsets, dim3(1), dim3(1024), 0, st, (const int*)bl.counts, bl.nblk, bl.offsets);
-    HIPCHK(hipMemcpyAsync(&bl.nL, bl.offsets + bl.nblk, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    bl.nchunks = (bl.nL + MB_CH - 1) / MB_CH;
-    return LSF_OK;
-}
-// phase 2 (nL > 0): the list in memory order and its brick keys, then -- `sort`, which needs keys_fit() -- sorted by key.  Both pairs of
-// arrays live in S_MB_KEY and S_MB_L; the sort's temporary storage is the staging buffer, free again once its segments have been
-// gathered (in stream order).
-int band_list_sort(BandList& bl, bool sort, hipStream_t st)
-{
-    int rc;
-    Ctx& c = ctx();
-    const size_t nL = (size_t)bl.nL;
-    if ((rc = ws(c.slot[S_MB_L], nL * sizeof(int)))) return rc;
-    if ((rc = ws(c.slot[S_MB_KEY], nL * 3 * sizeof(int)))) return rc;
-    bl.L = (int*)c.slot[S_MB_L].p;
-    unsigned* key_in = (unsigned*)c.slot[S_MB_KEY].p;
-    unsigned* key = key_in + nL;
-    int* L_in = (int*)(key + nL);
-    hipLaunchKernelGGL(k_mb_gather, dim3((unsigned)((bl.nblk + 3) / 4)), dim3(256), 0, st, (const int*)bl.staging, (const int*)bl.counts,
-                       (const int*)bl.offsets, bl.nblk, bl.nx + 1, bl.ny + 1, bl.nbx, bl.nby, sort ? L_in : bl.L, key_in);
-    if (!sort) return LSF_OK;
-    size_t tmp_bytes = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key_in, key, L_in, bl.L, nL, 0, 32, st));
-    void* tmp = bl.staging;
-    if (tmp_bytes > bl.n * sizeof(int)) { // tiny grids
-        if ((rc = ws(c.slot[S_MB_TMP], tmp_bytes))) return rc;
-        tmp = c.slot[S_MB_TMP].p;
-    }
-    HIPCHK(rocprim::radix_sort_pairs(tmp, tmp_bytes, key_in, key, L_in, bl.L, nL, 0, 32, st));
-    bl.key = key;
-    return LSF_OK;
 }
 
 // The min/max flow on the narrow band only (lsf_minmax_band.hpp): the list of cells that can ever be in the band is built once

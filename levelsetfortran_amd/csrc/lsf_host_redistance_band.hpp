@@ -1,6 +1,7 @@
 // lsf_host_redistance_band.hpp -- host side of lsf_redistance_band (kernels and design: lsf_redistance_band.hpp; argument checks:
 // lsf_host_args_redistance.hpp): the list, the foot launch with its error counts, the seed, the Jacobi passes of the fill enqueued
-// CHECK_EVERY at a time, and the finish.  Included by lsf_api.hip inside its anonymous namespace.
+// CHECK_EVERY at a time, and the finish (the list, the pass driver and the finish of the counts: lsf_host_band.hpp).  Included by
+// lsf_api.hip inside its anonymous namespace.
 #pragma once
 
 // the arguments have passed redistance_band_args_ok.  passes_done, changed_trace, change and info are written on LSF_OK only, phi after
@@ -11,11 +12,9 @@ int redistance_band_core(double* d_phi, const int32_t* d_mask, int nx, int ny, i
     int rc;
     Ctx& c = ctx();
     BandList bl;
-    if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, dx, st))) return rc;
+    if ((rc = band_list_build(bl, d_mask, nx, ny, nz, dx, true, st))) return rc;
     const int nL = bl.nL, nchunks = bl.nchunks;
     if (nL <= 0) return fail(LSF_ERR_INVALID, "lsf_redistance_band: the list is empty (no interior point with mask == 1)");
-    // (a grid whose brick keys do not fit 32 bits keeps the memory order: only the locality of a chunk depends on the order)
-    if ((rc = band_list_sort(bl, bl.keys_fit(), st))) return rc;
     const int* L = bl.L;
     if ((rc = ws(c.slot[S_RD_VAL], (size_t)nL * 3 * sizeof(double)))) return rc;
     if ((rc = ws(c.slot[S_RD_FLAG], (size_t)nL * RDB_NFLAG))) return rc;
@@ -34,12 +33,8 @@ int redistance_band_core(double* d_phi, const int32_t* d_mask, int nx, int ny, i
     // the feet: read-only on the caller's arrays; the counts decide the errors
     hipLaunchKernelGGL(k_rdb_foot, grid, blk, 0, st, G, L, nL, iters, tol_dx, near_dx, dist, old, fz, neg, nbits, part);
     HIPCHK(hipGetLastError());
-    std::vector<unsigned long long> h((size_t)nchunks * RDB_NPART);
-    HIPCHK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    unsigned long long tot[RDB_NPART] = {};
-    for (int b = 0; b < nchunks; ++b) // integer counts: no order in the result
-        for (int q = 0; q < RDB_NPART; ++q) tot[q] += h[(size_t)b * RDB_NPART + q];
+    unsigned long long tot[RDB_NPART];
+    if ((rc = block_counts_finish(part, nchunks, RDB_NPART, tot, nullptr, st))) return rc;
     if (tot[6]) return fail(LSF_ERR_INVALID, "lsf_redistance_band: " + std::to_string(tot[6]) + " list cell(s) hold a non-finite phi");
     if (tot[0] == 0) return fail(LSF_ERR_INVALID, "lsf_redistance_band: no frozen cell (no list cell whose foot was found closer than near*dx)");
 
@@ -47,44 +42,26 @@ int redistance_band_core(double* d_phi, const int32_t* d_mask, int nx, int ny, i
     // the passes, a batch enqueued ahead of the device; the kernels behind a pass that lowered nothing return at once, and the host
     // reads the counts of the batch -- which are the trace -- once
     std::vector<int64_t> trace;
-    unsigned long long hc[CHECK_EVERY];
-    bool stopped = false;
-    while (!stopped && (int)trace.size() < max_passes) {
-        const int batch = std::min(CHECK_EVERY, max_passes - (int)trace.size());
-        HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)batch * sizeof(unsigned long long), st));
-        for (int p = 0; p < batch; ++p) {
-            hipLaunchKernelGGL(k_rdb_compute, grid, blk, 0, st, (const double*)d_phi, L, (const unsigned char*)fz, (const unsigned char*)nbits, nL, nx,
-                               ny, dx, nv, chg, (const unsigned long long*)d_cnt, p);
-            hipLaunchKernelGGL(k_extb_commit, grid, blk, 0, st, d_phi, L, (const double*)nv, (const unsigned char*)chg, nL, d_cnt, p);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hc, d_cnt, (size_t)batch * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int p = 0; p < batch && !stopped; ++p) {
-            trace.push_back((int64_t)hc[p]);
-            stopped = hc[p] == 0; // that pass is counted
-        }
-    }
+    rc = band_passes(trace, d_cnt, max_passes, 0, st, [&](int p) {
+        hipLaunchKernelGGL(k_rdb_compute, grid, blk, 0, st, (const double*)d_phi, L, (const unsigned char*)fz, (const unsigned char*)nbits, nL, nx, ny,
+                           dx, nv, chg, (const unsigned long long*)d_cnt, p);
+        hipLaunchKernelGGL(k_extb_commit, grid, blk, 0, st, d_phi, L, (const double*)nv, (const unsigned char*)chg, nL, d_cnt, p);
+    });
+    if (rc) return rc;
 
     hipLaunchKernelGGL(k_rdb_finish, grid, blk, 0, st, d_phi, L, (const double*)dist, (const double*)old, (const unsigned char*)fz,
                        (const unsigned char*)neg, nL, part);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h.data(), part, (size_t)nchunks * RDB_NFIN * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    unsigned long long nfilled = 0, nunreached = 0, maxbits = 0;
-    for (int b = 0; b < nchunks; ++b) {
-        nfilled += h[(size_t)b * RDB_NFIN], nunreached += h[(size_t)b * RDB_NFIN + 1];
-        maxbits = std::max(maxbits, h[(size_t)b * RDB_NFIN + 2]);
-    }
+    unsigned long long fin[RDB_NFIN]; // filled, unreached, the largest change as a bit pattern
+    if ((rc = block_counts_finish(part, nchunks, RDB_NFIN, fin, nullptr, st, true))) return rc;
+    const unsigned long long nfilled = fin[0], nunreached = fin[1];
     double maxchange;
-    std::memcpy(&maxchange, &maxbits, sizeof(double));
+    std::memcpy(&maxchange, &fin[2], sizeof(double));
     if (getenv("LSF_TRACE"))
         fprintf(stderr, "[lsf] redistance on the band: %d list cells (%.2f %% of the grid), %d chunks, %llu frozen, %d pass(es), last count %lld, "
                         "%llu unreached, largest change %.3e\n",
                 nL, 100.0 * nL / (double)bl.n, nchunks, tot[0], (int)trace.size(), (long long)trace.back(), nunreached, maxchange);
-    if (passes_done) *passes_done = (int)trace.size();
-    if (changed_trace)
-        for (int p = 0; p < (int)trace.size() && p < trace_cap; ++p) changed_trace[p] = trace[p];
+    passes_report(trace, passes_done, changed_trace, trace_cap);
     if (change) *change = maxchange;
     if (info) {
         info[0] = nL, info[1] = (int64_t)tot[0], info[2] = (int64_t)nfilled, info[3] = (int64_t)nunreached;

@@ -1,5 +1,5 @@
-// lsf_host_reinit_band.hpp -- host side of lsf_reinit_band (kernels and design: lsf_reinit_band.hpp).  Included by lsf_api.hip inside
-// its anonymous namespace.
+// lsf_host_reinit_band.hpp -- host side of lsf_reinit_band (kernels and design: lsf_reinit_band.hpp; the list: lsf_host_band.hpp).
+// Included by lsf_api.hip inside its anonymous namespace.
 #pragma once
 
 int reinit_band_core(double* d_phi, const double* d_phiS, const int32_t* d_mask, int nx, int ny, int nz, int iter, double dx, double h,
@@ -23,16 +23,13 @@ int reinit_band_core(double* d_phi, const double* d_phiS, const int32_t* d_mask,
     const bool trace = getenv("LSF_TRACE") != nullptr;
     const double t_build0 = trace ? now_s() : 0.0;
     BandList bl;
-    if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, dx, st))) return rc;
+    if ((rc = band_list_build(bl, d_mask, nx, ny, nz, dx, true, st))) return rc;
     const int nL = bl.nL, nchunks = bl.nchunks;
     if (nL <= 0) return LSF_OK; // empty list: nothing to do, nothing written
     const int max_sweeps = iter + 1; // DO n=0,iter (subs.f90:735)
     if ((rc = ws(c.slot[S_RB_PHIS], (size_t)nL * sizeof(double)))) return rc;
     if ((rc = ws(c.slot[S_PART], (size_t)nchunks * sizeof(double)))) return rc;
     if ((rc = ws(c.slot[S_PART2], 256 * sizeof(double)))) return rc;
-    // A grid whose brick keys do not fit 32 bits keeps the memory order: the result does not depend on the order of the list, only the
-    // locality of a chunk does
-    if ((rc = band_list_sort(bl, bl.keys_fit(), st))) return rc;
     const int* L = bl.L;
     double* pong = (double*)bl.staging; // the second field was the staging of the list build, which is over before the field is copied into it
     double* ps = (double*)c.slot[S_RB_PHIS].p;
@@ -53,10 +50,12 @@ int reinit_band_core(double* d_phi, const double* d_phiS, const int32_t* d_mask,
     for (int s = 0; s < max_sweeps; ++s) {
         const double* A = bufs[s & 1];
         double* B = bufs[(s + 1) & 1];
-        if (strict)
-            hipLaunchKernelGGL((k_reinit_band<true>), gl, b256, 0, st, A, B, (const double*)ps, L, nL, nx, ny, nz, dx, h, part, (const int*)stop.ctl);
-        else
-            hipLaunchKernelGGL((k_reinit_band<false>), gl, b256, 0, st, A, B, (const double*)ps, L, nL, nx, ny, nz, dx, h, part, (const int*)stop.ctl);
+        with_flags(
+            [&](auto S) {
+                hipLaunchKernelGGL((k_reinit_band<decltype(S)::value>), gl, b256, 0, st, A, B, (const double*)ps, L, nL, nx, ny, nz, dx, h, part,
+                                   (const int*)stop.ctl);
+            },
+            strict);
         reduce_finish(part, nchunks, part2, (double)nL, tol, stop);
         if (stop.poll(s, max_sweeps)) break;
     }

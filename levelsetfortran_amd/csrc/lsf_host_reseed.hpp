@@ -32,12 +32,8 @@ int reseed_core(const double* d_phi, const int32_t* d_mask, int nx, int ny, int 
     size_t nwork = n;
     const int* L = nullptr;
     if (d_mask) {
-        if ((rc = band_list_count<true>(bl, nullptr, d_mask, nx, ny, nz, dx, st))) return rc;
-        nwork = (size_t)std::max(bl.nL, 0);
-        if (nwork) {
-            if ((rc = band_list_sort(bl, false, st))) return rc;
-            L = bl.L;
-        }
+        if ((rc = band_list_build(bl, d_mask, nx, ny, nz, dx, false, st))) return rc;
+        nwork = (size_t)std::max(bl.nL, 0), L = bl.L; // (an empty list: no L)
     }
     const size_t tilesK = (np + RS_BLOCK - 1) / RS_BLOCK, tilesC = (nwork + RS_BLOCK - 1) / RS_BLOCK;
     if ((rc = ws(c.slot[S_RS_COUNT], n * sizeof(int)))) return rc;

@@ -168,7 +168,7 @@ CENTRE, RADIUS = (0.1, 0.0, -0.1), 0.6  # the sphere of the other band tests
 # case -> (points, width of the mask in cells or None for every point, frozen band in cells)
 CASES = {"small": ((10, 10, 10), 2.1, 1.1), "general": ((40, 33, 27), 4.1, 1.5), "wide": ((40, 33, 27), 8.1, 1.5),
          "interior": ((25, 25, 25), None, 1.5), "onecell": ((10, 10, 10), None, 1.1), "values": ((12, 11, 10), 1.3, 0.8),
-         "onesided": ((40, 33, 27), 4.1, None)}
+         "onesided": ((40, 33, 27), 4.1, None), "stop8": ((40, 33, 27), 2.6, 1.5), "stop9": ((40, 33, 27), 3.1, 1.5)}
 FORMS = ("band", "known")
 
 

@@ -21,7 +21,8 @@ from advect_band_ref import list_of
 from levelsetfortran_amd import fields
 
 DEFAULTS = dict(near=2.5, iters=8, tol=1e-9, max_passes=64)
-CASES = ("baseline", "asymmetric", "cut", "walls", "zeros", "cap1", "cap3", "one_iteration", "flat", "values")
+# cap8, cap9: the baseline (12 passes) cut off on the last pass of the first batch of 8 that the host enqueues, and on the first of the next
+CASES = ("baseline", "asymmetric", "cut", "walls", "zeros", "cap1", "cap3", "cap8", "cap9", "one_iteration", "flat", "values")
 
 
 def _two_spheres(npts, ranges=None, whole=None):
@@ -78,10 +79,8 @@ def inputs(case):
                 for side in (0, -1):
                     sl[a] = side
                     mask[tuple(sl)] = 1
-        elif case == "cap1":
-            kw["max_passes"] = 1
-        elif case == "cap3":
-            kw["max_passes"] = 3
+        elif case in ("cap1", "cap3", "cap8", "cap9"):
+            kw["max_passes"] = int(case[3:])
         elif case == "one_iteration":
             kw["iters"], kw["tol"] = 1, 1e-2  # one Newton step reaches the looser tolerance from some cells and not from others
     phi, mask = np.asfortranarray(phi), np.asfortranarray(mask)

@@ -9,7 +9,10 @@ csrc/lsf_minmax_band.hpp; the host reads the counts of 8 passes at a time, CHECK
   onecell   a list of one frozen cell and one neighbour
   values    (12,11,10): a mask carrying 0, 7, -1 and 1s on wall points
   interior  (25,25,25), every interior point: chosen neighbours on all six walls (never in the list); 30 passes, four batches
-  onesided  general with `known` on the side phi > 0 only: 136 cells stay NaN"""
+  onesided  general with `known` on the side phi > 0 only: 136 cells stay NaN
+  stop8     general with |phi| < 2.6 dx: 3 850 cells; 8 passes: the stop is the last pass of the first batch
+  stop9     general with |phi| < 3.1 dx: 4 612 cells; 9 passes: the stop is the first pass of the second batch
+The edges of a batch: "interior" and "general" at max_passes 7, 8, 9, 16 and 17, and stop8 / stop9 uncapped and capped at their stop."""
 import ctypes
 import functools
 
@@ -26,6 +29,9 @@ CHUNK, CHECK_EVERY = 256, 8
 RUNS = [(c, f) for c in ("small", "general", "onecell", "values", "interior") for f in X.FORMS] + [("onesided", "known")]
 CAPS = [1, 3, 256]
 SEAMS = ["host", "device"]
+# the edges of a batch: caps next to the multiples of CHECK_EVERY, and natural stops on the last pass of a batch and the first of the next
+EDGE_RUNS = [(c, f, cap) for c, f in (("interior", "band"), ("general", "band"), ("general", "known")) for cap in (7, 8, 9, 16, 17)]
+EDGE_RUNS += [("stop8", "band", 256), ("stop8", "band", 8), ("stop9", "band", 256), ("stop9", "band", 9)]
 
 
 @pytest.fixture(scope="module")
@@ -48,7 +54,9 @@ def test_the_cases_are_what_the_docstring_says():
     assert (inner == 0).any() and (inner == 7).any() and (inner == -1).any() and B.list_of(mask).sum() < mask[mask == 1].size
     assert X.want("interior", "band").passes == 30 > 3 * CHECK_EVERY and X.want("interior", "band").cells == 23 ** 3
     assert X.want("onesided", "known").unreached == 136
-    for case, form in RUNS:
+    s8, s9 = X.want("stop8", "band"), X.want("stop9", "band")
+    assert (s8.cells, s8.passes, s8.trace[-2:]) == (3850, CHECK_EVERY, [6, 0]) and (s9.cells, s9.passes, s9.trace[-2:]) == (4612, CHECK_EVERY + 1, [24, 0])
+    for case, form in RUNS + [("stop8", "band"), ("stop9", "band")]:
         q, phi, mask, known, dx, band = X.inputs(case)
         lst = B.list_of(mask)
         assert X.check(q, phi, mask, dx, band=band, known=known if form == "known" else None)[2:] == (0, 0)
@@ -116,6 +124,18 @@ def test_bit_identical_to_the_statement(lsf, case, form, cap, seam):
     lst = B.list_of(mask)
     assert _bits(got[~lst], q0[~lst])  # off the list: the caller's bits
     assert int(np.isnan(got[lst]).sum()) == want.unreached
+
+
+@pytest.mark.parametrize("seam", SEAMS)
+@pytest.mark.parametrize("case,form,cap", EDGE_RUNS)
+def test_batch_edges_bit_identical_to_the_statement(lsf, case, form, cap, seam):
+    """a cap or a stop on the last pass of a batch of CHECK_EVERY, or on the first pass of the next"""
+    want = X.want(case, form, cap)
+    got, rep = _run(lsf, seam, case, form, cap)
+    print(f"{case} {form} cap {cap} {seam}: {rep.passes} passes, trace {rep.trace}; want {want.passes}, {want.trace}; "
+          f"q differs at {int(np.count_nonzero(got.view(np.int64) != want.field.view(np.int64)))} points")
+    assert want.passes == min(cap, X.want(case, form).passes)
+    _assert_equal(got, rep, want, cap)
 
 
 # ---------------------------------------------------------------------------------- 2: streams, run to run

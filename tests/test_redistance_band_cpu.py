@@ -321,6 +321,10 @@ def test_every_gpu_case_reaches_the_path_it_is_named_after():
     assert filled.sum() == 2 and (r.field[filled] > 0).all() and np.signbit(phi[filled]).any()
     assert C.want("cap1").passes == 1 and C.want("cap3").passes == 3 and info["cap3"][3] > 0
     assert C.want("cap3").trace == C.want("baseline").trace[:3]
+    assert C.want("baseline").passes == 12 > 9  # the caps at the edge of a batch of 8 cut a run that would go on
+    for cap in (8, 9):
+        assert C.want(f"cap{cap}").passes == cap and C.want(f"cap{cap}").trace == C.want("baseline").trace[:cap]
+        assert not np.array_equal(C.want(f"cap{cap}").field, C.want("baseline").field)  # (every cell is reached by then: values still fall)
     assert info["one_iteration"][7] > 0 and info["flat"][6] > 0
     assert set(np.unique(C.inputs("values")[1])) == {-1, 0, 1, 7} and info["values"] == info["baseline"]
     assert np.array_equal(C.want("values").field, C.want("baseline").field)
